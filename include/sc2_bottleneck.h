@@ -657,6 +657,52 @@ int sc2_rans_decode_host(const sc2_rans_host_tables *tables, const uint8_t *in, 
                          int n_streams, int64_t n_sym, int32_t *symbols_out, int32_t *status, int n_threads);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Serial context-model scan of the joint autoregressive hierarchical prior (csrc/ar_context.hip).  */
+/* ------------------------------------------------------------------------------------------ */
+/* One workgroup per image walks the B x H x W latent in raster order over pixels [pix0, pix1); per pixel (all bf16 weights,
+ * f32 activations, a fixed reduction order per output that does not depend on B):
+ *   ctx = Wc . gather(y_hat_pad, the 12 causal taps of the 5x5 type-A mask) + bc          (12M -> 2M)
+ *   h1  = lrelu(W1b . ctx + p1[pixel])      p1 = W1[:, :2M] . params + b1, computed before the scan (C1p wide)
+ *   h2  = lrelu(W2 . h1 + b2)   gp = W3 . h2 + b3   scales = gp[:M], means = gp[M:]
+ *   index = gc_symbols_indexes' table search on max(scale, scale_bound)
+ *   symbol = rint(y - mean) (decode == 0: y is f32 NCHW)  or  the next symbol of the image's rANS stream (decode == 1)
+ *   y_hat_pad[b][h+2][w+2][:] = symbol + mean;  y_hat_nhwc[b][h][w][:] = bf16 of it.
+ * Weights are k-major bf16: wc [12M][2M] (k = tap * M + channel, taps in raster order), w1 [2M][C1p], w2 [C1p][C2p],
+ * w3 [C2p][2M]; C1p, C2p multiples of 8 with zero padding.  y_hat_pad: f32 [B][H+2][W+4][M], zero outside the latent.
+ * symbols / indexes: i32 [B][H*W*M], pixel-major, channel-minor (written by the encoder; the decoder writes symbols if non-NULL).
+ * Decoder: stream b at buf[b*stride + io_offset[b] ..+ io_nbytes[b]) (io_offset % 4 == 0); its rANS state and read position
+ * live in st_x / st_pos between calls (initialised when pix0 == 0), so a scan may be split into pixel ranges.  status[b]:
+ * bit 3 = a corrupt or truncated stream (no word outside the stream is read), bit 4 = the stream did not end where the last
+ * pixel ended (state != 2^31 or words left over).  All M <= 512, 2M and C1p / C2p <= 1280. */
+typedef struct sc2_ar_scan_args {
+    int32_t B, H, W, M, C1p, C2p;
+    int32_t n_table, n_cdfs, cdf_stride, pix0, pix1, decode;
+    float scale_bound;
+    int32_t cdf_entries;   /* decode: sum(cdf_sizes) - n_cdfs (the packed table's length) */
+    int64_t stride;
+    const void *wc, *bc, *w1, *p1, *w2, *b2, *w3, *b3;
+    const float *scale_table;
+    float *y_hat_pad;
+    void *y_hat_nhwc;
+    const float *y;
+    int32_t *symbols, *indexes;
+    const uint8_t *buf;
+    const int32_t *io_offset, *io_nbytes;
+    const int32_t *cdfs, *cdf_sizes, *offsets;
+    uint64_t *st_x;
+    int32_t *st_pos, *status;
+    float *gaussian_params;   /* nullable: f32 [B][H*W][2M], each pixel's scales then means as the step computed them */
+} sc2_ar_scan_args;
+int sc2_ar_scan(const sc2_ar_scan_args *args, void *stream);
+/* Resumable rANS decoder (the scan's decoder as a kernel of its own): decodes n_sym symbols per stream with explicit per-symbol
+ * indexes [n_streams][n_sym], continuing from st_x / st_pos / status unless `first` (then it starts at the stream's first word).
+ * `last`: also check that the stream ends here (status bit 4).  Same stream layout and status bits as sc2_ar_scan. */
+int sc2_rans_decode_resume(const uint8_t *buf, int64_t stride, const int32_t *io_offset, const int32_t *io_nbytes,
+                           const int32_t *indexes, int n_streams, int64_t n_sym, const int32_t *cdfs, int n_cdfs,
+                           int cdf_stride, const int32_t *cdf_sizes, const int32_t *offsets, int first, int last,
+                           uint64_t *st_x, int32_t *st_pos, int32_t *status, int32_t *symbols_out, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Diagnostics (csrc/diag.hip; no product path calls these).                                    */
 /* ------------------------------------------------------------------------------------------ */
 /* The shader clock the chip holds while OTHER kernels run: `n_workgroups` probe waves (one per workgroup; launch >= 8 so that

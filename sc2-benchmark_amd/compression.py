@@ -1,7 +1,8 @@
-"""Learned image-compression models for the neural INPUT compression baseline of the reference
-(configs/ilsvrc2012/input_compression/factorized_prior-resnet50.yaml:60-65: `bmshj2018_factorized`, quality 8,
-built through sc2bench/models/registry.py:58-105 from CompressAI's zoo and driven by
-`NeuralInputCompressionClassifier`, sc2bench/models/wrapper.py:80-135).
+"""Learned image-compression models for the neural INPUT compression baselines of the reference
+(configs/ilsvrc2012/input_compression/factorized_prior-resnet50.yaml:60-65: `bmshj2018_factorized`, quality 8;
+scale_hyperprior-*.yaml, mean_scale_hyperprior-*.yaml and joint_autoregressive_hierarchical_prior-*.yaml:
+`bmshj2018_hyperprior`, `mbt2018_mean`, `mbt2018`), built through sc2bench/models/registry.py:58-105 from CompressAI's
+zoo and driven by `NeuralInputCompressionClassifier`, sc2bench/models/wrapper.py:80-135.
 
 `FactorizedPrior` keeps CompressAI's architecture, parameter / buffer names and API (`forward`, `compress`,
 `decompress`, `update`, `aux_loss`, `load_state_dict`): g_a = 4 x Conv(k5, s2, p2, bias) with 3 GDN in between,
@@ -14,7 +15,8 @@ import torch
 from torch import nn
 
 from . import hip
-from .entropy import CompressionModel, GDN, HipConv2d, HipConvTranspose2d, _require_device
+from .entropy import (CompressionModel, EntropyBottleneck, GaussianConditional, GDN, HipConv2d, HipConvTranspose2d,
+                      _raise_on_status, _require_device, get_scale_table, update_registered_buffers)
 
 COMPRESSION_MODEL_CLASS_DICT = dict()
 COMPRESSION_MODEL_FUNC_DICT = dict()
@@ -177,6 +179,453 @@ def bmshj2018_factorized(quality, metric='mse', pretrained=False, progress=True,
             logging.getLogger(__name__).warning(msg)
     return model
 
+
+# --------------------------------------------------------------------------------------------- #
+# hyperprior models (compressai.models.google: ScaleHyperprior, MeanScaleHyperprior,
+# JointAutoregressiveHierarchicalPriors) -- the architecture is [recalled] from CompressAI 1.2.x, not read from an install
+# --------------------------------------------------------------------------------------------- #
+def _run_biased(seq, x_nhwc, a_op=hip.AOP_NONE, last_out_format=hip.OUT_F32_NCHW):
+    """An nn.Sequential of biased HipConv2d / HipConvTranspose2d with ReLU / LeakyReLU(0.01) in between (the h_a / h_s
+    transforms of the hyperprior models) on bf16 NHWC activations: bias and activation ride in the conv's epilogue.  `a_op`
+    applies to the first conv's input (|y| of the scale hyperprior)."""
+    mods = list(seq)
+    h = x_nhwc
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        nxt = mods[i + 1] if i + 1 < len(mods) else None
+        epi = hip.EPI_BIAS
+        if isinstance(nxt, nn.ReLU):
+            epi = hip.EPI_BIAS_RELU
+        elif isinstance(nxt, nn.LeakyReLU):
+            if abs(nxt.negative_slope - 0.01) > 1e-12:
+                raise hip.Sc2Error('LeakyReLU({}): only a slope of 0.01 is fused'.format(nxt.negative_slope))
+            epi = hip.EPI_BIAS_LEAKY_RELU
+        last = i + (2 if epi != hip.EPI_BIAS else 1) >= len(mods)
+        fmt = last_out_format if last else hip.OUT_BF16_NHWC
+        if isinstance(m, HipConvTranspose2d):
+            if i == 0 and a_op != hip.AOP_NONE:
+                raise hip.Sc2Error('_run_biased: an input operand on a transposed convolution')
+            kfmt = hip.OUT_F32_NHWC if fmt == hip.OUT_F32_NCHW else fmt
+            h = m.forward_nhwc(h, hip.EPI_NONE if epi == hip.EPI_BIAS else epi, None, out_format=kfmt)
+            if fmt == hip.OUT_F32_NCHW:
+                h = h.permute(0, 3, 1, 2).contiguous()
+        elif isinstance(m, HipConv2d):
+            assert m.bias is not None and h.shape[-1] == m.in_channels
+            h = hip.conv2d_fwd(h, m.packed_weight(), m.out_channels, m.kernel_size[0], m.kernel_size[1], m.stride,
+                               m.padding, a_op=a_op if i == 0 else hip.AOP_NONE, epilogue=epi, ep_beta=m.bias_f32(),
+                               out_format=fmt, tag=getattr(m, '_tag', None), k_order=m.k_order())
+        else:
+            raise hip.Sc2Error('_run_biased: unsupported module {}'.format(type(m).__name__))
+        i += 1 if epi == hip.EPI_BIAS else 2
+    return h
+
+
+def _tag(prefix, seq):
+    for i, mod in enumerate(seq):
+        mod._tag = '{}.{}'.format(prefix, i)
+
+
+class _HyperpriorBase(CompressionModel):
+    """g_a / g_s as in FactorizedPrior, an EntropyBottleneck(N) on z and a GaussianConditional on y."""
+
+    def __init__(self, N, M, **kwargs):
+        super().__init__(entropy_bottleneck_channels=N)
+        self.g_a = nn.Sequential(conv(3, N), GDN(N), conv(N, N), GDN(N), conv(N, N), GDN(N), conv(N, M))
+        self.g_s = nn.Sequential(deconv(M, N), GDN(N, inverse=True), deconv(N, N), GDN(N, inverse=True),
+                                 deconv(N, N), GDN(N, inverse=True), deconv(N, 3))
+        self.gaussian_conditional = GaussianConditional(None)
+        self.N = int(N)
+        self.M = int(M)
+
+    def _tag_all(self):
+        for name in ('g_a', 'g_s', 'h_a', 'h_s'):
+            _tag(name, getattr(self, name))
+
+    @property
+    def downsampling_factor(self):
+        return 2 ** (4 + 2)
+
+    analysis = FactorizedPrior.analysis
+    synthesis_nhwc = FactorizedPrior.synthesis_nhwc
+    synthesis = FactorizedPrior.synthesis
+
+    def hyper_analysis(self, y):
+        """h_a(|y|) (scale hyperprior) or h_a(y): f32 NCHW y -> f32 NCHW z."""
+        y_nhwc = hip.nchw_f32_to_nhwc_bf16(y.float().contiguous(), y.shape[1])
+        return _run_biased(self.h_a, y_nhwc, a_op=hip.AOP_ABS if self._hyper_abs else hip.AOP_NONE)
+
+    def hyper_synthesis(self, z_hat_nhwc, out_format=hip.OUT_F32_NCHW):
+        return _run_biased(self.h_s, z_hat_nhwc, last_out_format=out_format)
+
+    def _z_hat_nhwc(self, z_strings, shape):
+        return self.entropy_bottleneck.decompress_to_device(z_strings, tuple(shape), want_f32=False, want_nhwc=True)[1]
+
+    def update(self, scale_table=None, force=False, update_quantiles=False):
+        if scale_table is None:
+            scale_table = get_scale_table()
+        updated = self.gaussian_conditional.update_scale_table(scale_table, force=force)
+        updated |= self.entropy_bottleneck.update(force=force, update_quantiles=update_quantiles)
+        return updated
+
+    def load_state_dict(self, state_dict, strict=True):
+        update_registered_buffers(self.gaussian_conditional, 'gaussian_conditional',
+                                  ['_quantized_cdf', '_offset', '_cdf_length', 'scale_table'], state_dict)
+        return super().load_state_dict(state_dict, strict=strict)
+
+    @classmethod
+    def from_state_dict(cls, state_dict):
+        N = state_dict['g_a.0.weight'].size(0)
+        M = state_dict['g_a.6.weight'].size(0)
+        net = cls(N, M)
+        net.load_state_dict(state_dict)
+        return net
+
+    # ---- the y stream of the two non-autoregressive models
+    def _gaussian(self, params):
+        return params, None
+
+    def forward(self, x):
+        y = self.analysis(x)
+        z = self.hyper_analysis(y)
+        z_hat, z_likelihoods = self.entropy_bottleneck(z)
+        scales_hat, means_hat = self._gaussian(self.hyper_synthesis(hip.nchw_f32_to_nhwc_bf16(z_hat.contiguous(), self.N)))
+        y_hat, y_likelihoods = self.gaussian_conditional(y, scales_hat, means=means_hat)
+        x_hat = self.synthesis(y_hat)
+        return {'x_hat': x_hat, 'likelihoods': {'y': y_likelihoods, 'z': z_likelihoods}}
+
+    def compress(self, x):
+        y = self.analysis(x)
+        z = self.hyper_analysis(y)
+        z_strings = self.entropy_bottleneck.compress(z)
+        scales_hat, means_hat = self._gaussian(self.hyper_synthesis(self._z_hat_nhwc(z_strings, z.shape[-2:])))
+        indexes = self.gaussian_conditional.build_indexes(scales_hat)
+        y_strings = self.gaussian_conditional.compress(y, indexes, means=means_hat)
+        return {'strings': [y_strings, z_strings], 'shape': z.size()[-2:]}
+
+    def decompress(self, strings, shape):
+        assert isinstance(strings, list) and len(strings) == 2
+        scales_hat, means_hat = self._gaussian(self.hyper_synthesis(self._z_hat_nhwc(strings[1], shape)))
+        indexes = self.gaussian_conditional.build_indexes(scales_hat)
+        y_hat_nhwc = self.gaussian_conditional.decompress_to_device(strings[0], indexes, means_hat, want_f32=False,
+                                                                    want_nhwc=True)[1]
+        return {'x_hat': self.synthesis_nhwc(y_hat_nhwc).clamp_(0, 1)}
+
+
+@register_compression_model_class
+class ScaleHyperprior(_HyperpriorBase):
+    """Scale hyperprior of Balle et al. 2018 (`compressai.models.ScaleHyperprior`) [recalled]: h_a = conv(M, N, k3, s1) ReLU
+    conv(N, N) ReLU conv(N, N) on |y|; h_s = deconv(N, N) ReLU deconv(N, N) ReLU conv(N, M, k3, s1) ReLU gives the scales.
+
+    :param N: channels of the transforms
+    :param M: channels of the latent
+    """
+    _hyper_abs = True
+
+    def __init__(self, N, M, **kwargs):
+        super().__init__(N, M, **kwargs)
+        self.h_a = nn.Sequential(conv(M, N, stride=1, kernel_size=3), nn.ReLU(inplace=True), conv(N, N), nn.ReLU(inplace=True),
+                                 conv(N, N))
+        self.h_s = nn.Sequential(deconv(N, N), nn.ReLU(inplace=True), deconv(N, N), nn.ReLU(inplace=True),
+                                 conv(N, M, stride=1, kernel_size=3), nn.ReLU(inplace=True))
+        self._tag_all()
+
+
+@register_compression_model_class
+class MeanScaleHyperprior(_HyperpriorBase):
+    """Mean-scale hyperprior of Minnen et al. 2018 (`compressai.models.MeanScaleHyperprior`) [recalled]: h_a with LeakyReLU
+    on y; h_s = deconv(N, M) LReLU deconv(M, 3M/2) LReLU conv(3M/2, 2M, k3, s1), chunked into scales and means."""
+    _hyper_abs = False
+
+    def __init__(self, N, M, **kwargs):
+        super().__init__(N, M, **kwargs)
+        self.h_a = nn.Sequential(conv(M, N, stride=1, kernel_size=3), nn.LeakyReLU(inplace=True), conv(N, N),
+                                 nn.LeakyReLU(inplace=True), conv(N, N))
+        self.h_s = nn.Sequential(deconv(N, M), nn.LeakyReLU(inplace=True), deconv(M, M * 3 // 2), nn.LeakyReLU(inplace=True),
+                                 conv(M * 3 // 2, M * 2, stride=1, kernel_size=3))
+        self._tag_all()
+
+    def _gaussian(self, params):
+        scales_hat, means_hat = params.chunk(2, 1)
+        return scales_hat, means_hat
+
+
+class MaskedConv2d(HipConv2d):
+    """compressai.layers.MaskedConv2d [recalled]: a Conv2d whose taps at and after the centre (mask type 'A'; 'B' keeps the
+    centre) in raster order are zero.  `mask` is a registered buffer.  The device kernels read the masked weights, packed
+    once per parameter version; the parameter itself is not rewritten."""
+
+    def __init__(self, *args, mask_type='A', **kwargs):
+        super().__init__(*args, **kwargs)
+        if mask_type not in ('A', 'B'):
+            raise ValueError('Invalid "mask_type" value "{}"'.format(mask_type))
+        self.register_buffer('mask', torch.ones_like(self.weight.data))
+        _, _, h, w = self.mask.size()
+        self.mask[:, :, h // 2, w // 2 + (mask_type == 'B'):] = 0
+        self.mask[:, :, h // 2 + 1:] = 0
+
+    def masked_weight(self):
+        return self.weight.detach() * self.mask
+
+    def packed_weight(self, k_order=None):
+        order = self.k_order() if k_order is None else k_order
+        key = (self.weight._version, self.mask._version, self.weight.device, self.weight.data_ptr(), order)
+        if self.__dict__.get('_masked_key') != key:
+            self._masked_packed = hip.pack_conv_weight(self.masked_weight(), order)
+            self._masked_key = key
+        return self._masked_packed
+
+
+def _pad8(c):
+    return (c + 7) // 8 * 8
+
+
+@register_compression_model_class
+class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
+    """Joint autoregressive and hierarchical priors of Minnen et al. 2018 (`compressai.models.
+    JointAutoregressiveHierarchicalPriors`, zoo name `mbt2018`) [recalled]: the mean-scale model's transforms plus a 5x5
+    type-A masked context model (M -> 2M) and `entropy_parameters` = 1x1 convs 12M/3 -> 10M/3 -> 8M/3 -> 6M/3 with LeakyReLU.
+
+    `forward` is the parallel form (context convolution over the whole dequantised map).  `compress` / `decompress` are the
+    serial raster scan of upstream's `_compress_ar` / `_decompress_ar` on the device (csrc/ar_context.hip): one workgroup per
+    image, the y stream of an image = ONE rANS stream of its symbols in pixel-major, channel-minor order with per-symbol
+    Gaussian indexes.  The hyper-params half of the first entropy_parameters layer runs for all pixels before the scan, in
+    both directions.  Channel counts that are not multiples of 8 (10M/3, 8M/3 at M = 320) are zero-padded in the packed
+    weights and activations."""
+
+    def __init__(self, N=192, M=192, **kwargs):
+        super().__init__(N, M, **kwargs)
+        self.h_a = nn.Sequential(conv(M, N, stride=1, kernel_size=3), nn.LeakyReLU(inplace=True), conv(N, N),
+                                 nn.LeakyReLU(inplace=True), conv(N, N))
+        self.h_s = nn.Sequential(deconv(N, M), nn.LeakyReLU(inplace=True), deconv(M, M * 3 // 2), nn.LeakyReLU(inplace=True),
+                                 conv(M * 3 // 2, M * 2, stride=1, kernel_size=3))
+        self.entropy_parameters = nn.Sequential(
+            HipConv2d(M * 12 // 3, M * 10 // 3, 1), nn.LeakyReLU(inplace=True),
+            HipConv2d(M * 10 // 3, M * 8 // 3, 1), nn.LeakyReLU(inplace=True),
+            HipConv2d(M * 8 // 3, M * 6 // 3, 1))
+        self.context_prediction = MaskedConv2d(M, 2 * M, kernel_size=5, padding=2, stride=1)
+        self._tag_all()
+        _tag('entropy_parameters', self.entropy_parameters)
+        self.context_prediction._tag = 'context_prediction'
+
+    @property
+    def downsampling_factor(self):
+        return 2 ** (4 + 2)
+
+    # ---- packed weights (once per parameter version)
+    def _packed(self):
+        ep = self.entropy_parameters
+        cp = self.context_prediction
+        params = [cp.weight, cp.bias, cp.mask] + [p for i in (0, 2, 4) for p in (ep[i].weight, ep[i].bias)]
+        key = tuple((p._version, p.data_ptr(), p.device) for p in params)
+        if self.__dict__.get('_packed_key') == key:
+            return self._packed_cache
+        M = self.M
+        C1, C2 = ep[0].out_channels, ep[2].out_channels
+        C1p, C2p = _pad8(C1), _pad8(C2)
+        dev = cp.weight.device
+        with torch.no_grad():
+            w1 = ep[0].weight.detach().float()[:, :, 0, 0]          # [C1, 4M]
+            w2 = ep[2].weight.detach().float()[:, :, 0, 0]          # [C2, C1]
+            w3 = ep[4].weight.detach().float()[:, :, 0, 0]          # [2M, C2]
+            b1 = torch.zeros(C1p, device=dev)
+            b1[:C1] = ep[0].bias.detach().float()
+            b2 = torch.zeros(C2p, device=dev)
+            b2[:C2] = ep[2].bias.detach().float()
+            w1p = torch.zeros(C1p, 4 * M, device=dev)
+            w1p[:C1] = w1
+            w2p = torch.zeros(C2p, C1p, device=dev)
+            w2p[:C2, :C1] = w2
+            w3p = torch.zeros(2 * M, C2p, device=dev)
+            w3p[:, :C2] = w3
+            mw = cp.masked_weight().float()                          # [2M, M, 5, 5]
+            taps = [(ky, kx) for ky in range(2) for kx in range(5)] + [(2, 0), (2, 1)]
+            wc = torch.cat([mw[:, :, ky, kx].t() for ky, kx in taps], 0)   # [12M, 2M], k = tap * M + channel
+            pk = {
+                'C1p': C1p, 'C2p': C2p,
+                # the parallel path: 1x1 convs on the packed-weight kernels (zero rows / columns for the padding)
+                'ep1': hip.pack_conv_weight(w1p.reshape(C1p, 4 * M, 1, 1)), 'eb1': b1.contiguous(),
+                'ep2': hip.pack_conv_weight(w2p.reshape(C2p, C1p, 1, 1)), 'eb2': b2.contiguous(),
+                'ep3': hip.pack_conv_weight(w3p.reshape(2 * M, C2p, 1, 1)), 'eb3': ep[4].bias.detach().float().contiguous(),
+                # the hyper-params half of layer 1, for all pixels before the scan
+                'ep1a': hip.pack_conv_weight(w1p[:, :2 * M].contiguous().reshape(C1p, 2 * M, 1, 1)),
+                # the scan: k-major bf16
+                'scan': {'wc': wc.to(torch.bfloat16).contiguous(), 'bc': cp.bias.detach().float().contiguous(),
+                         'w1': w1p[:, 2 * M:].t().to(torch.bfloat16).contiguous(),
+                         'w2': w2p.t().to(torch.bfloat16).contiguous(), 'b2': b2.contiguous(),
+                         'w3': w3p.t().to(torch.bfloat16).contiguous(), 'b3': ep[4].bias.detach().float().contiguous()},
+            }
+        self._packed_cache = pk
+        self._packed_key = key
+        return pk
+
+    def entropy_parameters_nhwc(self, params_nhwc, ctx_nhwc):
+        """entropy_parameters(cat(params, ctx)) on bf16 NHWC maps -> f32 NCHW gaussian params [B, 2M, H, W]."""
+        pk = self._packed()
+        h = torch.cat([params_nhwc, ctx_nhwc], dim=3).contiguous()
+        h = hip.conv2d_fwd(h, pk['ep1'], pk['C1p'], 1, 1, 1, 0, epilogue=hip.EPI_BIAS_LEAKY_RELU, ep_beta=pk['eb1'],
+                           tag='entropy_parameters.0')
+        h = hip.conv2d_fwd(h, pk['ep2'], pk['C2p'], 1, 1, 1, 0, epilogue=hip.EPI_BIAS_LEAKY_RELU, ep_beta=pk['eb2'],
+                           tag='entropy_parameters.2')
+        return hip.conv2d_fwd(h, pk['ep3'], 2 * self.M, 1, 1, 1, 0, epilogue=hip.EPI_BIAS, ep_beta=pk['eb3'],
+                              out_format=hip.OUT_F32_NCHW, tag='entropy_parameters.4')
+
+    def context_nhwc(self, y_hat):
+        """context_prediction(y_hat) over the whole map: f32 NCHW y_hat -> bf16 NHWC [B, H, W, 2M]."""
+        cp = self.context_prediction
+        x = hip.nchw_f32_to_nhwc_bf16(y_hat.float().contiguous(), self.M)
+        return hip.conv2d_fwd(x, cp.packed_weight(), 2 * self.M, 5, 5, 1, 2, epilogue=hip.EPI_BIAS, ep_beta=cp.bias_f32(),
+                              tag='context_prediction', k_order=cp.k_order())
+
+    def forward(self, x):
+        y = self.analysis(x)
+        z = self.hyper_analysis(y)
+        z_hat, z_likelihoods = self.entropy_bottleneck(z)
+        params = self.hyper_synthesis(hip.nchw_f32_to_nhwc_bf16(z_hat.contiguous(), self.N), out_format=hip.OUT_BF16_NHWC)
+        y_hat = self.gaussian_conditional.quantize(y, 'noise' if self.training else 'dequantize')
+        gaussian_params = self.entropy_parameters_nhwc(params, self.context_nhwc(y_hat))
+        scales_hat, means_hat = gaussian_params.chunk(2, 1)
+        _, y_likelihoods = self.gaussian_conditional(y, scales_hat, means=means_hat)
+        x_hat = self.synthesis(y_hat)
+        return {'x_hat': x_hat, 'likelihoods': {'y': y_likelihoods, 'z': z_likelihoods}}
+
+    # ---- the serial scan
+    def _scan_inputs(self, z_hat_nhwc):
+        """-> (p1 f32 [B, H, W, C1p], y_hat_pad f32 zeros [B, H+2, W+4, M]) for the y grid of 4x z's size."""
+        pk = self._packed()
+        params = self.hyper_synthesis(z_hat_nhwc, out_format=hip.OUT_BF16_NHWC)
+        p1 = hip.conv2d_fwd(params, pk['ep1a'], pk['C1p'], 1, 1, 1, 0, epilogue=hip.EPI_BIAS, ep_beta=pk['eb1'],
+                            out_format=hip.OUT_F32_NHWC, tag='entropy_parameters.0.params')
+        B, H, W, _ = p1.shape
+        y_hat_pad = torch.zeros((B, H + 2, W + 4, self.M), dtype=torch.float32, device=p1.device)
+        return p1, y_hat_pad
+
+    def _check_tables(self):
+        gc = self.gaussian_conditional
+        if gc.scale_table.numel() == 0 or gc._quantized_cdf.numel() == 0:
+            raise ValueError('Uninitialized scale table. Run update() first')
+        return gc
+
+    def compress_device(self, x, gaussian_params=None):
+        """-> dict(y, symbols, indexes [B, H*W*M] pixel-major, y_hat_pad, z_strings, shape) with the scan done on the device."""
+        gc = self._check_tables()
+        y = self.analysis(x)
+        z = self.hyper_analysis(y)
+        z_strings = self.entropy_bottleneck.compress(z)
+        p1, y_hat_pad = self._scan_inputs(self._z_hat_nhwc(z_strings, z.shape[-2:]))
+        B, H, W, _ = p1.shape
+        if tuple(y.shape[-2:]) != (H, W):
+            raise ValueError('mbt2018: the latent is {} but its hyperprior covers {}: the input size must be a multiple of '
+                             '{}'.format(tuple(y.shape[-2:]), (H, W), self.downsampling_factor))
+        sym = torch.empty((B, H * W * self.M), dtype=torch.int32, device=y.device)
+        idx = torch.empty_like(sym)
+        hip.ar_scan(self._packed()['scan'], p1, y_hat_pad, None, gc.scale_table.float().contiguous(), gc._scale_bound,
+                    y=y.float().contiguous(), symbols=sym, indexes=idx, gaussian_params=gaussian_params)
+        return {'y': y, 'symbols': sym, 'indexes': idx, 'y_hat_pad': y_hat_pad, 'z_strings': z_strings,
+                'shape': z.size()[-2:]}
+
+    def compress(self, x):
+        out = self.compress_device(x)
+        y_strings = _encode_strings(self.gaussian_conditional, out['symbols'], out['indexes'])
+        return {'strings': [y_strings, out['z_strings']], 'shape': out['shape']}
+
+    def decompress_device(self, strings, shape, gaussian_params=None, chunks=1):
+        """-> (y_hat_pad f32 [B, H+2, W+4, M], y_hat bf16 NHWC [B, H, W, M], symbols [B, H*W*M]); raises on a corrupt stream.
+        `chunks` > 1 splits the scan into that many launches over consecutive pixel ranges (the decoder state carries over)."""
+        assert isinstance(strings, list) and len(strings) == 2
+        gc = self._check_tables()
+        p1, y_hat_pad = self._scan_inputs(self._z_hat_nhwc(strings[1], shape))
+        B, H, W, _ = p1.shape
+        if len(strings[0]) != B:
+            raise ValueError('Invalid strings or shape: {} y strings for {} z strings'.format(len(strings[0]), B))
+        dev = p1.device
+        buf, off, nb = gc.pack_strings(strings[0], dev)
+        cdf, cdf_len, offset = gc._tables()
+        dec = {'buf': buf, 'off': off, 'nb': nb, 'cdfs': cdf, 'cdf_sizes': cdf_len.int().contiguous(),
+               'offsets': offset.int().contiguous(), 'cdf_entries': int(cdf_len.sum().item()) - cdf_len.numel(),
+               'st_x': torch.zeros(B, dtype=torch.int64, device=dev), 'st_pos': torch.zeros(B, dtype=torch.int32, device=dev),
+               'status': torch.zeros(B, dtype=torch.int32, device=dev)}
+        y_hat = torch.empty((B, H, W, self.M), dtype=torch.bfloat16, device=dev)
+        sym = torch.empty((B, H * W * self.M), dtype=torch.int32, device=dev)
+        n = H * W
+        bounds = [n * i // chunks for i in range(chunks + 1)]
+        for i in range(chunks):
+            hip.ar_scan(self._packed()['scan'], p1, y_hat_pad, y_hat, gc.scale_table.float().contiguous(), gc._scale_bound,
+                        symbols=sym, decode=dec, pix=(bounds[i], bounds[i + 1]), gaussian_params=gaussian_params)
+        what = 'JointAutoregressiveHierarchicalPriors.decompress'
+        _raise_on_status(dec['status'] & ~16, what)   # bit 4 (16): the scan's own end-of-stream check
+        if int((dec['status'] & 16).max().item()):
+            raise ValueError('{}: a byte stream does not end where its last symbol ends (corrupt or foreign stream)'.format(what))
+        return y_hat_pad, y_hat, sym
+
+    def decompress(self, strings, shape):
+        _, y_hat, _ = self.decompress_device(strings, shape)
+        return {'x_hat': self.synthesis_nhwc(y_hat).clamp_(0, 1)}
+
+
+def _encode_strings(gc, sym, idx):
+    """int32 symbols / indexes [B, n] on the device -> list[bytes], one rANS stream per row (the batched device coder)."""
+    buf, off, nb, st = gc.encode_symbols_device(sym, idx)
+    if int(st.max().item()) != 0:
+        buf, off, nb, st = gc.encode_symbols_device(sym, idx, out_stride=hip.rans_max_bytes(sym.shape[1]))
+        _raise_on_status(st, 'GaussianConditional.compress')
+    nb_h = nb.cpu().numpy()
+    stride = buf.shape[1]
+    width = int(nb_h.max())
+    tail = buf[:, stride - width:].contiguous().cpu().numpy()
+    return [tail[i, width - int(nb_h[i]):].tobytes() for i in range(tail.shape[0])]
+
+
+# compressai.zoo.image [recalled]: quality -> (N, M)
+HYPERPRIOR_CFGS = {q: ((128, 192) if q <= 5 else (192, 320)) for q in range(1, 9)}
+MEAN_SCALE_CFGS = {q: ((128, 192) if q <= 4 else (192, 320)) for q in range(1, 9)}
+MBT2018_CFGS = {q: ((192, 192) if q <= 4 else (192, 320)) for q in range(1, 9)}
+
+
+def _zoo_model(zoo_name, file_stem, cls, cfgs, quality, metric, pretrained, kwargs):
+    import logging
+    import os
+    import warnings
+    if metric not in ('mse', 'ms-ssim'):
+        raise ValueError('Invalid metric "{}"'.format(metric))
+    if quality < 1 or quality > 8:
+        raise ValueError('Invalid quality "{}", should be between (1, 8)'.format(quality))
+    model = cls(*cfgs[quality], **kwargs)
+    if pretrained:
+        root = os.environ.get('SC2_PRETRAINED_DIR')
+        path = os.path.join(root, '{}-{}-{}.pth'.format(file_stem, metric, quality)) if root else None
+        if path and os.path.isfile(path):
+            from .ckpt import _torch_load
+            model.load_state_dict(_torch_load(path))
+        else:
+            msg = ('{}(quality={}, pretrained=True): no local weights ({}); the model is RANDOMLY '
+                   'INITIALISED'.format(zoo_name, quality, path or 'SC2_PRETRAINED_DIR unset'))
+            if os.environ.get('SC2_STRICT_WEIGHTS') == '1':
+                raise FileNotFoundError(msg)
+            warnings.warn(msg)
+            logging.getLogger(__name__).warning(msg)
+    return model
+
+
+@register_compression_model_func
+def bmshj2018_hyperprior(quality, metric='mse', pretrained=False, progress=True, **kwargs):
+    """compressai.zoo.bmshj2018_hyperprior; offline weights from $SC2_PRETRAINED_DIR/bmshj2018-hyperprior-{metric}-{quality}.pth
+    (as bmshj2018_factorized)."""
+    return _zoo_model('bmshj2018_hyperprior', 'bmshj2018-hyperprior', ScaleHyperprior, HYPERPRIOR_CFGS, quality, metric,
+                      pretrained, kwargs)
+
+
+@register_compression_model_func
+def mbt2018_mean(quality, metric='mse', pretrained=False, progress=True, **kwargs):
+    """compressai.zoo.mbt2018_mean; offline weights from $SC2_PRETRAINED_DIR/mbt2018-mean-{metric}-{quality}.pth."""
+    return _zoo_model('mbt2018_mean', 'mbt2018-mean', MeanScaleHyperprior, MEAN_SCALE_CFGS, quality, metric, pretrained, kwargs)
+
+
+@register_compression_model_func
+def mbt2018(quality, metric='mse', pretrained=False, progress=True, **kwargs):
+    """compressai.zoo.mbt2018; offline weights from $SC2_PRETRAINED_DIR/mbt2018-{metric}-{quality}.pth."""
+    return _zoo_model('mbt2018', 'mbt2018', JointAutoregressiveHierarchicalPriors, MBT2018_CFGS, quality, metric, pretrained,
+                      kwargs)
 
 def get_compression_model(compression_model_config, device):
     """sc2bench/models/registry.py:83-105: {'key', 'kwargs', 'src_ckpt'?, 'update'?} -> model on `device`, CDF tables

@@ -199,9 +199,12 @@ class HipConvTranspose2d(nn.ConvTranspose2d):
         OW = (W - 1) * sw - 2 * self.padding[1] + self.kernel_size[1] + self.output_padding[1]
         cout, cpad = self.out_channels, self._cout_pad()
         if self.bias is not None:      # the bias rides in each parity class's epilogue
-            if epilogue != hip.EPI_NONE:
+            if epilogue in (hip.EPI_BIAS_RELU, hip.EPI_BIAS_LEAKY_RELU) and ep_beta is None:
+                ep_beta = self.bias.detach().float().contiguous()     # bias + activation in one epilogue
+            elif epilogue != hip.EPI_NONE:
                 raise hip.Sc2Error('HipConvTranspose2d: a bias and a fused activation epilogue together are not supported')
-            epilogue, ep_beta = hip.EPI_BIAS, self.bias.detach().float().contiguous()
+            else:
+                epilogue, ep_beta = hip.EPI_BIAS, self.bias.detach().float().contiguous()
         if ep_beta is not None and cpad != cout:
             ep_beta = torch.cat([ep_beta, ep_beta.new_zeros(cpad - cout)])
         out = torch.empty((N, OH, OW, cpad), dtype=torch.bfloat16 if out_format == hip.OUT_BF16_NHWC else torch.float32,

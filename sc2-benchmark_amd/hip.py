@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     'sc2_pmf_to_quantized_cdf',
     'sc2_rans_max_bytes', 'sc2_rans_workspace_bytes', 'sc2_rans_encode_batch', 'sc2_rans_decode_batch', 'sc2_rans_decode_dequantize_batch', 'sc2_rans_decode_dequantize_batch_ev',
     'sc2_mse_partial_len', 'sc2_mse_sum_bf16', 'sc2_mse_grad_bf16', 'sc2_relu_bwd_bf16', 'sc2_relu_bwd_mse_bf16',
+    'sc2_ar_scan', 'sc2_rans_decode_resume',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
 ]
 
@@ -43,6 +44,17 @@ class ConvDesc(ctypes.Structure):
         'N', 'H', 'W', 'Cin', 'Cout', 'KH', 'KW', 'stride_h', 'stride_w', 'pad_h', 'pad_w', 'OH', 'OW',
         'a_op', 'epilogue', 'out_format', 'Kpad', 'Cout_pad', 'out_H', 'out_W', 'out_stride_h', 'out_stride_w',
         'out_off_h', 'out_off_w', 'k_order', 'dil_h', 'dil_w')]
+
+
+class ArScanArgs(ctypes.Structure):
+    """sc2_ar_scan_args of include/sc2_bottleneck.h."""
+    _fields_ = ([(n, ctypes.c_int32) for n in ('B', 'H', 'W', 'M', 'C1p', 'C2p', 'n_table', 'n_cdfs', 'cdf_stride', 'pix0',
+                                               'pix1', 'decode')] +
+                [('scale_bound', ctypes.c_float), ('cdf_entries', ctypes.c_int32), ('stride', ctypes.c_int64)] +
+                [(n, ctypes.c_void_p) for n in ('wc', 'bc', 'w1', 'p1', 'w2', 'b2', 'w3', 'b3', 'scale_table', 'y_hat_pad',
+                                                'y_hat_nhwc', 'y', 'symbols', 'indexes', 'buf', 'io_offset', 'io_nbytes',
+                                                'cdfs', 'cdf_sizes', 'offsets', 'st_x', 'st_pos', 'status',
+                                                'gaussian_params')])
 
 
 class Sc2Error(RuntimeError):
@@ -255,6 +267,8 @@ def lib():
     L.sc2_mse_grad_bf16.argtypes = [vp, vp, ctypes.c_longlong, vp, vp, vp]
     L.sc2_relu_bwd_bf16.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp]
     L.sc2_relu_bwd_mse_bf16.argtypes = [vp, vp, vp, vp, ctypes.c_longlong, i32, vp, vp]
+    L.sc2_ar_scan.argtypes = [ctypes.POINTER(ArScanArgs), vp]
+    L.sc2_rans_decode_resume.argtypes = [vp, i64, vp, vp, vp, i32, i64, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.sc2_rans_host_tables_create.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp)]
     L.sc2_rans_host_tables_destroy.argtypes = [vp]
     L.sc2_rans_host_tables_destroy.restype = None
@@ -1847,3 +1861,97 @@ def rans_decode_batch(buf, off, nb, n_sym, cdfs, cdf_sizes, offsets, indexes=Non
                                        _ptr(cdf_sizes), _ptr(offsets), _ptr(sym), _ptr(st), _ptr(ws), ws_bytes,
                                            _stream()), 'rans_decode_batch')
     return sym, st
+
+
+# --------------------------------------------------------------------------------------------- #
+# serial context-model scan (ar_context.hip): the joint autoregressive hierarchical prior's compress / decompress
+# --------------------------------------------------------------------------------------------- #
+def ar_scan(weights, p1, y_hat_pad, y_hat_nhwc, scale_table, scale_bound, y=None, symbols=None, indexes=None, decode=None,
+            pix=None, gaussian_params=None):
+    """One scan over pixels pix = (pix0, pix1) of the B x H x W latent (all of it by default).
+
+    weights: dict wc / bc / w1 / w2 / b2 / w3 / b3 (bf16 k-major, f32 biases; see sc2_ar_scan_args); p1: f32 [B,H,W,C1p];
+    y_hat_pad: f32 [B,H+2,W+4,M] (updated in place); y_hat_nhwc: bf16 [B,H,W,M] or None.
+    Encoder: y f32 [B,M,H,W], symbols / indexes i32 [B,H*W*M] (written).  Decoder: decode = dict buf / off / nb / cdfs /
+    cdf_sizes / offsets / cdf_entries / st_x / st_pos / status (device tensors; state updated in place), symbols optional.
+    gaussian_params: None or f32 [B,H*W,2M] receiving each pixel's scales and means."""
+    B, H, W, C1p = p1.shape
+    M = y_hat_pad.shape[3]
+    assert tuple(y_hat_pad.shape) == (B, H + 2, W + 4, M) and y_hat_pad.dtype == torch.float32 and y_hat_pad.is_contiguous()
+    assert p1.dtype == torch.float32 and p1.is_contiguous()
+    C2p = weights['w2'].shape[1]
+    for name in ('wc', 'bc', 'w1', 'w2', 'b2', 'w3', 'b3'):
+        t = _dev(weights[name], name)
+        assert t.is_contiguous() and t.dtype == (torch.bfloat16 if name[0] == 'w' else torch.float32), name
+    assert tuple(weights['wc'].shape) == (12 * M, 2 * M) and tuple(weights['w1'].shape) == (2 * M, C1p)
+    assert tuple(weights['w2'].shape) == (C1p, C2p) and tuple(weights['w3'].shape) == (C2p, 2 * M)
+    for t in (p1, y_hat_pad, scale_table):
+        _dev(t, 'tensor')
+    assert scale_table.dtype == torch.float32 and scale_table.is_contiguous()
+    if y_hat_nhwc is not None:
+        assert tuple(y_hat_nhwc.shape) == (B, H, W, M) and y_hat_nhwc.dtype == torch.bfloat16 and y_hat_nhwc.is_contiguous()
+    for t in (symbols, indexes):
+        if t is not None:
+            _dev(t, 'symbols / indexes')
+            assert tuple(t.shape) == (B, H * W * M) and t.dtype == torch.int32 and t.is_contiguous()
+    pix0, pix1 = (0, H * W) if pix is None else pix
+    a = ArScanArgs()
+    a.B, a.H, a.W, a.M, a.C1p, a.C2p = B, H, W, M, C1p, C2p
+    a.n_table, a.pix0, a.pix1 = scale_table.numel(), pix0, pix1
+    a.scale_bound = float(scale_bound)
+    for name in ('wc', 'bc', 'w1', 'w2', 'b2', 'w3', 'b3'):
+        setattr(a, name, weights[name].data_ptr())
+    a.p1, a.scale_table, a.y_hat_pad = p1.data_ptr(), scale_table.data_ptr(), y_hat_pad.data_ptr()
+    a.y_hat_nhwc = y_hat_nhwc.data_ptr() if y_hat_nhwc is not None else None
+    a.symbols = symbols.data_ptr() if symbols is not None else None
+    a.indexes = indexes.data_ptr() if indexes is not None else None
+    if gaussian_params is not None:
+        _dev(gaussian_params, 'gaussian_params')
+        assert tuple(gaussian_params.shape) == (B, H * W, 2 * M) and gaussian_params.dtype == torch.float32
+        assert gaussian_params.is_contiguous()
+        a.gaussian_params = gaussian_params.data_ptr()
+    if decode is None:
+        _dev(y, 'y')
+        assert tuple(y.shape) == (B, M, H, W) and y.dtype == torch.float32 and y.is_contiguous()
+        a.y = y.data_ptr()
+    else:
+        d = decode
+        assert d['buf'].dtype == torch.uint8 and d['buf'].dim() == 2 and d['buf'].shape[0] == B
+        assert d['cdfs'].dtype == torch.int32 and d['cdfs'].dim() == 2 and d['cdfs'].shape[0] == scale_table.numel()
+        assert d['st_x'].dtype == torch.int64 and d['st_x'].numel() == B
+        for name in ('buf', 'off', 'nb', 'cdfs', 'cdf_sizes', 'offsets', 'st_x', 'st_pos', 'status'):
+            _dev(d[name], name)
+            assert d[name].is_contiguous(), name
+        a.decode = 1
+        a.stride = d['buf'].shape[1]
+        a.n_cdfs, a.cdf_stride, a.cdf_entries = d['cdfs'].shape[0], d['cdfs'].shape[1], int(d['cdf_entries'])
+        for name, key in (('buf', 'buf'), ('io_offset', 'off'), ('io_nbytes', 'nb'), ('cdfs', 'cdfs'),
+                          ('cdf_sizes', 'cdf_sizes'), ('offsets', 'offsets'), ('st_x', 'st_x'), ('st_pos', 'st_pos'),
+                          ('status', 'status')):
+            setattr(a, name, d[key].data_ptr())
+    with _timed('ar_scan.{}'.format('dec' if decode is not None else 'enc')):
+        _check(lib().sc2_ar_scan(ctypes.byref(a), _stream()), 'ar_scan')
+
+
+def rans_decode_resume(buf, off, nb, indexes, cdfs, cdf_sizes, offsets, state=None, last=True):
+    """Decodes indexes.shape[1] more symbols of every stream (explicit per-symbol indexes), continuing from `state`
+    (st_x i64 [N], st_pos i32 [N], status i32 [N]; None: start at each stream's first word).  -> (symbols, state); the
+    state's status carries the stream's error bits (8: corrupt / truncated, 16: `last` and the stream did not end there)."""
+    for name, t in (('buf', buf), ('off', off), ('nb', nb), ('indexes', indexes), ('cdfs', cdfs), ('cdf_sizes', cdf_sizes),
+                    ('offsets', offsets)):
+        _dev(t, name)
+        assert t.is_contiguous(), name
+    assert buf.dtype == torch.uint8 and buf.dim() == 2 and indexes.dtype == torch.int32 and indexes.dim() == 2
+    n, stride = buf.shape
+    dev = buf.device
+    first = state is None
+    if first:
+        state = (torch.zeros(n, dtype=torch.int64, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
+                 torch.zeros(n, dtype=torch.int32, device=dev))
+    sym = torch.empty_like(indexes)
+    with _timed('rans_decode_resume'):
+        _check(lib().sc2_rans_decode_resume(_ptr(buf), stride, _ptr(off), _ptr(nb), _ptr(indexes), n, indexes.shape[1],
+                                            _ptr(cdfs), cdfs.shape[0], cdfs.shape[1], _ptr(cdf_sizes), _ptr(offsets),
+                                            int(first), int(bool(last)), _ptr(state[0]), _ptr(state[1]), _ptr(state[2]),
+                                            _ptr(sym), _stream()), 'rans_decode_resume')
+    return sym, state
