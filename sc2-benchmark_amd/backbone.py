@@ -115,10 +115,11 @@ class FeatureExtractionBackbone(UpdatableBackbone):
                                                                          c.padding == c.dilation and c.dilation[0] == c.dilation[1]))
                for b in module for c in (b.conv1, b.conv2, b.conv3)):
             return None
-        key = tuple(t._version for t in list(module.parameters()) + list(module.buffers()))
+        key = tuple((t._version, t.data_ptr()) for t in list(module.parameters()) + list(module.buffers()))
         cached = self._hip_layers.get(name)
         if cached is None or cached[0] != key:
-            cached = (key, HipHead([(name, module)], None))
+            with torch.inference_mode(False), torch.no_grad():     # (see _hip_head_for_eval)
+                cached = (key, HipHead([(name, module)], None))
             self._hip_layers[name] = cached
         return cached[1]
 
@@ -266,14 +267,18 @@ class SplittableResNet(UpdatableBackbone):
         return self
 
     def _hip_head_for_eval(self):
-        """Folded conv+BN(+ReLU)(+residual) head for bf16 eval; rebuilt when a parameter changes."""
+        """Folded conv+BN(+ReLU)(+residual) head for bf16 eval; rebuilt when a parameter changes (in place: its version; replaced,
+        `p.data = t` or a new Parameter: its address)."""
         mods = [m for m in (self.layer2, self.layer3, self.layer4, self.fc) if m is not None]
-        key = tuple(p._version for m in mods for p in m.parameters()) + \
-            tuple(b._version for m in mods for b in m.buffers()) + (str(next(mods[0].parameters()).device),)
+        key = tuple((p._version, p.data_ptr()) for m in mods for p in m.parameters()) + \
+            tuple((b._version, b.data_ptr()) for m in mods for b in m.buffers()) + (str(next(mods[0].parameters()).device),)
         if self._hip_head is None or self._hip_head_key != key:
             from .head import HipHead
             layers = [(i + 2, m) for i, m in enumerate((self.layer2, self.layer3, self.layer4)) if m is not None]
-            self._hip_head = HipHead(layers, self.fc if self.avgpool is not None else None)
+            # folded weights outside inference mode whatever the caller's (evaluate() runs under torch.inference_mode): the
+            # decoder's fused tail keys its packed weights on their versions, which inference tensors do not have
+            with torch.inference_mode(False), torch.no_grad():
+                self._hip_head = HipHead(layers, self.fc if self.avgpool is not None else None)
             self._hip_head_key = key
         return self._hip_head
 

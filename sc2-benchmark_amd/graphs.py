@@ -14,18 +14,38 @@ two device halves once per input shape --
 bit-identical to the eager forward, tests/test_gpu_graphs.py), no re-exec, no second process.  The byte strings, the
 {'strings', 'shape'} object the analyzers see and the status checks are the eager path's.
 
-A captured graph bakes in device addresses: of the packed weights (re-packed when a parameter's version changes), of the CDF
-tables and of its static input / output buffers.  The versions of every parameter and buffer are compared per call (`signature`)
-and the model drops its graphs when its storage is re-homed or its mode changes (`invalidate`); the next call captures again.  Persistent kernels take their
-work counters from a region of their own when captured (csrc/sc2_common.h: sc2_counter_ring::launch_slot), so a replay never
-shares a counter with an eager launch on another stream.
+A captured graph bakes in device addresses: of the packed weights (re-packed when a parameter's storage or version changes), of
+the CDF tables, of the median vector and of its static input / output buffers -- every one of them owned by the graph or the model
+for as long as the graph lives.  The version and address of every parameter and buffer are compared per call (`signature`); a
+parameter, buffer or submodule registered anywhere (`m.weight = nn.Parameter(..)`, `load_state_dict(assign=True)`) makes the next
+call walk the module tree again; and the model drops its graphs when its storage is re-homed or its mode changes (`invalidate`);
+the next call captures again.  A graph is captured outside inference mode whatever the caller's, so that evaluate()'s
+torch.inference_mode and a plain no_grad caller can take turns on it.  Persistent kernels take their work counters from a region
+of their own when captured (csrc/sc2_common.h: sc2_counter_ring::launch_slot), so a replay never shares a counter with an eager
+launch on another stream.
 """
 import numpy as np
 import torch
+from torch import nn
 
 from . import hip
 
 __all__ = ['EvalGraphs', 'graphs_for']
+
+
+# bumped whenever any module of the process registers a parameter, buffer or submodule (assignment, register_*, load_state_dict
+# with assign=True): the tensor list kept with a model's graphs may then be stale
+_registrations = [0]
+
+
+def _registered(module, name, value):
+    _registrations[0] += 1
+
+
+for _hook in (nn.modules.module.register_module_parameter_registration_hook,
+              nn.modules.module.register_module_buffer_registration_hook,
+              nn.modules.module.register_module_module_registration_hook):
+    _hook(_registered)
 
 
 def _tensors(model):
@@ -33,10 +53,11 @@ def _tensors(model):
 
 
 def signature(tensors):
-    """what a captured graph depends on besides its input: the version of every tensor of the model (25 us for the 304 tensors of
-    the ResNet-50 student; walking the module tree for them costs 0.4 ms, so the list is kept with the graphs).  Re-homed storage
-    (`.to()`, `load_state_dict`, `update()`, a change of mode or precision) drops the graphs through `invalidate`."""
-    return hash(tuple(t._version for t in tensors))
+    """what a captured graph depends on besides its input: the version and the address of every tensor of the model (`p.data = t`
+    keeps the version; walking the module tree for the tensors costs 0.4 ms, so the list is kept with the graphs and taken again
+    only after a registration).  Re-homed storage (`.to()`, `load_state_dict`, `update()`, a change of mode or precision) drops
+    the graphs through `invalidate`."""
+    return hash(tuple((t._version, t.data_ptr()) for t in tensors))
 
 
 def invalidate(model):
@@ -48,12 +69,19 @@ class EvalGraphs(object):
     analysis / entropy_bottleneck, decode_head)."""
 
     def __init__(self, model, x):
+        # (outside inference mode whatever the caller's: a graph captured under evaluate()'s torch.inference_mode is replayed by a
+        #  later call under plain no_grad, which writes x_static / sym_in in place)
+        with torch.inference_mode(False), torch.no_grad():
+            self._capture(model, x)
+
+    def _capture(self, model, x):
         bl = model.bottleneck_layer
         eb = bl.entropy_bottleneck
         dev = x.device
         self.shape_key = (tuple(x.shape), x.dtype)
         self.x_static = x.detach().clone()
-        medians = eb._median_vector()
+        # graph B reads the medians from this address on every replay: the graph owns the vector
+        self.medians = medians = eb._median_vector()
         # warm-up on a side stream (weights packed, LDS attributes set, work counters allocated, caching-allocator pools
         # filled): a first launch of a persistent kernel cannot be captured (hipMalloc), and torch asks for it anyway
         side = torch.cuda.Stream(device=dev)
@@ -99,21 +127,23 @@ def graphs_for(model, x, max_shapes=4):
     """The EvalGraphs of (model, x's shape), captured on first use; None when graphs do not apply or capture fails (the caller
     runs the eager forward; the reason is kept in `model._eval_graphs_error`)."""
     cache = model.__dict__.setdefault('_eval_graphs', {})
-    if 'tensors' not in cache:
-        cache['tensors'] = _tensors(model)
+    if cache.get('registrations') != _registrations[0]:
+        cache['tensors'], cache['registrations'] = _tensors(model), _registrations[0]
     sig = signature(cache['tensors'])
     if cache.get('sig') != sig:
-        tensors = cache['tensors']
+        tensors, registrations = cache['tensors'], cache['registrations']
         cache.clear()
-        cache['tensors'], cache['sig'] = tensors, sig
+        cache['tensors'], cache['registrations'], cache['sig'] = tensors, registrations, sig
     key = (tuple(x.shape), x.dtype, x.device)
     g = cache.get(key)
     if g is None and key not in cache:
-        if len(cache) > max_shapes + 2:      # a loader of ever-changing shapes: stop capturing, run eagerly
+        if len(cache) > max_shapes + 3:      # a loader of ever-changing shapes: stop capturing, run eagerly
             return None
         try:
             g = EvalGraphs(model, x)
             # (capturing allocates packed weights on first use: take the signature again so that the next call matches)
+            if cache['registrations'] != _registrations[0]:
+                cache['tensors'], cache['registrations'] = _tensors(model), _registrations[0]
             cache['sig'] = signature(cache['tensors'])
         except Exception as e:      # noqa: BLE001 -- a capture that fails must leave the eager path usable
             model.__dict__['_eval_graphs_error'] = repr(e)

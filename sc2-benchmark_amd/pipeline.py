@@ -107,6 +107,8 @@ class StagePipeline(object):
                  host_steps=None):
         self.model = model
         self.device = torch.device(device)
+        if self.device.index is None:       # 'cuda': the current device, fixed now (the host-coder worker thread selects it by index)
+            self.device = torch.device(self.device.type, torch.cuda.current_device())
         self.G = max(1, int(coder_group))
         self.max_inflight = max(1, int(max_inflight))
         self.ramp = bool(ramp)

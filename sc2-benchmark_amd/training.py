@@ -236,7 +236,7 @@ class DistillationStage(object):
         from .frozen import FrozenStack
         if not self.use_hip_frozen or not FrozenStack.supported(module):
             return None
-        key = tuple(t._version for t in list(module.parameters()) + list(module.buffers()))
+        key = tuple((t._version, t.data_ptr()) for t in list(module.parameters()) + list(module.buffers()))
         cached = self._frozen_stacks.get(id(module))
         if cached is None or cached[0] != key:
             cached = (key, FrozenStack(name, module))
@@ -277,7 +277,7 @@ class DistillationStage(object):
             return None
         if any(q.split('.')[0] in (n0, n1, n2) for q in hooks.all_paths):
             return None
-        key = tuple(t._version for t in list(conv.parameters()) + list(bn.parameters()) + list(bn.buffers()))
+        key = tuple((t._version, t.data_ptr()) for t in list(conv.parameters()) + list(bn.parameters()) + list(bn.buffers()))
         cached = self._frozen_stacks.get(id(conv))
         if cached is None or cached[0] != key:
             w = conv.weight.detach().float()

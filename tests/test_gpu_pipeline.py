@@ -230,3 +230,28 @@ def test_pipelines_of_a_process_share_one_pool_of_streams(S, dev, bench_mod):
         pipe.synchronize()
         for i in range(len(batches)):
             _equal(got[i], ref[i], 'batch {}'.format(i))
+
+
+def test_index_less_device_with_host_coder_steps(S, dev, bench_mod):
+    """torch.device('cuda') -- what `python -m sc2bench_amd.evaluation --device cuda` passes: the pipeline resolves the current device
+    (its host-coder worker thread selects the device by index), outputs equal the forward's, and evaluate() counts the hits of the
+    cuda:0 run at bs 8 (pipelined, host-coder steps) and at bs 1 (per-batch forward on the graphs)."""
+    from sc2bench_amd import evaluation
+    model = bench_mod.build_model(dev)
+    any_cuda = torch.device('cuda')
+    batches = [bench_mod.synthetic_batch(8, dev, seed=60 + s) for s in range(4)]
+    ref, got, _ = _run_both(S, model, batches, any_cuda, coder_group=2, coder_streams=2, host_steps=2)
+    for i, (a, b) in enumerate(zip(got, ref)):
+        _equal(a, b, 'batch {} (device cuda)'.format(i))
+    x = bench_mod.synthetic_batch(16, torch.device('cpu'), seed=3)
+    with torch.no_grad():
+        labels = model(x.to(dev)).float().argmax(1).cpu()
+    labels[::3] = (labels[::3] + 1) % 1000
+    ds = torch.utils.data.TensorDataset(x, labels)
+    for bs, kw in ((8, {'coder_group': 2, 'coder_streams': 2, 'host_steps': 2}), (1, None)):
+        loader = torch.utils.data.DataLoader(ds, batch_size=bs)
+        a = evaluation.evaluate(model, loader, dev, max_samples=8, pipeline_kwargs=kw)
+        b = evaluation.evaluate(model, loader, any_cuda, max_samples=8, pipeline_kwargs=kw)
+        assert a['pipeline'] == b['pipeline'] and a['pipeline'].startswith('stage pipeline' if bs > 1 else 'none')
+        assert a['samples'] == b['samples'] == 8 and a['acc1'] == b['acc1'] and a['acc5'] == b['acc5']
+        assert abs(a['acc1'] - 100.0 * 5 / 8) < 1e-9, (bs, a['acc1'])
