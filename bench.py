@@ -21,9 +21,13 @@ pipeline; the wall time is the max over ranks.  One process per GPU; the path sh
 shards, no data-path collective ("weak" scaling, bs per GPU fixed).  `--workload mshp224 | seg513 | det800x1216 |
 fp_input` run the other configs' models through the same pipeline class.
 
-Prints ONE JSON line (rank 0) with the contract keys plus `roofline` (dominant MFMA kernel, HIP events on
-its own stream, inside the timed region) and `cpu_baseline` (the oracle = CPU port of the same path, timed on
-the host cores of this box on a bounded sample; N = 1 only).
+Prints ONE JSON line (rank 0) with the contract keys plus what the timed region's own HIP events give: `roofline` (dominant
+MFMA kernel, HIP events on its own stream, inside the timed region), `bottleneck_forward`, `kernels_ms`, `rans`.  A plain run
+does nothing else: set-up, warm-up, the K timed steps, `--dump-outputs`, the line.  `--full` also runs what takes runs of its
+own or checks the result after the timed region: the roofline's stand-alone and steady-state runs, the bitstream digest
+(every rank's, on more than one rank), the precision check, the f32-encoder run, `cpu_baseline` (the oracle = CPU port of the
+same path, timed on the host's cores on a bounded sample; N = 1 only), the `secondary` rows and the bs-1 row; with
+`--workload`, that line's CPU baseline.
 """
 import argparse
 import json
@@ -324,9 +328,13 @@ def main():
     ap.add_argument('--host-steps', type=int, default=-1, help='leading steps whose streams the HOST coder codes (sc2bench_amd/pipeline.py); -1 = auto from the core count, 0 = none')
     ap.add_argument('--host-ramp-skip', type=int, default=1, help='A/B: 1 = behind host-coded steps the device coder ramp starts at 2^host_steps steps per launch; 0 = at 1')
     ap.add_argument('--numa-bind', choices=['auto', 'on', 'off'], default='auto', help="bind this process to the CPUs of its GPU's NUMA node before the first HIP call (auto: when there is more than one rank)")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-bs1', action='store_true', help='skip the bs-1 evaluation-mode row')
-    ap.add_argument('--no-secondary', action='store_true', help='skip the `secondary` rows (the other workloads + the training step, a few steps each, after the timed region)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed region, also the runs and checks the headline figure does not need: stand-alone and '
+                         'steady-state roofline runs, bitstream digests, precision check, f32-encoder run, CPU baseline, '
+                         '`secondary` rows, bs-1 row (the --no-* options below leave parts out)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the precision check, the f32-encoder run and the CPU baseline')
+    ap.add_argument('--no-bs1', action='store_true', help='with --full: skip the bs-1 evaluation-mode row')
+    ap.add_argument('--no-secondary', action='store_true', help='with --full: skip the `secondary` rows (the other workloads + the training step, a few steps each, after the timed region)')
     ap.add_argument('--split-mfma', type=int, default=1, help='decoder+head stages round-robin on K HIP streams of their own')
     ap.add_argument('--front-priority', type=int, default=0, help='HIP stream priority of the encoder stream (-1 = high)')
     ap.add_argument('--back-priority', type=int, default=0, help='HIP stream priority of the decoder+head stream(s) (-1 = high)')
@@ -402,7 +410,7 @@ def main():
     if args.mode == 'train':
         return train_bench(args, dev, rank, world, distributed)
     if args.workload != 'es224':
-        workload_bench(args, dev, rank, world, distributed, cpu_baseline_fn=workload_cpu_baseline)
+        workload_bench(args, dev, rank, world, distributed, cpu_baseline_fn=workload_cpu_baseline if args.full else None)
         if distributed:
             dist.barrier()
             dist.destroy_process_group()
@@ -483,7 +491,7 @@ def main():
     value = images / elapsed
 
     per_rank = None
-    if distributed:
+    if distributed and args.full:
         # every rank's own bpp and the digest of the byte streams of the first 8 images of ITS shard travel to rank 0 as device
         # tensors on the backend (RCCL cannot gather host objects): a multi-GPU line can be judged for bitstream / bpp parity
         # rank by rank, not only through rank 0's shard
@@ -546,47 +554,6 @@ def main():
             except Exception:
                 traffic = None
         lat_ms = [e0.elapsed_time(e1) for _, e0, e1 in latency if e1 is not None]
-        # the same launches stand-alone: one stream, nothing beside them (the in-pipeline durations above are taken while the
-        # other MFMA stream and the coder share the chip with the launch: the sum of overlapped kernel durations counts shared
-        # time twice)
-        with torch.no_grad():
-            sym_s, hw_s = model.stage_front(x)
-            dec_s, _, _ = model.stage_coder(sym_s, hw_s, **pipe.coder_kwargs)
-            torch.cuda.synchronize(dev)
-            with hip.KernelTimer(select) as solo:
-                for _ in range(5):
-                    model.stage_front(x)
-                    model.stage_back(dec_s, hw_s)
-                torch.cuda.synchronize(dev)
-            solo_sum = {k: v for k, v in solo.summary().items() if launch_work(k) is not None}
-            solo_ms = sum(v[1] for v in solo_sum.values())
-            # ... and on SURVEY 8(d)'s own basis: the ten layers of the bottleneck and nothing else (8.3418 GFLOP per image), i.e.
-            # with the decoder's last conv as a launch of its own instead of the form that carries layer2.0's two 1x1 layers
-            with hip.KernelTimer(select) as solo_p:
-                for _ in range(5):
-                    model.stage_front(x)
-                    model.stage_decoder(dec_s, hw_s)
-                torch.cuda.synchronize(dev)
-            plain_sum = {k: v for k, v in solo_p.summary().items() if launch_work(k) is not None}
-            plain_ms = sum(v[1] for v in plain_sum.values())
-            del sym_s, dec_s
-        # steady state of the dominant kernel: a tail run of >= 60 steps after the timed region, the first 8
-        # launches dropped -- with the pipeline full the encoder stage of later steps and the coder share the CUs with it, which a
-        # 20-step region barely reaches
-        steady_steps = max(60, args.steps)
-        with hip.KernelTimer(lambda tag: tag == dom) as steady_t:
-            pipe.run(x, n_steps=steady_steps)
-            sync_all()
-        steady = [r[1].elapsed_time(r[2]) for r in steady_t.records if r[0] == dom][8:]
-        steady_ms = sum(steady) / max(1, len(steady))
-        # the device bitstreams of the first 8 images of this shard, and the symbols they were coded from
-        with torch.no_grad():
-            sym, hw = model.stage_front(x)
-            eb = model.bottleneck_layer.entropy_bottleneck
-            buf, off, nbs, sts = eb.encode_symbols_device(sym, hw[0] * hw[1])
-            assert int(sts.max().item()) == 0
-            dev_streams = eb.unpack_strings(buf[:8], off[:8], nbs[:8])
-            sym8 = sym[:8].cpu()
         out = {
             'metric': 'images/s + bpp, Entropic-Student ResNet-50 224^2',
             'value': value, 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -606,7 +573,7 @@ def main():
                                   'peaked prior, latent std ~1, ~1e-4 escape symbols)',
                        'images': 'torch.rand, per-image contrast 0.25-1, ImageNet normalisation',
                        'streams': 'device-resident in the timed region (u8 rows in HBM with offset / nbytes vectors, no Python '
-                                  'bytes objects); the host-bytes encode()/decode() API of the reference is timed in bs1_eval',
+                                  'bytes objects); the host-bytes encode()/decode() API of the reference is timed in bs1_eval (--full)',
                        'encoder_precision': args.encoder_precision + (' (f32 operands on v_mfma_f32_16x16x4_f32: bitstreams of the f32 '
                                                                       'reference path; decoder + head bf16)' if args.encoder_precision == 'f32' else
                                                                       ' MFMA operands, f32 accumulation'),
@@ -617,15 +584,10 @@ def main():
                        'numa_binding': numa if (world > 1 or args.numa_bind == 'on') else 'none (one rank)'},
             'bpp': bpp, 'bytes_per_image': bytes_per_img,
             'bytes_per_image_min_mean_max': [nb_f.min().item(), bytes_per_img, nb_f.max().item()],
-            'bitstream_sha256_first8': sha256_of(dev_streams),
             'latency_ms_per_batch': {'mean': sum(lat_ms) / max(1, len(lat_ms)), 'max': max(lat_ms) if lat_ms else None,
                                      'what': 'encoder stage start -> logits of the same batch'},
             'host_issue_ms_per_step': 1e3 * issue_s / args.steps,
-            'roofline': dict(per_kernel[dom], kernel=dom, traffic=traffic, launches_timed=conv[dom][0],
-                             frac_steady=roof(dom, steady_ms)['frac'],
-                             steady={'kernel_ms': steady_ms, 'launches_averaged': len(steady), 'launches_dropped': 8,
-                                     'what': 'the same kernel in a tail run of {} steps of the same pipeline after the timed region '
-                                             '(pipeline full: the encoder stages of later steps and the coder share the CUs)'.format(steady_steps)}),
+            'roofline': dict(per_kernel[dom], kernel=dom, traffic=traffic, launches_timed=conv[dom][0]),
             'bottleneck_forward': {'ms_per_batch_sum_of_its_launches': fwd_ms,
                                    'launches_counted': sorted(per_kernel),
                                    'gflop_per_image': fwd_gflop,
@@ -633,23 +595,8 @@ def main():
                                    'frac_of_mfma_peak': fwd_gflop * args.bs / fwd_ms / PEAK_BF16_TFLOPS,
                                    # SURVEY 8(d)'s numerator only: the rider's FLOPs left out, its time left IN (a lower bound)
                                    'frac_8p3418': BOTTLENECK_GFLOP_PER_IMG * args.bs / fwd_ms / PEAK_BF16_TFLOPS,
-                                   # ... and with the rider's time taken out too, by its stand-alone cost (an estimate: inside the
-                                   # pipeline the launch that carries it stretches like every other)
-                                   'frac_8p3418_rider_time_removed': BOTTLENECK_GFLOP_PER_IMG * args.bs / max(1e-9, fwd_ms - max(0.0, solo_ms - plain_ms)) / PEAK_BF16_TFLOPS,
-                                   'head_2_0_rider': {'gflop_per_image': fwd_gflop - BOTTLENECK_GFLOP_PER_IMG,
-                                                      'stand_alone_ms': solo_ms - plain_ms,
-                                                      'what': 'layer2.0 conv1 + downsample of the task head, carried by the decoder\'s last launch '
-                                                              '(dec.conv4+head.2.0); stand_alone_ms = that launch minus dec.conv4 as a launch of its own'},
                                    'roofline_floor_ms_of_this_launch_structure': floor_ms,
-                                   'frac_of_floor': floor_ms / fwd_ms,
-                                   'stand_alone': {'ms_per_batch': solo_ms, 'frac_of_mfma_peak': fwd_gflop * args.bs / solo_ms / PEAK_BF16_TFLOPS,
-                                                   'what': 'the same launches (without the dequantise pass) on one stream with nothing beside them, 5 repetitions after the timed region',
-                                                   'kernels_ms': {k: round(v[1], 4) for k, v in sorted(solo_sum.items())},
-                                                   'frac_8p3418': BOTTLENECK_GFLOP_PER_IMG * args.bs / plain_ms / PEAK_BF16_TFLOPS,
-                                                   'ms_per_batch_8p3418': plain_ms,
-                                                   'kernels_ms_8p3418': {k: round(v[1], 4) for k, v in sorted(plain_sum.items())},
-                                                   'what_8p3418': 'SURVEY 8(d) basis: the bottleneck\'s ten layers alone (dec.conv4 as a launch of its '
-                                                                  'own, no head layer inside), 8.3418 GFLOP per image'}},
+                                   'frac_of_floor': floor_ms / fwd_ms},
             'kernel_rooflines': {k: {'bound': v['bound'], 'frac': round(v['frac'], 4), 'tflops': round(v['tflops'], 1),
                                      'gbs': round(v['gbs'], 1), 'ms': round(v['kernel_ms'], 4)}
                                  for k, v in sorted(per_kernel.items())},
@@ -668,12 +615,75 @@ def main():
                            'encode_Msym_per_s_per_stream': n_sym / ksum['rans_encode'][1] / 1e3,
                            'decode_Msym_per_s_per_stream': n_sym / ksum['rans_decode'][1] / 1e3}
         failed = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            # the same launches stand-alone: one stream, nothing beside them (the in-pipeline durations above are taken while the
+            # other MFMA stream and the coder share the chip with the launch: the sum of overlapped kernel durations counts shared
+            # time twice)
+            with torch.no_grad():
+                sym_s, hw_s = model.stage_front(x)
+                dec_s, _, _ = model.stage_coder(sym_s, hw_s, **pipe.coder_kwargs)
+                torch.cuda.synchronize(dev)
+                with hip.KernelTimer(select) as solo:
+                    for _ in range(5):
+                        model.stage_front(x)
+                        model.stage_back(dec_s, hw_s)
+                    torch.cuda.synchronize(dev)
+                solo_sum = {k: v for k, v in solo.summary().items() if launch_work(k) is not None}
+                solo_ms = sum(v[1] for v in solo_sum.values())
+                # ... and on SURVEY 8(d)'s own basis: the ten layers of the bottleneck and nothing else (8.3418 GFLOP per image), i.e.
+                # with the decoder's last conv as a launch of its own instead of the form that carries layer2.0's two 1x1 layers
+                with hip.KernelTimer(select) as solo_p:
+                    for _ in range(5):
+                        model.stage_front(x)
+                        model.stage_decoder(dec_s, hw_s)
+                    torch.cuda.synchronize(dev)
+                plain_sum = {k: v for k, v in solo_p.summary().items() if launch_work(k) is not None}
+                plain_ms = sum(v[1] for v in plain_sum.values())
+                del sym_s, dec_s
+            # steady state of the dominant kernel: a tail run of >= 60 steps after the timed region, the first 8
+            # launches dropped -- with the pipeline full the encoder stage of later steps and the coder share the CUs with it, which a
+            # 20-step region barely reaches
+            steady_steps = max(60, args.steps)
+            with hip.KernelTimer(lambda tag: tag == dom) as steady_t:
+                pipe.run(x, n_steps=steady_steps)
+                sync_all()
+            steady = [r[1].elapsed_time(r[2]) for r in steady_t.records if r[0] == dom][8:]
+            steady_ms = sum(steady) / max(1, len(steady))
+            # the device bitstreams of the first 8 images of this shard, and the symbols they were coded from
+            with torch.no_grad():
+                sym, hw = model.stage_front(x)
+                eb = model.bottleneck_layer.entropy_bottleneck
+                buf, off, nbs, sts = eb.encode_symbols_device(sym, hw[0] * hw[1])
+                assert int(sts.max().item()) == 0
+                dev_streams = eb.unpack_strings(buf[:8], off[:8], nbs[:8])
+                sym8 = sym[:8].cpu()
+            out['bitstream_sha256_first8'] = sha256_of(dev_streams)
+            out['roofline'].update(frac_steady=roof(dom, steady_ms)['frac'],
+                                   steady={'kernel_ms': steady_ms, 'launches_averaged': len(steady), 'launches_dropped': 8,
+                                           'what': 'the same kernel in a tail run of {} steps of the same pipeline after the timed region '
+                                                   '(pipeline full: the encoder stages of later steps and the coder share the CUs)'.format(steady_steps)})
+            out['bottleneck_forward'].update({
+                # SURVEY 8(d)'s numerator with the rider's time taken out too, by its stand-alone cost (an estimate: inside the
+                # pipeline the launch that carries it stretches like every other)
+                'frac_8p3418_rider_time_removed': BOTTLENECK_GFLOP_PER_IMG * args.bs / max(1e-9, fwd_ms - max(0.0, solo_ms - plain_ms)) / PEAK_BF16_TFLOPS,
+                'head_2_0_rider': {'gflop_per_image': fwd_gflop - BOTTLENECK_GFLOP_PER_IMG,
+                                   'stand_alone_ms': solo_ms - plain_ms,
+                                   'what': 'layer2.0 conv1 + downsample of the task head, carried by the decoder\'s last launch '
+                                           '(dec.conv4+head.2.0); stand_alone_ms = that launch minus dec.conv4 as a launch of its own'},
+                'stand_alone': {'ms_per_batch': solo_ms, 'frac_of_mfma_peak': fwd_gflop * args.bs / solo_ms / PEAK_BF16_TFLOPS,
+                                'what': 'the same launches (without the dequantise pass) on one stream with nothing beside them, 5 repetitions after the timed region',
+                                'kernels_ms': {k: round(v[1], 4) for k, v in sorted(solo_sum.items())},
+                                'frac_8p3418': BOTTLENECK_GFLOP_PER_IMG * args.bs / plain_ms / PEAK_BF16_TFLOPS,
+                                'ms_per_batch_8p3418': plain_ms,
+                                'kernels_ms_8p3418': {k: round(v[1], 4) for k, v in sorted(plain_sum.items())},
+                                'what_8p3418': 'SURVEY 8(d) basis: the bottleneck\'s ten layers alone (dec.conv4 as a launch of its '
+                                               'own, no head layer inside), 8.3418 GFLOP per image'}})
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out['precision_check'] = precision_check(model, x, dev)
             out['symbol_mismatch_rate'] = out['precision_check'][args.encoder_precision + '_encoder']['symbol_mismatch_rate']
             out['delta_bpp'] = out['precision_check'][args.encoder_precision + '_encoder']['delta_bpp']
             out['bpp_estimated'] = out['precision_check'][args.encoder_precision + '_encoder']['bpp_estimated']
-        if world == 1 and not args.no_cpu_baseline and args.encoder_precision == 'bf16':
+        if args.full and world == 1 and not args.no_cpu_baseline and args.encoder_precision == 'bf16':
             # the same K steps of the same pipeline with the reference-precision encoder (f32 operands on the f32 matrix cores):
             # the mode whose bitstreams are the f32 reference path's, measured by the same command as the headline figure
             model.set_encoder_precision('f32')
@@ -692,7 +702,7 @@ def main():
                                                                                   out['precision_check']['images']),
                                'what': 'the same pipeline with set_encoder_precision("f32"): symbols / bitstreams of the f32 reference '
                                        'path (the residual mismatch is f32 summation order against torch CPU); decoder + head bf16'}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out['cpu_baseline'] = cpu_baseline(8, model.state_dict(), dev_symbols=sym8, hw=hw[0] * hw[1])
                 out['bitstream_match'] = out['cpu_baseline'].get('bitstream_sha256_first8') == out['bitstream_sha256_first8']
@@ -700,12 +710,12 @@ def main():
                 out['cpu_baseline'] = {'value': None, 'unit': 'images/s', 'cores': os.cpu_count(), 'kind': 'port',
                                        'sample': 'failed: {!r}'.format(e)}
                 failed = 'cpu_baseline failed: {!r}'.format(e)
-        if world == 1 and not distributed and not args.no_secondary:
+        if args.full and world == 1 and not distributed and not args.no_secondary:
             # the other configurations through the SAME command (VERDICT r4 "builder-only numbers"): after the headline's timed
             # region, each on the package's stage pipeline (or the training step), a few steps each, compact rows in `secondary`
             del logits, nb, st, last
             out['secondary'] = secondary_lines(args, dev)
-        if world == 1 and not args.no_bs1:   # (behind the secondary rows: its graphs make streams of their own -- pipeline.pooled_stream)
+        if args.full and world == 1 and not args.no_bs1:   # (behind the secondary rows: its graphs make streams of their own -- pipeline.pooled_stream)
             out['bs1_eval'] = bs1_eval(model, x, dev)
         print(json.dumps(out))
         if failed:

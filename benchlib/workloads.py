@@ -1,5 +1,5 @@
 """`bench.py --workload mshp224 | seg513 | det800x1216 | fp_input` (BASELINE configs 3 - 5 and the hyperprior bottleneck) and the
-`secondary` rows of the default line."""
+`secondary` rows of the `--full` line."""
 import json
 import os
 import sys
@@ -248,7 +248,7 @@ def workload_bench(args, dev, rank, world, distributed, emit=True, cpu_baseline_
 
 
 def secondary_lines(args, dev):
-    """Compact rows of the other workloads and of the stage-1 training step, measured by the default invocation after its own
+    """Compact rows of the other workloads and of the stage-1 training step, measured by `bench.py --full` after its own
     timed region: {name: {'value', 'unit', 'ms_per_step', 'steps', ...}}; a workload that fails leaves {'error': ...}."""
     import copy
     import gc

@@ -53,8 +53,8 @@ def test_rccl_world1_inference_and_training_as_child_processes():
     if torch.cuda.is_initialized():
         pytest.skip('this process has already initialised the GPU: the RCCL child processes must be started first '
                     '(run the whole suite, or this file alone)')
-    # ---- inference line: process group, barriers, MAX all-reduce of the timing
-    line = _torchrun_bench(['--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-bs1'])
+    # ---- inference line: process group, barriers, MAX all-reduce of the timing (--full: the per-rank rows below)
+    line = _torchrun_bench(['--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-bs1'])
     assert line['n_gpus'] == 1 and line['steps'] == 2 and line['unit'] == 'images/s' and line['value'] > 0
     assert line['config']['process_group'].startswith('nccl'), line['config']['process_group']
     assert line['config']['ranks_reduced'] == 1, 'the device all-reduce of 1 over the RCCL group must count this rank'

@@ -22,8 +22,8 @@ for s in $STEPS; do
   case $s in
     tests) timeout 2700 python -m pytest tests -m gpu -x -q 2>&1 | tail -25 > $OUT/gpu_tests.log; tail -4 $OUT/gpu_tests.log;;
     smoke) timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; tail -2 $OUT/smoke.log;;
-    bench20) timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench20.json 2> $OUT/bench20.err; python tools/bench_brief.py $OUT/bench20.json; tail -3 $OUT/bench20.err;;
-    bench100) timeout 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; python tools/bench_brief.py $OUT/bench_default.json; tail -3 $OUT/bench_default.err;;
+    bench20) timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench20.json 2> $OUT/bench20.err; python tools/bench_brief.py $OUT/bench20.json; tail -3 $OUT/bench20.err;;
+    bench100) timeout 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; python tools/bench_brief.py $OUT/bench_default.json; tail -3 $OUT/bench_default.err;;
     ktimes) timeout 300 python tools/k_times.py --head 2>&1 | grep -v amdgpu.ids | tee $OUT/k_times.txt;;
     head) timeout 600 python tools/head_times.py > $OUT/head_times.txt 2>&1; tail -45 $OUT/head_times.txt;;
     clock) timeout 900 python tools/clock_probe.py --f32 --head 2>&1 | grep -v amdgpu.ids | tee $OUT/clock_probe.txt;;

@@ -6,8 +6,8 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 if [ -n "$TESTS" ]; then timeout 1500 python -m pytest $TESTS -m gpu -x -q 2>&1 | tail -25 > $OUT/tests.log; cat $OUT/tests.log; fi
 case $BENCH in
-  bench20) timeout 900 python bench.py --steps 20 --no-secondary > $OUT/bench20.json 2> $OUT/bench20.err; python tools/bench_brief.py $OUT/bench20.json; tail -3 $OUT/bench20.err;;
-  bench100) timeout 900 python bench.py --no-secondary > $OUT/bench100.json 2> $OUT/bench100.err; python tools/bench_brief.py $OUT/bench100.json; tail -3 $OUT/bench100.err;;
+  bench20) timeout 900 python bench.py --steps 20 --full --no-secondary > $OUT/bench20.json 2> $OUT/bench20.err; python tools/bench_brief.py $OUT/bench20.json; tail -3 $OUT/bench20.err;;
+  bench100) timeout 900 python bench.py --full --no-secondary > $OUT/bench100.json 2> $OUT/bench100.err; python tools/bench_brief.py $OUT/bench100.json; tail -3 $OUT/bench100.err;;
 esac
 python - <<PY
 import json
