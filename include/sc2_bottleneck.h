@@ -307,6 +307,34 @@ int sc2_conv_f32_chunk_channels(int Cout);
 int sc2_conv2d_f32_fwd(const sc2_conv_desc *d, const float *x, const float *w_frag, void *y, const float *ep_x,
                        const float *ep_beta, void *stream);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Split-bf16 analysis transform: the same convolution / GDN1 with every f32 operand written as  */
+/* a sum of n_parts bf16 numbers (hi = bf16_rne(x), lo = bf16_rne(x - hi), lo2 = bf16_rne(x - hi  */
+/* - lo)) and the part products (i, j) with i + j <= n_parts - 1 accumulated in f32 on            */
+/* v_mfma_f32_16x16x32_bf16: 3 products (n_parts 2) or 6 (n_parts 3) per k.  Each product is      */
+/* exact in f32, so only the dropped products separate the result from an f32 convolution.        */
+/* `FPBasedResNetBottleneck.set_encoder_precision('bf16x3' / 'bf16x6')`; csrc/conv_split.hip.     */
+/* ------------------------------------------------------------------------------------------ */
+/* Output channels per weight chunk for a given Cout (32, 48 or 96): the packing unit of w_frag below. */
+int sc2_conv_split_chunk_channels(int Cout);
+/* d       : as for sc2_conv2d_f32_fwd, but x is always f32 NHWC (k_order must be 0; Kpad / Cout_pad are ignored): Cin % 4 == 0,
+ *           square stride / padding, no output scatter.  a_op: NONE / ABS / SQUARE, applied to the f32 value before the split.
+ *           epilogue: NONE, BIAS, GDN, IGDN, FUSED_GDN / FUSED_IGDN (a_op NONE, Cout <= 96 with ceil(Cout / 16) * 16 == the chunk width),
+ *           in the operation order of sc2_conv2d_f32_fwd; the fused form is bit-identical to the two launches.
+ * n_parts : 2 or 3 (anything else: SC2_ERR_UNSUPPORTED); w_frag and gamma_frag must be packed for the same value.
+ * x       : f32 NHWC [N,H,W,Cin], N*H*W*Cin*4 below 0x7FF00000 bytes (SC2_ERR_UNSUPPORTED otherwise)
+ * w_frag  : bf16, [chunks][steps][n_parts][NT][64 lanes][8] with cc = sc2_conv_split_chunk_channels(Cout), NT = cc / 16, chunks =
+ *           ceil(Cout / cc), steps = ceil(KH*KW*Cin / 32); entry (ch, s, part, nt, lane = q*16 + r, j) = part `part` of
+ *           W[ch*cc + nt*16 + r][k = 32 s + 16 (j >> 2) + 4 q + (j & 3)], k = (kh*KW + kw)*Cin + ci, zero beyond Cout / K.
+ * ep_x    : f32 NHWC [N,OH,OW,Cout] for GDN / IGDN (NULL otherwise)
+ * gamma_frag : FUSED_* only (NULL otherwise; unlike sc2_conv2d_f32_fwd, gamma does not travel in ep_x): the effective gamma as
+ *           the w_frag of a 1x1 conv Cout -> Cout, same packing and n_parts
+ * ep_beta : f32 [Cout] (beta, bias, or the medians for symbols)
+ * y       : SC2_OUT_F32_NHWC [N,OH,OW,Cout] / SC2_OUT_F32_NCHW / SC2_OUT_I32_NCHW_SYM (round_half_even(acc - ep_beta[c])).
+ * Unsupported geometry returns SC2_ERR_UNSUPPORTED. */
+int sc2_conv2d_split_fwd(const sc2_conv_desc *d, int n_parts, const float *x, const void *w_frag, void *y, const float *ep_x,
+                         const void *gamma_frag, const float *ep_beta, void *stream);
+
 /* First decoder stage in ONE launch: y = GDN1_512(Conv2d(Cin -> 512, k2, s1, p1, bias=False)(x)) with the inverse
  * (multiplicative) or forward (divisive) normalisation: t = conv(x); y = t * (beta + gamma |t|) resp. t / (...).
  * Replaces decoder[0] + decoder[1] of FPBasedResNetBottleneck (sc2bench/models/layer.py:486-488); the 512-channel

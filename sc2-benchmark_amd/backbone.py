@@ -261,7 +261,8 @@ class SplittableResNet(UpdatableBackbone):
 
     def set_encoder_precision(self, precision):
         """'f32': the bottleneck's analysis transform with f32 operands, so that symbols / byte streams / bpp are the f32
-        reference path's (FPBasedResNetBottleneck.set_encoder_precision); 'bf16': the fast default."""
+        reference path's (FPBasedResNetBottleneck.set_encoder_precision); 'bf16': the fast default; 'bf16x3' / 'bf16x6': f32-grade
+        symbols from split operands on the bf16 matrix cores (same docstring: what they cost and when to use which)."""
         self._drop_eval_graphs()
         self.bottleneck_layer.set_encoder_precision(precision)
         return self

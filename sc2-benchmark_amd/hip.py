@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     'sc2_nchw_f32_to_nhwc_bf16', 'sc2_nhwc_bf16_to_nchw_f32', 'sc2_avgpool_nhwc', 'sc2_maxpool_nhwc', 'sc2_bn_ws_floats', 'sc2_bn_train_fwd', 'sc2_bn_train_bwd', 'sc2_fc_fwd',
     'sc2_conv_weight_rows', 'sc2_conv_weight_pitch', 'sc2_conv_fused_gdn_supported', 'sc2_conv_patch_supported',
     'sc2_conv2d_fwd', 'sc2_gdn1_bwd_gemm', 'sc2_colsum_bf16', 'sc2_nchw_f32_to_nhwc_f32', 'sc2_conv_f32_chunk_channels', 'sc2_conv2d_f32_fwd',
+    'sc2_conv_split_chunk_channels', 'sc2_conv2d_split_fwd',
     'sc2_conv2x2_gdn512_supported', 'sc2_conv2x2_gdn512_fwd', 'sc2_conv1x1_stream_supported', 'sc2_conv1x1_stream_mask_supported', 'sc2_conv1x1_stream_fwd', 'sc2_conv1x1_pair_supported', 'sc2_conv1x1_pair_fwd',
     'sc2_conv0_gdn96_supported', 'sc2_conv0_gdn96_fwd', 'sc2_conv0_gdn96_nchw_fwd', 'sc2_conv2_gdn48_supported', 'sc2_conv2_gdn48_fwd', 'sc2_conv2x2_c48_supported', 'sc2_conv2x2_c48_fwd', 'sc2_conv1x1_kres_supported', 'sc2_conv1x1_kres_fwd', 'sc2_conv1x1_win_supported', 'sc2_conv1x1_win_fwd', 'sc2_conv3x3_win_supported', 'sc2_conv3x3_win_fwd', 'sc2_conv3x3s2_win_supported', 'sc2_conv3x3s2_win_fwd', 'sc2_conv2x2_win_supported', 'sc2_conv2x2_win_fwd', 'sc2_conv2x2_win_tail_supported', 'sc2_conv2x2_win_tail_fwd', 'sc2_conv2d_wgrad', 'sc2_gdn_bwd_pre', 'sc2_gdn_bwd_post', 'sc2_gdn1_rows_supported', 'sc2_gdn1_rows_fwd', 'sc2_gdn1_rows_bwd',
     'sc2_eb_forward', 'sc2_eb_backward', 'sc2_eb_bits_partial_len', 'sc2_eb_symbols', 'sc2_eb_dequantize',
@@ -210,6 +211,8 @@ def lib():
     L.sc2_nchw_f32_to_nhwc_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp]
     L.sc2_conv_f32_chunk_channels.argtypes = [i32]
     L.sc2_conv2d_f32_fwd.argtypes = [ctypes.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp]
+    L.sc2_conv_split_chunk_channels.argtypes = [i32]
+    L.sc2_conv2d_split_fwd.argtypes = [ctypes.POINTER(ConvDesc), i32, vp, vp, vp, vp, vp, vp, vp]
     L.sc2_conv2x2_gdn512_supported.argtypes = [i32] * 6
     L.sc2_conv2x2_gdn512_fwd.argtypes = [vp, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]
     L.sc2_conv0_gdn96_supported.argtypes = [i32, i32, i32]
@@ -1621,6 +1624,103 @@ def conv2d_f32_fwd(x_nhwc, w_frag, cout, kh, kw, stride, padding, a_op=AOP_NONE,
     with _timed(tag or 'conv_f32'):
         _check(lib().sc2_conv2d_f32_fwd(ctypes.byref(d), _ptr(x_nhwc), _ptr(w_frag), _ptr(y), _ptr(ep_x), _ptr(ep_beta),
                                         _stream()), 'conv2d_f32_fwd')
+    return y
+
+
+# --------------------------------------------------------------------------------------------- #
+# split-bf16 convolution / GDN1 (f32 operands as sums of bf16 parts on the bf16 matrix cores): csrc/conv_split.hip
+# --------------------------------------------------------------------------------------------- #
+def conv_split_fused_gdn_supported(cout):
+    """conv + GDN1 in one split launch: every channel of a pixel in one wave (Cout <= 96) and ceil(Cout / 16) * 16 == the chunk
+    width (96 / 48 / 32 / 20 ... yes; 64 or 16 no: two launches)."""
+    cout = int(cout)
+    return cout <= 96 and (cout + 15) // 16 * 16 == int(lib().sc2_conv_split_chunk_channels(cout))
+
+
+def split_bf16(t, ns):
+    """f32 tensor -> ns bf16 tensors whose sum approximates t: hi = bf16(t), lo = bf16(t - hi), lo2 = bf16(t - hi - lo)."""
+    parts, r = [], t.float().clone()
+    for _ in range(ns):
+        p = r.to(torch.bfloat16)
+        parts.append(p)
+        r = r - p.float()
+    return parts
+
+
+def pack_conv_split(weight, ns, cin_pad=None):
+    """Conv weight [Cout, Cin, KH, KW] (any float dtype) -> the bf16 fragment stream of sc2_conv2d_split_fwd for ns (2 or 3) parts:
+    [chunks][steps][ns][NT][64 lanes][8], entry (ch, s, part, nt, lane = q*16 + r, j) = part `part` of
+    W[ch*cc + nt*16 + r][32 s + 16 (j >> 2) + 4 q + (j & 3)] with k = (kh*KW + kw)*cin_pad + ci."""
+    ns = int(ns)
+    if ns not in (2, 3):
+        raise Sc2Error('pack_conv_split: ns must be 2 or 3, got {}'.format(ns))
+    w = weight.detach().float()
+    Cout, Cin, KH, KW = w.shape
+    cin_pad = (Cin + 3) // 4 * 4 if cin_pad is None else cin_pad
+    cc = int(lib().sc2_conv_split_chunk_channels(Cout))
+    chunks, NT = (Cout + cc - 1) // cc, cc // 16
+    K = KH * KW * cin_pad
+    steps = (K + 31) // 32
+    m = torch.zeros((chunks * cc, KH, KW, cin_pad), dtype=torch.float32, device=w.device)
+    m[:Cout, :, :, :Cin] = w.permute(0, 2, 3, 1)
+    m = torch.nn.functional.pad(m.reshape(chunks * cc, K), (0, steps * 32 - K))
+    m = torch.stack(split_bf16(m, ns))                        # [part, row, k]
+    m = m.reshape(ns, chunks, NT, 16, steps, 2, 4, 4)         # [part, ch, nt, r, s, half, q, e]
+    return m.permute(1, 4, 0, 2, 6, 3, 5, 7).contiguous()     # [ch, s, part, nt, q, r, half, e]
+
+
+def conv2d_split_fwd(x_nhwc, w_frag, cout, kh, kw, stride, padding, ns, a_op=AOP_NONE, epilogue=EPI_NONE, out_format=None,
+                     ep_x=None, ep_beta=None, out=None, tag=None, cin_real=0, x_is_nchw_rgb=False):
+    """conv2d_f32_fwd's interface on the split-bf16 kernels (ns = 2: three bf16 products per k, ns = 3: six; w_frag and, for the
+    fused epilogues, ep_x = gamma from pack_conv_split with the same ns).  x_is_nchw_rgb: x_nhwc is the f32 NCHW image; it goes
+    through its NHWC copy (same result).  cin_real is accepted and ignored (the padding channel's products are exact zeros)."""
+    _dev(x_nhwc, 'x')
+    assert x_nhwc.dtype == torch.float32 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
+    assert w_frag.dtype == torch.bfloat16 and w_frag.is_contiguous() and w_frag.dim() == 8 and w_frag.shape[2] == ns
+    out_format = OUT_F32_NHWC if out_format is None else out_format
+    if x_is_nchw_rgb:
+        assert x_nhwc.shape[1] == 3
+        x_nhwc = nchw_f32_to_nhwc_f32(x_nhwc, 4)
+    N, H, W, Cin = x_nhwc.shape
+    sh = stride[0] if isinstance(stride, (tuple, list)) else stride
+    ph = padding[0] if isinstance(padding, (tuple, list)) else padding
+    OH, OW = (H + 2 * ph - kh) // sh + 1, (W + 2 * ph - kw) // sh + 1
+    steps = (kh * kw * Cin + 31) // 32
+    if w_frag.shape[1] != steps or w_frag.shape[0] * w_frag.shape[3] * 16 < cout:
+        raise Sc2Error('conv2d_split_fwd: w_frag {} was not packed for Cout {} K {}'.format(tuple(w_frag.shape), cout, kh * kw * Cin))
+    d = ConvDesc(N=N, H=H, W=W, Cin=Cin, Cout=cout, KH=kh, KW=kw, stride_h=sh, stride_w=sh, pad_h=ph, pad_w=ph, OH=OH, OW=OW,
+                 a_op=a_op, epilogue=epilogue, out_format=out_format, Kpad=0, Cout_pad=0, out_H=0, out_W=0, out_stride_h=0,
+                 out_stride_w=0, out_off_h=0, out_off_w=0, k_order=0)
+    if out_format == OUT_F32_NHWC:
+        y = torch.empty((N, OH, OW, cout), dtype=torch.float32, device=x_nhwc.device)
+    elif out_format == OUT_F32_NCHW:
+        y = torch.empty((N, cout, OH, OW), dtype=torch.float32, device=x_nhwc.device)
+    else:
+        assert out_format == OUT_I32_NCHW_SYM
+        if out is not None:
+            assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == N * cout * OH * OW
+            y = out.view(N, cout, OH, OW)
+        else:
+            y = torch.empty((N, cout, OH, OW), dtype=torch.int32, device=x_nhwc.device)
+    gamma = None
+    if epilogue in (EPI_FUSED_GDN, EPI_FUSED_IGDN):
+        gamma, ep_x = ep_x, None
+        if gamma is not None:
+            _dev(gamma, 'gamma')
+            assert gamma.dtype == torch.bfloat16 and gamma.is_contiguous() and gamma.dim() == 8 and gamma.shape[2] == ns
+            if gamma.shape[0] != 1 or gamma.shape[1] != (cout + 31) // 32 or gamma.shape[3] != w_frag.shape[3]:
+                raise Sc2Error('conv2d_split_fwd: gamma {} was not packed as a 1x1 weight of {} channels'.format(tuple(gamma.shape), cout))
+    for t in (ep_x, ep_beta):
+        if t is not None:
+            _dev(t, 'epilogue operand')
+            assert t.dtype == torch.float32 and t.is_contiguous()
+    if ep_x is not None:
+        assert ep_x.numel() == N * OH * OW * cout
+    if ep_beta is not None:
+        assert ep_beta.numel() >= cout
+    with _timed(tag or 'conv_split'):
+        _check(lib().sc2_conv2d_split_fwd(ctypes.byref(d), int(ns), _ptr(x_nhwc), _ptr(w_frag), _ptr(y), _ptr(ep_x), _ptr(gamma),
+                                          _ptr(ep_beta), _stream()), 'conv2d_split_fwd')
     return y
 
 

@@ -7,6 +7,8 @@ class names, constructor arguments, module paths (`encoder`, `decoder`, `entropy
 the reference's YAML files builds this class unchanged.  The arithmetic runs in libsc2amd.so: activations
 stay bf16 NHWC between the implicit-GEMM kernels; GDN1 is a 1x1 MFMA GEMM with fused epilogue.
 """
+import functools
+
 import torch
 from torch import nn
 
@@ -16,6 +18,7 @@ from .entropy import (CompressionModel, GDN1, GaussianConditional, HipConv2d, Hi
 
 LAYER_CLASS_DICT = dict()
 LAYER_FUNC_DICT = dict()
+_SPLIT_PARTS = {'bf16x3': 2, 'bf16x6': 3}   # encoder precision -> bf16 parts per operand (csrc/conv_split.hip)
 
 
 def register_layer_class(cls):
@@ -166,51 +169,64 @@ class FPBasedResNetBottleneck(BaseBottleneck):
         differ from the reference's f32 CPU path (a latent within bf16 rounding distance of a .5 boundary flips).
         'f32': f32 operands on the f32 matrix cores (csrc/conv_f32.hip; an exact f32 fma chain, 1/16 of the bf16 rate): the
         symbols -- hence the byte streams and bpp -- are the reference's up to the order of f32 additions (~1e-5 of the
-        symbols).  Only the encoder: the decoder's precision moves logits within tolerance, never a bitstream."""
-        if precision not in ('bf16', 'f32'):
-            raise ValueError("encoder precision must be 'bf16' or 'f32', got {!r}".format(precision))
+        symbols).
+        'bf16x3' / 'bf16x6': f32 activations and weights written as sums of two / three bf16 parts, the part products with index
+        sum <= 1 / <= 2 (three / six per k) accumulated in f32 on the bf16 matrix cores (csrc/conv_split.hip).  Every product is
+        exact, so the error is that of the dropped products: 'bf16x3' leaves 5e-6 of the symbols different from the f32 oracle
+        (600 times fewer than 'bf16'), 'bf16x6' 6.5e-7, half of what 'f32' measures, at 0.72 / 0.91 of the time of 'f32'.  Use
+        'bf16x3' when most images should code to the reference's bytes at a fraction of the cost of 'f32', 'bf16x6' when as
+        many as possible should.  Measured times: DESIGN.md row g3.
+        Only the encoder: the decoder's precision moves logits within tolerance, never a bitstream."""
+        if precision not in ('bf16', 'f32') + tuple(_SPLIT_PARTS):
+            raise ValueError("encoder precision must be 'bf16', 'f32', 'bf16x3' or 'bf16x6', got {!r}".format(precision))
         self.encoder_precision = precision
         return self
 
     set_compute_dtype = set_encoder_precision    # the bottleneck-level switch VERDICT r2 asks for, under that name
 
-    def _f32_pack(self, mod):
-        """cached f32 fragment-major operands of one analysis module: conv -> (weights, bias or None, padded Cin); GDN1 ->
-        (effective gamma as a 1x1 conv, effective beta)."""
+    def _f32_pack(self, mod, ns=0):
+        """cached fragment-major operands of one analysis module: conv -> (weights, bias or None, padded Cin); GDN1 ->
+        (effective gamma as a 1x1 conv, effective beta).  ns = 0: f32 (hip.pack_conv_f32); 2 / 3: bf16 parts (hip.pack_conv_split)."""
         cache = self.__dict__.setdefault('_f32_cache', {})
+        pack = (lambda w: hip.pack_conv_split(w, ns)) if ns else hip.pack_conv_f32
         params = [q for q in (getattr(mod, 'weight', None), getattr(mod, 'bias', None), getattr(mod, 'beta', None),
                               getattr(mod, 'gamma', None)) if q is not None]
         key = tuple((q._version, q.data_ptr(), str(q.device)) for q in params)
-        ent = cache.get(id(mod))
+        ent = cache.get((id(mod), ns))
         if ent is None or ent[0] != key:
             with torch.no_grad():
                 if isinstance(mod, GDN1):
                     C = mod.in_channels
                     gamma = mod.gamma_reparam(mod.gamma).float().reshape(C, C, 1, 1)
-                    ent = (key, hip.pack_conv_f32(gamma), mod.beta_reparam(mod.beta).float().contiguous())
+                    ent = (key, pack(gamma), mod.beta_reparam(mod.beta).float().contiguous())
                 else:
                     bias = None if mod.bias is None else mod.bias.detach().float().contiguous()
-                    ent = (key, hip.pack_conv_f32(mod.weight), bias)
-            cache[id(mod)] = ent
+                    ent = (key, pack(mod.weight), bias)
+            cache[(id(mod), ns)] = ent
         return ent[1], ent[2]
 
-    def _analysis_f32(self, x, symbols_for=None, out=None):
+    def _analysis_f32(self, x, symbols_for=None, out=None, ns=0, slice_bytes=0x7FF00000 - 1):
         """encoder(x) with f32 operands (set_encoder_precision('f32')): every Conv2d / GDN1 of the analysis stack as one
-        launch of sc2_conv2d_f32_fwd on f32 NHWC activations; the last conv writes the f32 NCHW latent or the symbols."""
+        launch of sc2_conv2d_f32_fwd on f32 NHWC activations; the last conv writes the f32 NCHW latent or the symbols.
+        ns = 2 / 3 ('bf16x3' / 'bf16x6'): the same walk on sc2_conv2d_split_fwd.  slice_bytes: the largest f32 tensor of a launch."""
         mods = list(self._g_a())
+        if ns:
+            conv, fused_ok, sfx = functools.partial(hip.conv2d_split_fwd, ns=ns), hip.conv_split_fused_gdn_supported, '.bf16x{}'.format(3 * (ns - 1))
+        else:
+            conv, fused_ok, sfx = hip.conv2d_f32_fwd, hip.conv_f32_fused_gdn_supported, '.f32'
         # sc2_conv2d_f32_fwd addresses activations through 32-bit buffer descriptors: every f32 tensor of a launch stays below
         # 2 GB (include/sc2_bottleneck.h).  The widest map of the stack is the first stage's output (C0 x H/2 x W/2 floats per
         # image: 4.8 MB at 224 x 224, i.e. ~445 images); larger batches run as slices of the batch (ADVICE r4)
         if x.dim() == 4 and x.shape[0] > 1:
             per_image = 4 * max(x.shape[1] * x.shape[2] * x.shape[3],
                                 max(getattr(m, 'out_channels', 0) for m in mods) * ((x.shape[2] + 1) // 2) * ((x.shape[3] + 1) // 2))
-            n_max = max(1, (0x7FF00000 - 1) // per_image)
+            n_max = max(1, slice_bytes // per_image)
             if x.shape[0] > n_max:
                 parts = []
                 flat = None if out is None else out.view(x.shape[0], -1)
                 for i in range(0, x.shape[0], n_max):
                     parts.append(self._analysis_f32(x[i:i + n_max].contiguous(), symbols_for=symbols_for,
-                                                    out=None if flat is None else flat[i:i + n_max]))
+                                                    out=None if flat is None else flat[i:i + n_max], ns=ns, slice_bytes=slice_bytes))
                 res = torch.cat(parts)
                 return res if out is None else out.view(res.shape)
         # an RGB image goes to the first convolution as it is (f32 NCHW, three planes read in place); anything else as f32 NHWC
@@ -227,33 +243,33 @@ class FPBasedResNetBottleneck(BaseBottleneck):
             if isinstance(mod, GDN1):
                 if type(mod) is not GDN1:
                     raise hip.Sc2Error('f32 analysis: {} is not supported'.format(type(mod).__name__))
-                gamma, beta = self._f32_pack(mod)
-                h = hip.conv2d_f32_fwd(h, gamma, mod.in_channels, 1, 1, 1, 0, a_op=hip.AOP_ABS,
-                                       epilogue=hip.EPI_IGDN if mod.inverse else hip.EPI_GDN, ep_x=h, ep_beta=beta,
-                                       out_format=hip.OUT_F32_NCHW if last else hip.OUT_F32_NHWC, tag=mod._tag + '.f32')
+                gamma, beta = self._f32_pack(mod, ns)
+                h = conv(h, gamma, mod.in_channels, 1, 1, 1, 0, a_op=hip.AOP_ABS,
+                         epilogue=hip.EPI_IGDN if mod.inverse else hip.EPI_GDN, ep_x=h, ep_beta=beta,
+                         out_format=hip.OUT_F32_NCHW if last else hip.OUT_F32_NHWC, tag=mod._tag + sfx)
                 continue
             if not isinstance(mod, nn.Conv2d) or mod.groups != 1 or mod.dilation != (1, 1) or mod.stride[0] != mod.stride[1] \
                     or mod.padding[0] != mod.padding[1]:
                 raise hip.Sc2Error('f32 analysis: unsupported module {}'.format(mod))
-            w, bias = self._f32_pack(mod)
+            w, bias = self._f32_pack(mod, ns)
             kh, kw = mod.kernel_size
             nxt = mods[i + 1] if i + 1 < len(mods) else None
             if (self.fuse_gdn and type(nxt) is GDN1 and bias is None and nxt.in_channels == mod.out_channels <= 96 and
-                    hip.conv_f32_fused_gdn_supported(mod.out_channels) and i + 2 < len(mods)):
+                    fused_ok(mod.out_channels) and i + 2 < len(mods)):
                 # conv + GDN1 in one launch: the wave that owns a pixel's channels applies the normalisation to its accumulators
-                gamma, beta = self._f32_pack(nxt)
-                h = hip.conv2d_f32_fwd(h, w, mod.out_channels, kh, kw, mod.stride, mod.padding,
-                                       epilogue=hip.EPI_FUSED_IGDN if nxt.inverse else hip.EPI_FUSED_GDN, ep_x=gamma, ep_beta=beta,
-                                       out_format=hip.OUT_F32_NHWC, tag=mod._tag + '.f32+' + nxt._tag + '.f32', cin_real=mod.in_channels, **first_kw)
+                gamma, beta = self._f32_pack(nxt, ns)
+                h = conv(h, w, mod.out_channels, kh, kw, mod.stride, mod.padding,
+                         epilogue=hip.EPI_FUSED_IGDN if nxt.inverse else hip.EPI_FUSED_GDN, ep_x=gamma, ep_beta=beta,
+                         out_format=hip.OUT_F32_NHWC, tag=mod._tag + sfx + '+' + nxt._tag + sfx, cin_real=mod.in_channels, **first_kw)
                 fused_into_previous = True
                 continue
             if last and symbols_for is not None and bias is None:
-                sym = hip.conv2d_f32_fwd(h, w, mod.out_channels, kh, kw, mod.stride, mod.padding, out_format=hip.OUT_I32_NCHW_SYM,
-                                         ep_beta=symbols_for._median_vector(), out=out, tag=mod._tag + '.f32', cin_real=mod.in_channels, **first_kw)
+                sym = conv(h, w, mod.out_channels, kh, kw, mod.stride, mod.padding, out_format=hip.OUT_I32_NCHW_SYM,
+                           ep_beta=symbols_for._median_vector(), out=out, tag=mod._tag + sfx, cin_real=mod.in_channels, **first_kw)
                 return sym
-            h = hip.conv2d_f32_fwd(h, w, mod.out_channels, kh, kw, mod.stride, mod.padding,
-                                   epilogue=hip.EPI_NONE if bias is None else hip.EPI_BIAS, ep_beta=bias,
-                                   out_format=hip.OUT_F32_NCHW if last else hip.OUT_F32_NHWC, tag=mod._tag + '.f32', cin_real=mod.in_channels, **first_kw)
+            h = conv(h, w, mod.out_channels, kh, kw, mod.stride, mod.padding,
+                     epilogue=hip.EPI_NONE if bias is None else hip.EPI_BIAS, ep_beta=bias,
+                     out_format=hip.OUT_F32_NCHW if last else hip.OUT_F32_NHWC, tag=mod._tag + sfx, cin_real=mod.in_channels, **first_kw)
         if symbols_for is None:
             return h
         sym = symbols_for.quantize(h, 'symbols', self._get_means(h))
@@ -270,8 +286,8 @@ class FPBasedResNetBottleneck(BaseBottleneck):
         _require_device(x, 'FPBasedResNetBottleneck')
         c0, g1, c2, g3, c4 = self._g_a()
         x = x.float()
-        if self.encoder_precision == 'f32':
-            return self._analysis_f32(x, symbols_for=symbols_for, out=out)
+        if self.encoder_precision == 'f32' or self.encoder_precision in _SPLIT_PARTS:
+            return self._analysis_f32(x, symbols_for=symbols_for, out=out, ns=_SPLIT_PARTS.get(self.encoder_precision, 0))
         fuse0 = self.fuse_gdn and c0.out_channels in hip.FUSABLE_GDN_CHANNELS
         fuse2 = self.fuse_gdn and c2.out_channels in hip.FUSABLE_GDN_CHANNELS
         if self._uses_pair_conv0(x):
