@@ -32,58 +32,24 @@
 
 #include <type_traits>
 
-#include "sc2_common.h"
+#include "conv_precise.h"
 
 namespace {
 
-struct F32Args {
-    const float *__restrict__ x;       // f32 NHWC [N, H, W, Cin] (Cin % 4 == 0)
+struct F32Args : PreciseArgs {         // (n_steps = K_pad / 16; ep_x: with the fused epilogues, gamma's fragments)
     const float *__restrict__ w;       // fragment-major weights
-    const float *__restrict__ ep_x;    // f32 NHWC [N, OH, OW, Cout] (GDN operand) or null
-    const float *__restrict__ ep_beta; // f32 [Cout]: beta (GDN) / medians (symbols) or null
-    void *__restrict__ y;
-    int N, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW;
-    int a_op, epilogue, out_format;
-    int n_steps;                       // K_pad / 16
-    long long M;                       // N * OH * OW
-    unsigned x_bytes;                  // size of x (< 2 GB: the activation loads go through a buffer descriptor)
     unsigned y_bytes;                  // size of y when it is < 4 GB (the persistent first stage stores through a descriptor), else 0
-    unsigned w_bytes;                  // size of w
-    unsigned ring_off;                 // LDS offset of the weight ring (after the tap table, 1 KB aligned)
     int skip_j3;                       // Cin == 4 carrying 3 real channels: every fourth k is a zero channel times a zero weight
     int planar;                        // with skip_j3: x is f32 NCHW [N, 3, H, W] (the reference's input layout), read in place
 };
 
-typedef __attribute__((ext_vector_type(4))) float f4_t;
+typedef f32x4_t f4_t;
 
-#ifndef SC2_F32_SYNC
-#define SC2_F32_SYNC 1   // a workgroup barrier every two k-steps: the four waves read the SAME weight fragments, and kept within two
-#endif                   // steps of each other three of the four reads are L1 hits
 #ifndef SC2_F32_WAVES
 #define SC2_F32_WAVES 4  // waves per SIMD the register allocation must allow for the narrow tiles (NT * MT <= 6)
 #endif
-#ifndef SC2_F32_MT4
-#define SC2_F32_MT4 0   // experiment: four pixel tiles per wave for the 48-channel chunk (twice the MFMAs per weight fragment)
-#endif
 
 typedef __attribute__((address_space(3))) void *f32_lds_ptr_t;
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t f32_rsrc_t;
-__device__ __forceinline__ f32_rsrc_t f32_make_rsrc(const float *base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ f4_t f32_buf_load16(f32_rsrc_t r, uint32_t voff) {   // out of range: zeros
-    return __builtin_bit_cast(f4_t, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
-}
-__device__ __forceinline__ void f32_buf_load_lds16(f32_rsrc_t r, uint32_t lds_addr, uint32_t voff) {   // lane l -> LDS lds_addr + 16 l
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (f32_lds_ptr_t)(uintptr_t)lds_addr, 16, (int)voff, 0, 0, 0);
-}
-#else   // host pass: stand-ins
-typedef int f32_rsrc_t;
-__device__ __forceinline__ f32_rsrc_t f32_make_rsrc(const float *, uint32_t) { return 0; }
-__device__ __forceinline__ f4_t f32_buf_load16(f32_rsrc_t, uint32_t) { return f4_t{0.f, 0.f, 0.f, 0.f}; }
-__device__ __forceinline__ void f32_buf_load_lds16(f32_rsrc_t, uint32_t, uint32_t) {}
-#endif
 // LDS reads of the k loop are inline asm (and its barriers raw s_barrier): hipcc knows that a direct-to-LDS load writes LDS and
 // drains the vector-memory counter in front of every LDS access it can see -- the operand prefetch with it (conv2_gdn48.hip).
 __device__ __forceinline__ f4_t f32_lds_read16(uint32_t addr) {
@@ -134,45 +100,15 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 ? SC2_F32_WAVES : SC2_F32_WAVES1
     extern __shared__ int2 ktab[];     // [n_steps * 4]: {byte offset of the lane's 4 k inside the window, kh | kw << 16}
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 15, q = lane >> 4;
-    for (int e = tid; e < p.n_steps * 4; e += 256) {
-        const int k0 = (e >> 2) * 16 + (e & 3) * 4;
-        const int tap = k0 / p.Cin, ci = k0 - tap * p.Cin;
-        int2 v;
-        if (tap < p.KH * p.KW) {
-            const int kh = tap / p.KW, kw = tap - kh * p.KW;
-            v.x = p.planar ? (kh * p.W + kw) * 4 : ((kh * p.W + kw) * p.Cin + ci) * 4;      // BYTE offset inside the window
-            v.y = kh | (kw << 16);
-        } else {            // K padding: never in bounds (its weights are zero too)
-            v.x = 0;
-            v.y = 0x7FFF | (0x7FFF << 16);
-        }
-        ktab[e] = v;
-    }
+    // (entry e = quad (e & 3) of step e >> 2 = k quad e; the planar form addresses a channel plane: one float per pixel)
+    for (int e = tid; e < p.n_steps * 4; e += 256) ktab[e] = precise_tap_entry(p, e, p.planar ? 1 : p.Cin);
     __syncthreads();
 
     const long long m_base = ((long long)blockIdx.x * 4 + wave) * (MT * 16);
     const int chunk = blockIdx.y;                                  // NT * 16 output channels per chunk
-    // the lane's A rows: pixel m_base + mt * 16 + r
-    // (byte offsets modulo 2^32: a window that starts above / left of the image has a negative base, but base + tap offset of
-    //  every tap that is INSIDE the image is a plain offset below x_bytes < 2^31)
     uint32_t a_base[MT];
     int ih0[MT], iw0[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        const long long m = m_base + mt * 16 + r;
-        if (m < p.M) {                             // (M < 2^31, checked by the host: 32-bit divisions)
-            const uint32_t ohw_u = (uint32_t)(p.OH * p.OW), n = (uint32_t)m / ohw_u;
-            const int rem = (int)((uint32_t)m - n * ohw_u);
-            const int oh = (int)((uint32_t)rem / (uint32_t)p.OW), ow = rem - oh * p.OW;
-            ih0[mt] = oh * p.stride - p.pad;
-            iw0[mt] = ow * p.stride - p.pad;
-            a_base[mt] = p.planar ? (uint32_t)(((((long long)n * 3 * p.H + ih0[mt]) * (long long)p.W + iw0[mt])) * 4)
-                                  : (uint32_t)(((((long long)n * p.H + ih0[mt]) * (long long)p.W + iw0[mt]) * p.Cin) * 4);
-        } else {
-            ih0[mt] = iw0[mt] = -(1 << 20);       // every tap out of bounds: zeros
-            a_base[mt] = 0;
-        }
-    }
+    precise_rows<MT>(p, m_base, r, p.planar ? 3 * p.H : p.H, p.planar ? 1 : p.Cin, a_base, ih0, iw0);
 
     f4_t acc[MT][NT];
 #pragma unroll
@@ -192,7 +128,7 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 ? SC2_F32_WAVES : SC2_F32_WAVES1
     const uint32_t ring = lds_base + p.ring_off;
     constexpr uint32_t GROUP_BYTES = 4u * NT * 1024u;
     const uint32_t w_chunk = (uint32_t)chunk * (uint32_t)p.n_steps * (NT * 1024u) + (uint32_t)lane * 16u;
-    const int n = p.n_steps, n_groups = (n + 3) >> 2;
+    const int n = p.n_steps;
     auto fetch_group = [&](int g) {          // this wave's step of group g (past the end: out of range = zeros, never consumed)
         const int st = g * 4 + wave;
         const uint32_t src = st < n ? w_chunk + (uint32_t)st * (NT * 1024u) : 0x80000000u;
@@ -332,7 +268,6 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 ? SC2_F32_WAVES : SC2_F32_WAVES1
     // no LDS, no HBM round trip of the f32 map (1.2 GB each way for conv0 at bs 256).  Same k order as the separate GDN launch:
     // bit-identical to it.
     f4_t nrm[FUSED ? MT : 1][FUSED ? NT : 1];     // (a compile-time property: as a runtime case it cost every launch 110 registers)
-    constexpr bool fused_gdn = FUSED;
     if (FUSED) {
         const f4_t *gf = reinterpret_cast<const f4_t *>(p.ep_x) + lane;
 #pragma unroll
@@ -354,79 +289,7 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 ? SC2_F32_WAVES : SC2_F32_WAVES1
         }
     }
 
-    // epilogue.  The WEIGHTS are the first MFMA operand, so the result tile is [channel][pixel]: acc[mt][nt][i] = output
-    // (pixel m_base + mt * 16 + r, channel (chunk * NT + nt) * 16 + 4 q + i) -- a lane holds FOUR CONSECUTIVE CHANNELS of one
-    // pixel: one 16-byte access per tile for NHWC tensors (ep_x, y), and for NCHW outputs the 16 lanes of a quarter write 16
-    // consecutive pixels of a channel plane.
-    const long long ohw = (long long)p.OH * p.OW;
-    const bool vec4 = (p.Cout & 3) == 0;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        const long long m = m_base + mt * 16 + r;
-        if (m >= p.M) continue;
-        const long long n_img = (uint32_t)m / (uint32_t)ohw;
-        const long long pix = m - n_img * ohw;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int c0 = (chunk * NT + nt) * 16 + 4 * q;
-            if (c0 >= p.Cout) continue;
-            float v[4] = {acc[mt][nt][0], acc[mt][nt][1], acc[mt][nt][2], acc[mt][nt][3]};
-            float bc[4] = {0.f, 0.f, 0.f, 0.f};
-            if (p.ep_beta) {
-                if (vec4) {
-                    const f4_t b = *reinterpret_cast<const f4_t *>(p.ep_beta + c0);
-                    bc[0] = b.x; bc[1] = b.y; bc[2] = b.z; bc[3] = b.w;
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) bc[i] = c0 + i < p.Cout ? p.ep_beta[c0 + i] : 0.f;
-                }
-            }
-            if (fused_gdn) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float norm = nrm[FUSED ? mt : 0][FUSED ? nt : 0][i] + bc[i];
-                    if (p.epilogue == SC2_EPI_FUSED_GDN) norm = 1.0f / norm;
-                    v[i] = v[i] * norm;
-                }
-            } else if (p.epilogue == SC2_EPI_GDN || p.epilogue == SC2_EPI_IGDN) {
-                float xv[4];
-                if (vec4) {
-                    const f4_t t = *reinterpret_cast<const f4_t *>(p.ep_x + m * p.Cout + c0);
-                    xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) xv[i] = c0 + i < p.Cout ? p.ep_x[m * p.Cout + c0 + i] : 0.f;
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float norm = v[i] + bc[i];                 // conv2d(|x|, gamma, beta): the bias joins the finished sum
-                    if (p.epilogue == SC2_EPI_GDN) norm = 1.0f / norm;   // IEEE division, then one multiply, as GDN1.forward
-                    v[i] = xv[i] * norm;
-                }
-            } else if (p.epilogue == SC2_EPI_BIAS) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] += bc[i];
-            }
-            if (p.out_format == SC2_OUT_F32_NHWC) {
-                float *dst = static_cast<float *>(p.y) + m * p.Cout + c0;
-                if (vec4) {
-                    *reinterpret_cast<f4_t *>(dst) = f4_t{v[0], v[1], v[2], v[3]};
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (c0 + i < p.Cout) dst[i] = v[i];
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (c0 + i >= p.Cout) continue;
-                    const long long o = (n_img * p.Cout + c0 + i) * ohw + pix;
-                    if (p.out_format == SC2_OUT_F32_NCHW) static_cast<float *>(p.y)[o] = v[i];
-                    else static_cast<int32_t *>(p.y)[o] = (int32_t)rintf(v[i] - bc[i]);   // symbols: bc = the channel's median
-                }
-            }
-        }
-    }
+    precise_epilogue<MT, NT, FUSED>(p, acc, nrm, m_base, chunk, r, q);
 }
 
 // The first encoder stage of the reference-precision path as a PERSISTENT kernel: Conv2d(3 -> 96, k5, s2, p2) on the RGB planes +
@@ -588,7 +451,7 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_f32_kernel(const float *__re
 
 }  // namespace
 
-extern "C" int sc2_conv_f32_chunk_channels(int Cout) { return Cout <= 32 ? 32 : (Cout <= 48 ? 48 : 96); }
+extern "C" int sc2_conv_f32_chunk_channels(int Cout) { return precise_chunk_channels(Cout); }
 
 extern "C" int sc2_nchw_f32_to_nhwc_f32(const float *x, float *y, int N, int C, int H, int W, int Cpad, void *stream) {
     SC2_REQUIRE(x && y, SC2_ERR_INVALID_ARG, "nchw_to_nhwc_f32: null argument");
@@ -605,37 +468,11 @@ extern "C" int sc2_nchw_f32_to_nhwc_f32(const float *x, float *y, int N, int C, 
 extern "C" int sc2_conv2d_f32_fwd(const sc2_conv_desc *d, const float *x, const float *w_frag, void *y, const float *ep_x,
                                   const float *ep_beta, void *stream) {
     SC2_REQUIRE(d && x && w_frag && y, SC2_ERR_INVALID_ARG, "conv2d_f32: null argument");
-    SC2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cin % 4 == 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0,
-                SC2_ERR_INVALID_ARG, "conv2d_f32: bad dims (Cin must be a multiple of 4)");
-    SC2_REQUIRE(d->stride_h == d->stride_w && d->pad_h == d->pad_w && d->stride_h > 0 && d->pad_h >= 0, SC2_ERR_UNSUPPORTED,
-                "conv2d_f32: square stride / padding only");
-    SC2_REQUIRE(d->OH == (d->H + 2 * d->pad_h - d->KH) / d->stride_h + 1 && d->OW == (d->W + 2 * d->pad_w - d->KW) / d->stride_w + 1,
-                SC2_ERR_INVALID_ARG, "conv2d_f32: OH / OW do not match the geometry");
-    SC2_REQUIRE(d->out_H == 0, SC2_ERR_UNSUPPORTED, "conv2d_f32: no output scatter");
-    SC2_REQUIRE(d->a_op == SC2_AOP_NONE || d->a_op == SC2_AOP_ABS || d->a_op == SC2_AOP_SQUARE, SC2_ERR_INVALID_ARG, "conv2d_f32: a_op");
+    if (const int rc = precise_check_desc("conv2d_f32", d, ep_x, ep_x, ep_beta)) return rc;   // (gamma travels in ep_x)
     const bool fused = d->epilogue == SC2_EPI_FUSED_GDN || d->epilogue == SC2_EPI_FUSED_IGDN;
-    SC2_REQUIRE(d->epilogue == SC2_EPI_NONE || d->epilogue == SC2_EPI_GDN || d->epilogue == SC2_EPI_IGDN || d->epilogue == SC2_EPI_BIAS || fused,
-                SC2_ERR_UNSUPPORTED, "conv2d_f32: epilogue %d", d->epilogue);
-    SC2_REQUIRE(!fused || (d->Cout <= 96 && ep_x && ep_beta), SC2_ERR_UNSUPPORTED,
-                "conv2d_f32: the fused GDN needs every channel of a pixel in one chunk (Cout <= 96), gamma fragments and beta");
-    // the fused norm GEMM walks chunk / 16 k-steps of gamma fragments; gamma is packed with ceil(Cout / 16) of them (a 1x1 weight
-    // of K = Cout): a narrower Cout (49 .. 80, or <= 16) would read up to 12 KB past the tensor
-    SC2_REQUIRE(!fused || (d->Cout + 15) / 16 * 16 == sc2_conv_f32_chunk_channels(d->Cout), SC2_ERR_UNSUPPORTED,
-                "conv2d_f32: the fused GDN needs ceil(Cout / 16) * 16 == the chunk width (%d channels: chunk %d); run conv and GDN1 as two launches",
-                d->Cout, sc2_conv_f32_chunk_channels(d->Cout));
-    SC2_REQUIRE(d->out_format == SC2_OUT_F32_NHWC || d->out_format == SC2_OUT_F32_NCHW || d->out_format == SC2_OUT_I32_NCHW_SYM,
-                SC2_ERR_UNSUPPORTED, "conv2d_f32: out_format %d", d->out_format);
-    const bool gdn = d->epilogue == SC2_EPI_GDN || d->epilogue == SC2_EPI_IGDN;
-    SC2_REQUIRE(!gdn || (ep_x && ep_beta), SC2_ERR_INVALID_ARG, "conv2d_f32: GDN epilogue needs ep_x and ep_beta");
-    SC2_REQUIRE((d->epilogue != SC2_EPI_BIAS && d->out_format != SC2_OUT_I32_NCHW_SYM) || ep_beta, SC2_ERR_INVALID_ARG,
-                "conv2d_f32: ep_beta (bias / medians) missing");
-    SC2_REQUIRE(d->out_format != SC2_OUT_I32_NCHW_SYM || d->epilogue == SC2_EPI_NONE, SC2_ERR_INVALID_ARG,
-                "conv2d_f32: symbols come straight from the accumulators (epilogue NONE)");
     F32Args a;
-    a.x = x; a.w = w_frag; a.ep_x = ep_x; a.ep_beta = ep_beta; a.y = y;
-    a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW;
-    a.stride = d->stride_h; a.pad = d->pad_h; a.OH = d->OH; a.OW = d->OW;
-    a.a_op = d->a_op; a.epilogue = d->epilogue; a.out_format = d->out_format;
+    precise_fill_args(a, d, x, ep_x, ep_beta, y);
+    a.w = w_frag;
     a.n_steps = (d->KH * d->KW * d->Cin + 15) / 16;
     // Kpad (the bf16 kernels' weight pitch) carries the REAL channel count here: 3 of Cin == 4 means the fourth channel of x and the
     // weights of k % 4 == 3 are zero (hip.nchw_f32_to_nhwc_f32 / hip.pack_conv_f32 make them so) and their products are skipped
@@ -643,14 +480,13 @@ extern "C" int sc2_conv2d_f32_fwd(const sc2_conv_desc *d, const float *x, const 
     // k_order (ignored otherwise) = 1 with it: x is the f32 NCHW image [N, 3, H, W] itself, the three planes read in place
     a.planar = d->k_order == 1 ? 1 : 0;
     SC2_REQUIRE(!a.planar || a.skip_j3, SC2_ERR_UNSUPPORTED, "conv2d_f32: the NCHW input form needs Cin == 4 with Kpad == 3 and a_op NONE");
-    a.M = (long long)d->N * d->OH * d->OW;
     {
         const long long xb = (long long)d->N * d->H * d->W * (d->k_order == 1 ? 3 : d->Cin) * 4;
         SC2_REQUIRE(xb < 0x7FF00000LL, SC2_ERR_UNSUPPORTED, "conv2d_f32: input of %lld bytes exceeds 2 GB", xb);
         a.x_bytes = (unsigned)xb;
         a.y_bytes = 0u;
     }
-    SC2_REQUIRE((long long)d->N * d->H * d->W * d->Cin < (1ll << 31) && a.M * d->Cout < (1ll << 33), SC2_ERR_UNSUPPORTED,
+    SC2_REQUIRE((long long)d->N * d->H * d->W * d->Cin < (1ll << 31) && a.M < (1ll << 31) && a.M * d->Cout < (1ll << 33), SC2_ERR_UNSUPPORTED,
                 "conv2d_f32: tensor too large for this kernel's index arithmetic");
     SC2_REQUIRE((size_t)a.n_steps * 32 <= 64 * 1024, SC2_ERR_UNSUPPORTED, "conv2d_f32: K too long for the tap table");
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -658,38 +494,30 @@ extern "C" int sc2_conv2d_f32_fwd(const sc2_conv_desc *d, const float *x, const 
     const int chunks = (d->Cout + cc - 1) / cc;
     // (measured: four row tiles per wave for the narrow chunks -- twice the MFMAs per operand load -- ran the 96 -> 48 k5 s2 conv
     //  in 2.89 ms instead of 2.38 at bs 256: fewer, fatter waves hide less of the operand latency; two row tiles everywhere)
-    constexpr int MT48 = SC2_F32_MT4 ? 4 : 2;
     if (fused && a.planar && d->Cout == 96 && d->KH == 5 && d->KW == 5 && d->stride_h == 2 && d->pad_h == 2 && d->out_format == SC2_OUT_F32_NHWC &&
         f32_persist0_enabled() && a.M * 96LL * 4LL < 0xFFFFFF00LL) {
         a.y_bytes = (unsigned)(a.M * 96LL * 4LL);
-        static int n_cu_dev[SC2_MAX_DEVICES] = {};     // per device, as the function attributes below
-        int &n_cu = n_cu_dev[sc2_device_slot()];
-        if (n_cu == 0) {
-            int dev = 0, v = 0;
-            n_cu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-        }
         const size_t lds = (size_t)(P0_W_FRAGS + P0_G_FRAGS + 24) * 16;
         const long long tiles = (a.M + 31) / 32;
-        int grid = n_cu * 2;
+        int grid = sc2_device_cus() * 2;
         if ((long long)grid * 4 > tiles) grid = (int)((tiles + 3) / 4);
-        static bool attr_set_dev[SC2_MAX_DEVICES] = {};
-        bool &attr_set = attr_set_dev[sc2_device_slot()];
-        if (!attr_set) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv0_gdn_f32_persist_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv0_gdn_f32_persist_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            attr_set = true;
+        // (80 KB of LDS; should the limit not be granted, the launch below reports it)
+        if (d->epilogue == SC2_EPI_FUSED_IGDN) {
+            (void)precise_raise_lds_limit<&conv0_gdn_f32_persist_kernel<true>>(lds);
+            hipLaunchKernelGGL(conv0_gdn_f32_persist_kernel<true>, dim3(grid), dim3(256), lds, s, a);
+        } else {
+            (void)precise_raise_lds_limit<&conv0_gdn_f32_persist_kernel<false>>(lds);
+            hipLaunchKernelGGL(conv0_gdn_f32_persist_kernel<false>, dim3(grid), dim3(256), lds, s, a);
         }
-        if (d->epilogue == SC2_EPI_FUSED_IGDN) hipLaunchKernelGGL(conv0_gdn_f32_persist_kernel<true>, dim3(grid), dim3(256), lds, s, a);
-        else hipLaunchKernelGGL(conv0_gdn_f32_persist_kernel<false>, dim3(grid), dim3(256), lds, s, a);
         SC2_CHECK_LAUNCH();
         return SC2_OK;
     }
     if (fused) {
         if (cc == 32) return launch_f32<2, 2, true>(a, chunks, s);
-        if (cc == 48) return launch_f32<3, MT48, true>(a, chunks, s);
+        if (cc == 48) return launch_f32<3, 2, true>(a, chunks, s);
         return launch_f32<6, 2, true>(a, chunks, s);
     }
     if (cc == 32) return launch_f32<2, 2>(a, chunks, s);
-    if (cc == 48) return launch_f32<3, MT48>(a, chunks, s);
+    if (cc == 48) return launch_f32<3, 2>(a, chunks, s);
     return launch_f32<6, 2>(a, chunks, s);
 }

@@ -16,29 +16,19 @@
 //   * a wave owns MT x 16 pixels x NT x 16 channels (one channel chunk); the four waves of a workgroup share the chunk's weight
 //     stream through a two-deep LDS ring of G-step groups, one barrier per group; activations are per-wave loads through a
 //     bounded buffer descriptor four steps ahead (a tap outside the image, a row past M: an out-of-range offset, zeros).
-//   * epilogues and outputs as conv_f32.hip, in its operation order.
+//   * epilogues and outputs: conv_precise.h, the one copy conv_f32.hip runs too.
 #include <stdlib.h>
 
-#include "sc2_common.h"
+#include "conv_precise.h"
 
 namespace {
 
-struct SplitArgs {
-    const float *__restrict__ x;        // f32 NHWC [N, H, W, Cin] (Cin % 4 == 0)
+struct SplitArgs : PreciseArgs {        // (n_steps = ceil(K / 32))
     const void *__restrict__ w;         // bf16 [chunks][steps][NS][NT][64 lanes][8]
-    const float *__restrict__ ep_x;     // f32 NHWC [N, OH, OW, Cout] (GDN operand) or null
     const void *__restrict__ gamma;     // fused GDN: gamma packed as a 1x1 weight (one chunk), else null
-    const float *__restrict__ ep_beta;  // f32 [Cout]: beta / bias / medians or null
-    void *__restrict__ y;
-    int N, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW;
-    int a_op, epilogue, out_format;
-    int n_steps;                        // ceil(K / 32)
-    long long M;                        // N * OH * OW
-    unsigned x_bytes, w_bytes;
-    unsigned ring_off;                  // LDS offset of the weight ring (after the tap table)
 };
 
-typedef __attribute__((ext_vector_type(4))) float sf4_t;
+typedef f32x4_t sf4_t;
 typedef __attribute__((ext_vector_type(4))) unsigned su4_t;
 
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -94,42 +84,13 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(const SplitArgs p) {
     const int n = p.n_steps;
     // (the table runs D steps past the last whole block of steps: those entries are K padding, so the loads that the k loop issues
     //  past the end -- it issues the same loads on every path, which keeps the counted waits exact -- return zeros)
-    for (int e = tid; e < ((n + D - 1) / D * D + D) * 8; e += 256) {
-        const int k0 = e * 4;
-        const int tap = k0 / p.Cin, ci = k0 - tap * p.Cin;
-        int2 v;
-        if (tap < p.KH * p.KW) {
-            const int kh = tap / p.KW, kw = tap - kh * p.KW;
-            v.x = ((kh * p.W + kw) * p.Cin + ci) * 4;    // byte offset inside the window
-            v.y = kh | (kw << 16);
-        } else {                                         // K padding: never in bounds (its weights are zero too)
-            v.x = 0;
-            v.y = 0x7FFF | (0x7FFF << 16);
-        }
-        ktab[e] = v;
-    }
+    for (int e = tid; e < ((n + D - 1) / D * D + D) * 8; e += 256) ktab[e] = precise_tap_entry(p, e, p.Cin);
 
     const long long m_base = ((long long)blockIdx.x * 4 + wave) * (MT * 16);
     const int chunk = blockIdx.y;
-    // byte offsets modulo 2^32: a window that starts above / left of the image has a negative base, but base + offset of every
-    // tap INSIDE the image is a plain offset below x_bytes < 2^31
     uint32_t a_base[MT];
     int ih0[MT], iw0[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        const long long m = m_base + mt * 16 + r;
-        if (m < p.M) {                                   // (M < 2^31, checked by the host)
-            const uint32_t ohw_u = (uint32_t)(p.OH * p.OW), ni = (uint32_t)m / ohw_u;
-            const int rem = (int)((uint32_t)m - ni * ohw_u);
-            const int oh = (int)((uint32_t)rem / (uint32_t)p.OW), ow = rem - oh * p.OW;
-            ih0[mt] = oh * p.stride - p.pad;
-            iw0[mt] = ow * p.stride - p.pad;
-            a_base[mt] = (uint32_t)(((((long long)ni * p.H + ih0[mt]) * (long long)p.W + iw0[mt]) * p.Cin) * 4);
-        } else {
-            ih0[mt] = iw0[mt] = -(1 << 20);              // every tap out of bounds: zeros
-            a_base[mt] = 0;
-        }
-    }
+    precise_rows<MT>(p, m_base, r, p.H, p.Cin, a_base, ih0, iw0);
 
     sf4_t acc[MT][NT];
 #pragma unroll
@@ -299,77 +260,7 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(const SplitArgs p) {
         }
     }
 
-    // epilogue.  The weights are the first MFMA operand, so acc[mt][nt][i] = output (pixel m_base + mt * 16 + r, channel
-    // (chunk * NT + nt) * 16 + 4 q + i): a lane holds four consecutive channels of one pixel.
-    const long long ohw = (long long)p.OH * p.OW;
-    const bool vec4 = (p.Cout & 3) == 0;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        const long long m = m_base + mt * 16 + r;
-        if (m >= p.M) continue;
-        const long long n_img = (uint32_t)m / (uint32_t)ohw;
-        const long long pix = m - n_img * ohw;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            const int c0 = (chunk * NT + nt) * 16 + 4 * q;
-            if (c0 >= p.Cout) continue;
-            float v[4] = {acc[mt][nt][0], acc[mt][nt][1], acc[mt][nt][2], acc[mt][nt][3]};
-            float bc[4] = {0.f, 0.f, 0.f, 0.f};
-            if (p.ep_beta) {
-                if (vec4) {
-                    const sf4_t b = *reinterpret_cast<const sf4_t *>(p.ep_beta + c0);
-                    bc[0] = b.x; bc[1] = b.y; bc[2] = b.z; bc[3] = b.w;
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) bc[i] = c0 + i < p.Cout ? p.ep_beta[c0 + i] : 0.f;
-                }
-            }
-            if constexpr (FUSED) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float norm = nrm[FUSED ? mt : 0][FUSED ? nt : 0][i] + bc[i];
-                    if (p.epilogue == SC2_EPI_FUSED_GDN) norm = 1.0f / norm;
-                    v[i] = v[i] * norm;
-                }
-            } else if (p.epilogue == SC2_EPI_GDN || p.epilogue == SC2_EPI_IGDN) {
-                float xv[4];
-                if (vec4) {
-                    const sf4_t t = *reinterpret_cast<const sf4_t *>(p.ep_x + m * p.Cout + c0);
-                    xv[0] = t.x; xv[1] = t.y; xv[2] = t.z; xv[3] = t.w;
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) xv[i] = c0 + i < p.Cout ? p.ep_x[m * p.Cout + c0 + i] : 0.f;
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float norm = v[i] + bc[i];                 // conv2d(|x|, gamma, beta): the bias joins the finished sum
-                    if (p.epilogue == SC2_EPI_GDN) norm = 1.0f / norm;   // IEEE division, then one multiply, as GDN1.forward
-                    v[i] = xv[i] * norm;
-                }
-            } else if (p.epilogue == SC2_EPI_BIAS) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) v[i] += bc[i];
-            }
-            if (p.out_format == SC2_OUT_F32_NHWC) {
-                float *dst = static_cast<float *>(p.y) + m * p.Cout + c0;
-                if (vec4) {
-                    *reinterpret_cast<sf4_t *>(dst) = sf4_t{v[0], v[1], v[2], v[3]};
-                } else {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (c0 + i < p.Cout) dst[i] = v[i];
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (c0 + i >= p.Cout) continue;
-                    const long long o = (n_img * p.Cout + c0 + i) * ohw + pix;
-                    if (p.out_format == SC2_OUT_F32_NCHW) static_cast<float *>(p.y)[o] = v[i];
-                    else static_cast<int32_t *>(p.y)[o] = (int32_t)rintf(v[i] - bc[i]);   // symbols: bc = the channel's median
-                }
-            }
-        }
-    }
+    precise_epilogue<MT, NT, FUSED>(p, acc, nrm, m_base, chunk, r, q);
 }
 
 template <int NS, int NT, int MT, bool FUSED, int AOP>
@@ -380,19 +271,9 @@ int launch_split(const SplitArgs &a, int chunks, hipStream_t s) {
     b.ring_off = (unsigned)(((size_t)((a.n_steps + 3) / 4 * 4 + 4) * 8 * sizeof(int2) + 1023) / 1024 * 1024);   // (D = 4 in the kernel)
     b.w_bytes = (unsigned)((size_t)chunks * a.n_steps * NS * NT * 1024);
     const size_t lds = (size_t)b.ring_off + 2 * (size_t)G * NS * NT * 1024;
-    auto kern = conv_split_kernel<NS, NT, MT, FUSED, AOP>;
-    if (lds > 64 * 1024) {      // a per-device property of the function
-        static size_t set_dev[SC2_MAX_DEVICES] = {};
-        size_t &have = set_dev[sc2_device_slot()];
-        if (have < lds) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-                (void)hipGetLastError();
-                sc2_set_error("conv2d_split: %zu bytes of LDS are not available", lds);
-                return SC2_ERR_UNSUPPORTED;
-            }
-            have = lds;
-        }
-    }
+    constexpr auto kern = &conv_split_kernel<NS, NT, MT, FUSED, AOP>;
+    SC2_REQUIRE(lds <= 64 * 1024 || precise_raise_lds_limit<kern>(lds), SC2_ERR_UNSUPPORTED,
+                "conv2d_split: %zu bytes of LDS are not available", lds);
     hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)chunks), dim3(256), lds, s, b);
     SC2_CHECK_LAUNCH();
     return SC2_OK;
@@ -415,48 +296,22 @@ int dispatch_split(const SplitArgs &a, int cc, int chunks, bool fused, hipStream
 
 }  // namespace
 
-extern "C" int sc2_conv_split_chunk_channels(int Cout) { return Cout <= 32 ? 32 : (Cout <= 48 ? 48 : 96); }
+extern "C" int sc2_conv_split_chunk_channels(int Cout) { return precise_chunk_channels(Cout); }
 
 extern "C" int sc2_conv2d_split_fwd(const sc2_conv_desc *d, int n_parts, const float *x, const void *w_frag, void *y, const float *ep_x,
                                     const void *gamma_frag, const float *ep_beta, void *stream) {
     SC2_REQUIRE(d && x && w_frag && y, SC2_ERR_INVALID_ARG, "conv2d_split: null argument");
     SC2_REQUIRE(n_parts == 2 || n_parts == 3, SC2_ERR_UNSUPPORTED, "conv2d_split: n_parts %d (2 or 3)", n_parts);
-    SC2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cin % 4 == 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0,
-                SC2_ERR_INVALID_ARG, "conv2d_split: bad dims (Cin must be a multiple of 4)");
-    SC2_REQUIRE(d->stride_h == d->stride_w && d->pad_h == d->pad_w && d->stride_h > 0 && d->pad_h >= 0, SC2_ERR_UNSUPPORTED,
-                "conv2d_split: square stride / padding only");
-    SC2_REQUIRE(d->OH == (d->H + 2 * d->pad_h - d->KH) / d->stride_h + 1 && d->OW == (d->W + 2 * d->pad_w - d->KW) / d->stride_w + 1 &&
-                    d->OH > 0 && d->OW > 0,
-                SC2_ERR_INVALID_ARG, "conv2d_split: OH / OW do not match the geometry");
-    SC2_REQUIRE(d->out_H == 0, SC2_ERR_UNSUPPORTED, "conv2d_split: no output scatter");
+    if (const int rc = precise_check_desc("conv2d_split", d, ep_x, gamma_frag, ep_beta)) return rc;
     SC2_REQUIRE(d->k_order == 0, SC2_ERR_UNSUPPORTED, "conv2d_split: f32 NHWC input only");
-    SC2_REQUIRE(d->a_op == SC2_AOP_NONE || d->a_op == SC2_AOP_ABS || d->a_op == SC2_AOP_SQUARE, SC2_ERR_INVALID_ARG, "conv2d_split: a_op");
     const bool fused = d->epilogue == SC2_EPI_FUSED_GDN || d->epilogue == SC2_EPI_FUSED_IGDN;
-    SC2_REQUIRE(d->epilogue == SC2_EPI_NONE || d->epilogue == SC2_EPI_GDN || d->epilogue == SC2_EPI_IGDN || d->epilogue == SC2_EPI_BIAS || fused,
-                SC2_ERR_UNSUPPORTED, "conv2d_split: epilogue %d", d->epilogue);
-    const int cc = sc2_conv_split_chunk_channels(d->Cout);
-    SC2_REQUIRE(!fused || d->a_op == SC2_AOP_NONE, SC2_ERR_UNSUPPORTED, "conv2d_split: the fused GDN takes a_op NONE");
-    SC2_REQUIRE(!fused || (d->Cout <= 96 && gamma_frag && ep_beta), SC2_ERR_UNSUPPORTED,
-                "conv2d_split: the fused GDN needs every channel of a pixel in one chunk (Cout <= 96), gamma fragments and beta");
-    // the fused norm GEMM walks ceil(chunk / 32) k-steps of chunk-wide gamma fragments; gamma is packed as a 1x1 weight of K = Cout
-    SC2_REQUIRE(!fused || (d->Cout + 15) / 16 * 16 == cc, SC2_ERR_UNSUPPORTED,
-                "conv2d_split: the fused GDN needs ceil(Cout / 16) * 16 == the chunk width (%d channels: chunk %d); run conv and GDN1 as two launches",
-                d->Cout, cc);
-    SC2_REQUIRE(d->out_format == SC2_OUT_F32_NHWC || d->out_format == SC2_OUT_F32_NCHW || d->out_format == SC2_OUT_I32_NCHW_SYM,
-                SC2_ERR_UNSUPPORTED, "conv2d_split: out_format %d", d->out_format);
     const bool gdn = d->epilogue == SC2_EPI_GDN || d->epilogue == SC2_EPI_IGDN;
-    SC2_REQUIRE(!gdn || (ep_x && ep_beta), SC2_ERR_INVALID_ARG, "conv2d_split: GDN epilogue needs ep_x and ep_beta");
-    SC2_REQUIRE((d->epilogue != SC2_EPI_BIAS && d->out_format != SC2_OUT_I32_NCHW_SYM) || ep_beta, SC2_ERR_INVALID_ARG,
-                "conv2d_split: ep_beta (bias / medians) missing");
-    SC2_REQUIRE(d->out_format != SC2_OUT_I32_NCHW_SYM || d->epilogue == SC2_EPI_NONE, SC2_ERR_INVALID_ARG,
-                "conv2d_split: symbols come straight from the accumulators (epilogue NONE)");
+    SC2_REQUIRE(!fused || d->a_op == SC2_AOP_NONE, SC2_ERR_UNSUPPORTED, "conv2d_split: the fused GDN takes a_op NONE");
+    const int cc = sc2_conv_split_chunk_channels(d->Cout);
     SplitArgs a;
-    a.x = x; a.w = w_frag; a.ep_x = gdn ? ep_x : nullptr; a.gamma = fused ? gamma_frag : nullptr; a.ep_beta = ep_beta; a.y = y;
-    a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW;
-    a.stride = d->stride_h; a.pad = d->pad_h; a.OH = d->OH; a.OW = d->OW;
-    a.a_op = d->a_op; a.epilogue = d->epilogue; a.out_format = d->out_format;
+    precise_fill_args(a, d, x, gdn ? ep_x : nullptr, ep_beta, y);
+    a.w = w_frag; a.gamma = fused ? gamma_frag : nullptr;
     a.n_steps = (d->KH * d->KW * d->Cin + 31) / 32;
-    a.M = (long long)d->N * d->OH * d->OW;
     const long long xb = (long long)d->N * d->H * d->W * d->Cin * 4;
     SC2_REQUIRE(xb < 0x7FF00000LL, SC2_ERR_UNSUPPORTED, "conv2d_split: input of %lld bytes exceeds 2 GB", xb);
     a.x_bytes = (unsigned)xb;

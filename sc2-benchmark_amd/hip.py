@@ -1559,29 +1559,72 @@ def nchw_f32_to_nhwc_f32(x, cpad=None):
     return y
 
 
+def _precise_fused_gdn_supported(cout, chunk_channels):
+    cout = int(cout)
+    return cout <= 96 and (cout + 15) // 16 * 16 == int(chunk_channels(cout))
+
+
 def conv_f32_fused_gdn_supported(cout):
     """conv + GDN1 in one f32 launch needs every channel of a pixel in one wave (Cout <= 96) AND a gamma stream as long as the
     chunk is wide: ceil(Cout / 16) * 16 == chunk width (96 / 48 / 32 / 20 ... yes; 64 or 16 no: two launches)."""
-    cout = int(cout)
-    return cout <= 96 and (cout + 15) // 16 * 16 == int(lib().sc2_conv_f32_chunk_channels(cout))
+    return _precise_fused_gdn_supported(cout, lib().sc2_conv_f32_chunk_channels)
+
+
+def _precise_weight_matrix(weight, cin_pad, chunk_channels, step_k):
+    """Conv weight [Cout, Cin, KH, KW] -> (f32 [chunks * cc, steps * step_k] with k = (kh*KW + kw)*cin_pad + ci, zeros beyond Cout,
+    Cin and K; chunks; NT = cc / 16; steps): the matrix whose elements pack_conv_f32 / pack_conv_split put into fragment order."""
+    w = weight.detach().float()
+    Cout, Cin, KH, KW = w.shape
+    cin_pad = (Cin + 3) // 4 * 4 if cin_pad is None else cin_pad
+    cc = int(chunk_channels(Cout))
+    chunks = (Cout + cc - 1) // cc
+    K = KH * KW * cin_pad
+    steps = (K + step_k - 1) // step_k
+    m = torch.zeros((chunks * cc, KH, KW, cin_pad), dtype=torch.float32, device=w.device)
+    m[:Cout, :, :, :Cin] = w.permute(0, 2, 3, 1)
+    return torch.nn.functional.pad(m.reshape(chunks * cc, K), (0, steps * step_k - K)), chunks, cc // 16, steps
 
 
 def pack_conv_f32(weight, cin_pad=None):
     """Conv weight [Cout, Cin, KH, KW] (any float dtype) -> the f32 fragment-major stream of sc2_conv2d_f32_fwd:
     [chunks][steps][NT][64 lanes][4], entry (ch, s, nt, lane = q*16 + r, j) = W[ch*cc + nt*16 + r][16 s + 4 q + j] with
     k = (kh*KW + kw)*cin_pad + ci."""
-    w = weight.detach().float()
-    Cout, Cin, KH, KW = w.shape
-    cin_pad = (Cin + 3) // 4 * 4 if cin_pad is None else cin_pad
-    cc = int(lib().sc2_conv_f32_chunk_channels(Cout))
-    chunks, NT = (Cout + cc - 1) // cc, cc // 16
-    K = KH * KW * cin_pad
-    steps = (K + 15) // 16
-    m = torch.zeros((chunks * cc, KH, KW, cin_pad), dtype=torch.float32, device=w.device)
-    m[:Cout, :, :, :Cin] = w.permute(0, 2, 3, 1)
-    m = torch.nn.functional.pad(m.reshape(chunks * cc, K), (0, steps * 16 - K))
+    m, chunks, NT, steps = _precise_weight_matrix(weight, cin_pad, lib().sc2_conv_f32_chunk_channels, 16)
     m = m.reshape(chunks, NT, 16, steps, 4, 4)            # [ch, nt, r, s, q, j]
     return m.permute(0, 3, 1, 4, 2, 5).contiguous()       # [ch, s, nt, q, r, j]
+
+
+def _precise_conv_setup(x_shape, device, cout, kh, kw, stride, padding, a_op, epilogue, out_format, ep_x, ep_beta, out, kpad=0, k_order=0):
+    """What conv2d_f32_fwd and conv2d_split_fwd share: x_shape (N, H, W, Cin) -> (the ConvDesc, the output tensor per out_format; a
+    symbol buffer passed as `out` is used in place).  ep_x: the GDN operand [N,OH,OW,Cout] (with a fused epilogue: the f32 kernel's
+    gamma fragments); ep_beta: [>= Cout]; both f32, dense."""
+    N, H, W, Cin = x_shape
+    sh = stride[0] if isinstance(stride, (tuple, list)) else stride
+    ph = padding[0] if isinstance(padding, (tuple, list)) else padding
+    OH, OW = (H + 2 * ph - kh) // sh + 1, (W + 2 * ph - kw) // sh + 1
+    d = ConvDesc(N=N, H=H, W=W, Cin=Cin, Cout=cout, KH=kh, KW=kw, stride_h=sh, stride_w=sh, pad_h=ph, pad_w=ph, OH=OH, OW=OW,
+                 a_op=a_op, epilogue=epilogue, out_format=out_format, Kpad=kpad, Cout_pad=0, out_H=0, out_W=0, out_stride_h=0,
+                 out_stride_w=0, out_off_h=0, out_off_w=0, k_order=k_order)
+    if out_format == OUT_F32_NHWC:
+        y = torch.empty((N, OH, OW, cout), dtype=torch.float32, device=device)
+    elif out_format == OUT_F32_NCHW:
+        y = torch.empty((N, cout, OH, OW), dtype=torch.float32, device=device)
+    else:
+        assert out_format == OUT_I32_NCHW_SYM
+        if out is not None:
+            assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == N * cout * OH * OW
+            y = out.view(N, cout, OH, OW)
+        else:
+            y = torch.empty((N, cout, OH, OW), dtype=torch.int32, device=device)
+    for t in (ep_x, ep_beta):
+        if t is not None:
+            _dev(t, 'epilogue operand')
+            assert t.dtype == torch.float32 and t.is_contiguous()
+    if ep_x is not None and epilogue not in (EPI_FUSED_GDN, EPI_FUSED_IGDN):
+        assert ep_x.numel() == N * OH * OW * cout
+    if ep_beta is not None:
+        assert ep_beta.numel() >= cout
+    return d, y
 
 
 def conv2d_f32_fwd(x_nhwc, w_frag, cout, kh, kw, stride, padding, a_op=AOP_NONE, epilogue=EPI_NONE, out_format=None,
@@ -1600,27 +1643,8 @@ def conv2d_f32_fwd(x_nhwc, w_frag, cout, kh, kw, stride, padding, a_op=AOP_NONE,
         Cin, cin_real = 4, 3
     else:
         N, H, W, Cin = x_nhwc.shape
-    sh = stride[0] if isinstance(stride, (tuple, list)) else stride
-    ph = padding[0] if isinstance(padding, (tuple, list)) else padding
-    OH, OW = (H + 2 * ph - kh) // sh + 1, (W + 2 * ph - kw) // sh + 1
-    d = ConvDesc(N=N, H=H, W=W, Cin=Cin, Cout=cout, KH=kh, KW=kw, stride_h=sh, stride_w=sh, pad_h=ph, pad_w=ph, OH=OH, OW=OW,
-                 a_op=a_op, epilogue=epilogue, out_format=out_format, Kpad=int(cin_real or 0), Cout_pad=0, out_H=0, out_W=0, out_stride_h=0,
-                 out_stride_w=0, out_off_h=0, out_off_w=0, k_order=1 if x_is_nchw_rgb else 0)
-    if out_format == OUT_F32_NHWC:
-        y = torch.empty((N, OH, OW, cout), dtype=torch.float32, device=x_nhwc.device)
-    elif out_format == OUT_F32_NCHW:
-        y = torch.empty((N, cout, OH, OW), dtype=torch.float32, device=x_nhwc.device)
-    else:
-        assert out_format == OUT_I32_NCHW_SYM
-        if out is not None:
-            assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == N * cout * OH * OW
-            y = out.view(N, cout, OH, OW)
-        else:
-            y = torch.empty((N, cout, OH, OW), dtype=torch.int32, device=x_nhwc.device)
-    for t in (ep_x, ep_beta):
-        if t is not None:
-            _dev(t, 'epilogue operand')
-            assert t.dtype == torch.float32 and t.is_contiguous()
+    d, y = _precise_conv_setup((N, H, W, Cin), x_nhwc.device, cout, kh, kw, stride, padding, a_op, epilogue, out_format,
+                               ep_x, ep_beta, out, kpad=int(cin_real or 0), k_order=1 if x_is_nchw_rgb else 0)
     with _timed(tag or 'conv_f32'):
         _check(lib().sc2_conv2d_f32_fwd(ctypes.byref(d), _ptr(x_nhwc), _ptr(w_frag), _ptr(y), _ptr(ep_x), _ptr(ep_beta),
                                         _stream()), 'conv2d_f32_fwd')
@@ -1633,8 +1657,7 @@ def conv2d_f32_fwd(x_nhwc, w_frag, cout, kh, kw, stride, padding, a_op=AOP_NONE,
 def conv_split_fused_gdn_supported(cout):
     """conv + GDN1 in one split launch: every channel of a pixel in one wave (Cout <= 96) and ceil(Cout / 16) * 16 == the chunk
     width (96 / 48 / 32 / 20 ... yes; 64 or 16 no: two launches)."""
-    cout = int(cout)
-    return cout <= 96 and (cout + 15) // 16 * 16 == int(lib().sc2_conv_split_chunk_channels(cout))
+    return _precise_fused_gdn_supported(cout, lib().sc2_conv_split_chunk_channels)
 
 
 def split_bf16(t, ns):
@@ -1654,16 +1677,7 @@ def pack_conv_split(weight, ns, cin_pad=None):
     ns = int(ns)
     if ns not in (2, 3):
         raise Sc2Error('pack_conv_split: ns must be 2 or 3, got {}'.format(ns))
-    w = weight.detach().float()
-    Cout, Cin, KH, KW = w.shape
-    cin_pad = (Cin + 3) // 4 * 4 if cin_pad is None else cin_pad
-    cc = int(lib().sc2_conv_split_chunk_channels(Cout))
-    chunks, NT = (Cout + cc - 1) // cc, cc // 16
-    K = KH * KW * cin_pad
-    steps = (K + 31) // 32
-    m = torch.zeros((chunks * cc, KH, KW, cin_pad), dtype=torch.float32, device=w.device)
-    m[:Cout, :, :, :Cin] = w.permute(0, 2, 3, 1)
-    m = torch.nn.functional.pad(m.reshape(chunks * cc, K), (0, steps * 32 - K))
+    m, chunks, NT, steps = _precise_weight_matrix(weight, cin_pad, lib().sc2_conv_split_chunk_channels, 32)
     m = torch.stack(split_bf16(m, ns))                        # [part, row, k]
     m = m.reshape(ns, chunks, NT, 16, steps, 2, 4, 4)         # [part, ch, nt, r, s, half, q, e]
     return m.permute(1, 4, 0, 2, 6, 3, 5, 7).contiguous()     # [ch, s, part, nt, q, r, half, e]
@@ -1682,26 +1696,9 @@ def conv2d_split_fwd(x_nhwc, w_frag, cout, kh, kw, stride, padding, ns, a_op=AOP
         assert x_nhwc.shape[1] == 3
         x_nhwc = nchw_f32_to_nhwc_f32(x_nhwc, 4)
     N, H, W, Cin = x_nhwc.shape
-    sh = stride[0] if isinstance(stride, (tuple, list)) else stride
-    ph = padding[0] if isinstance(padding, (tuple, list)) else padding
-    OH, OW = (H + 2 * ph - kh) // sh + 1, (W + 2 * ph - kw) // sh + 1
     steps = (kh * kw * Cin + 31) // 32
     if w_frag.shape[1] != steps or w_frag.shape[0] * w_frag.shape[3] * 16 < cout:
         raise Sc2Error('conv2d_split_fwd: w_frag {} was not packed for Cout {} K {}'.format(tuple(w_frag.shape), cout, kh * kw * Cin))
-    d = ConvDesc(N=N, H=H, W=W, Cin=Cin, Cout=cout, KH=kh, KW=kw, stride_h=sh, stride_w=sh, pad_h=ph, pad_w=ph, OH=OH, OW=OW,
-                 a_op=a_op, epilogue=epilogue, out_format=out_format, Kpad=0, Cout_pad=0, out_H=0, out_W=0, out_stride_h=0,
-                 out_stride_w=0, out_off_h=0, out_off_w=0, k_order=0)
-    if out_format == OUT_F32_NHWC:
-        y = torch.empty((N, OH, OW, cout), dtype=torch.float32, device=x_nhwc.device)
-    elif out_format == OUT_F32_NCHW:
-        y = torch.empty((N, cout, OH, OW), dtype=torch.float32, device=x_nhwc.device)
-    else:
-        assert out_format == OUT_I32_NCHW_SYM
-        if out is not None:
-            assert out.dtype == torch.int32 and out.is_contiguous() and out.numel() == N * cout * OH * OW
-            y = out.view(N, cout, OH, OW)
-        else:
-            y = torch.empty((N, cout, OH, OW), dtype=torch.int32, device=x_nhwc.device)
     gamma = None
     if epilogue in (EPI_FUSED_GDN, EPI_FUSED_IGDN):
         gamma, ep_x = ep_x, None
@@ -1710,14 +1707,8 @@ def conv2d_split_fwd(x_nhwc, w_frag, cout, kh, kw, stride, padding, ns, a_op=AOP
             assert gamma.dtype == torch.bfloat16 and gamma.is_contiguous() and gamma.dim() == 8 and gamma.shape[2] == ns
             if gamma.shape[0] != 1 or gamma.shape[1] != (cout + 31) // 32 or gamma.shape[3] != w_frag.shape[3]:
                 raise Sc2Error('conv2d_split_fwd: gamma {} was not packed as a 1x1 weight of {} channels'.format(tuple(gamma.shape), cout))
-    for t in (ep_x, ep_beta):
-        if t is not None:
-            _dev(t, 'epilogue operand')
-            assert t.dtype == torch.float32 and t.is_contiguous()
-    if ep_x is not None:
-        assert ep_x.numel() == N * OH * OW * cout
-    if ep_beta is not None:
-        assert ep_beta.numel() >= cout
+    d, y = _precise_conv_setup(tuple(x_nhwc.shape), x_nhwc.device, cout, kh, kw, stride, padding, a_op, epilogue, out_format,
+                               ep_x, ep_beta, out)
     with _timed(tag or 'conv_split'):
         _check(lib().sc2_conv2d_split_fwd(ctypes.byref(d), int(ns), _ptr(x_nhwc), _ptr(w_frag), _ptr(y), _ptr(ep_x), _ptr(gamma),
                                           _ptr(ep_beta), _stream()), 'conv2d_split_fwd')
