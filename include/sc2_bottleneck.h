@@ -287,8 +287,8 @@ int sc2_conv1x1_pair_fwd(const void *o, const void *w3_frag, const float *b3, co
 int sc2_nchw_f32_to_nhwc_f32(const float *x, float *y, int N, int C, int H, int W, int Cpad, void *stream);
 /* Output channels per weight chunk for a given Cout (32, 48 or 96): the packing unit of w_frag below. */
 int sc2_conv_f32_chunk_channels(int Cout);
-/* d      : as for sc2_conv2d_fwd; Cin % 4 == 0 (the padded channel count of x), square stride / padding, no output scatter;
- *          Cout_pad / k_order are ignored.  Kpad: 0, or the number of REAL input channels: Cin == 4 with Kpad == 3 says that
+/* d      : as for sc2_conv2d_fwd; Cin % 4 == 0 (the padded channel count of x), square stride (stride_h == stride_w), pad_h and
+ *          pad_w each >= 0 and independent; Cout_pad / k_order are ignored.  Kpad: 0, or the number of REAL input channels: Cin == 4 with Kpad == 3 says that
  *          channel 3 of x is zero and zero-weighted (the layout sc2_nchw_f32_to_nhwc_f32 and the packer produce for RGB), and
  *          the kernel skips those products (same sums: they are exact zeros).  With that, k_order == 1 says that x is the f32 NCHW image
  *          [N, 3, H, W] itself (the reference's input layout): the three channel planes are read in place, no NHWC copy.  a_op: NONE / ABS / SQUARE.  epilogue: NONE, BIAS, GDN (y = ep_x * (1 /
@@ -296,6 +296,15 @@ int sc2_conv_f32_chunk_channels(int Cout);
  *          FUSED_GDN / FUSED_IGDN (Cout <= 96): the conv followed by GDN1 over its own output in one launch, `ep_x` = the
  *          effective gamma as the w_frag of a 1x1 conv Cout -> Cout (same packing), ep_beta = the effective beta; bit-identical
  *          to the two launches.
+ *          BIAS_RELU / BIAS_LEAKY_RELU (the activations of the hyperprior transforms h_a / h_s): on the f32 value v = acc
+ *          (+ ep_beta[c]; ep_beta may be NULL: no bias), v > 0 ? v : 0 resp. v > 0 ? v : v * 0.01f -- torch's CPU forms, one f32
+ *          multiply; any out_format but the symbols.
+ *          Output scatter (out_H != 0), with the meaning sc2_conv2d_fwd gives the fields: OH / OW are taken as given (rows past the
+ *          padding formula read implicit zeros) and output pixel (oh, ow) goes to (oh*out_stride_h + out_off_h, ow*out_stride_w +
+ *          out_off_w) of y = f32 NHWC [N,out_H,out_W,Cout]; pixels outside it are dropped.  SC2_OUT_F32_NHWC only, with the
+ *          epilogues NONE / BIAS / BIAS_RELU / BIAS_LEAKY_RELU: a transposed convolution is one such launch per stride-parity
+ *          class (`HipConvTranspose2d.forward_nhwc_precise`).  Scatter with GDN / IGDN / FUSED_*, with another out_format, or a
+ *          stride_h != stride_w returns SC2_ERR_UNSUPPORTED.
  * x      : f32 NHWC [N,H,W,Cin]; addressed through a 32-bit buffer descriptor: N*H*W*Cin*4 (N*H*W*12 for the NCHW image) must be
  *          below 0x7FF00000 bytes (SC2_ERR_UNSUPPORTED otherwise -- about 445 images of the 96-channel 112 x 112 map; the host side
  *          runs larger batches as slices, `FPBasedResNetBottleneck._analysis_f32`)
@@ -318,9 +327,11 @@ int sc2_conv2d_f32_fwd(const sc2_conv_desc *d, const float *x, const float *w_fr
 /* Output channels per weight chunk for a given Cout (32, 48 or 96): the packing unit of w_frag below. */
 int sc2_conv_split_chunk_channels(int Cout);
 /* d       : as for sc2_conv2d_f32_fwd, but x is always f32 NHWC (k_order must be 0; Kpad / Cout_pad are ignored): Cin % 4 == 0,
- *           square stride / padding, no output scatter.  a_op: NONE / ABS / SQUARE, applied to the f32 value before the split.
- *           epilogue: NONE, BIAS, GDN, IGDN, FUSED_GDN / FUSED_IGDN (a_op NONE, Cout <= 96 with ceil(Cout / 16) * 16 == the chunk width),
- *           in the operation order of sc2_conv2d_f32_fwd; the fused form is bit-identical to the two launches.
+ *           square stride, pad_h / pad_w independent.  a_op: NONE / ABS / SQUARE, applied to the f32 value before the split.
+ *           epilogue: NONE, BIAS, BIAS_RELU, BIAS_LEAKY_RELU, GDN, IGDN, FUSED_GDN / FUSED_IGDN (a_op NONE, Cout <= 96 with
+ *           ceil(Cout / 16) * 16 == the chunk width), in the operation order of sc2_conv2d_f32_fwd; the fused form is bit-identical
+ *           to the two launches.  Output scatter (out_H != 0): exactly as for sc2_conv2d_f32_fwd -- both kernels run one copy of
+ *           the epilogue and of the descriptor rules (csrc/conv_precise.h).
  * n_parts : 2 or 3 (anything else: SC2_ERR_UNSUPPORTED); w_frag and gamma_frag must be packed for the same value.
  * x       : f32 NHWC [N,H,W,Cin], N*H*W*Cin*4 below 0x7FF00000 bytes (SC2_ERR_UNSUPPORTED otherwise)
  * w_frag  : bf16, [chunks][steps][n_parts][NT][64 lanes][8] with cc = sc2_conv_split_chunk_channels(Cout), NT = cc / 16, chunks =

@@ -494,7 +494,7 @@ extern "C" int sc2_conv2d_f32_fwd(const sc2_conv_desc *d, const float *x, const 
     const int chunks = (d->Cout + cc - 1) / cc;
     // (measured: four row tiles per wave for the narrow chunks -- twice the MFMAs per operand load -- ran the 96 -> 48 k5 s2 conv
     //  in 2.89 ms instead of 2.38 at bs 256: fewer, fatter waves hide less of the operand latency; two row tiles everywhere)
-    if (fused && a.planar && d->Cout == 96 && d->KH == 5 && d->KW == 5 && d->stride_h == 2 && d->pad_h == 2 && d->out_format == SC2_OUT_F32_NHWC &&
+    if (fused && a.planar && d->Cout == 96 && d->KH == 5 && d->KW == 5 && d->stride_h == 2 && d->pad_h == 2 && d->pad_w == 2 && d->out_format == SC2_OUT_F32_NHWC &&
         f32_persist0_enabled() && a.M * 96LL * 4LL < 0xFFFFFF00LL) {
         a.y_bytes = (unsigned)(a.M * 96LL * 4LL);
         const size_t lds = (size_t)(P0_W_FRAGS + P0_G_FRAGS + 24) * 16;

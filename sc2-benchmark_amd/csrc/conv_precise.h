@@ -17,7 +17,8 @@ struct PreciseArgs {
     const float *__restrict__ ep_x;    // f32 NHWC [N, OH, OW, Cout] (GDN operand) or null
     const float *__restrict__ ep_beta; // f32 [Cout]: beta (GDN) / bias / medians (symbols) or null
     void *__restrict__ y;
-    int N, H, W, Cin, Cout, KH, KW, stride, pad, OH, OW;
+    int N, H, W, Cin, Cout, KH, KW, stride, pad_h, pad_w, OH, OW;
+    int o_H, o_W, o_sh, o_sw, o_h0, o_w0;   // output scatter (o_H == 0: dense): pixel (oh, ow) -> (oh o_sh + o_h0, ow o_sw + o_w0) of [N, o_H, o_W, Cout]
     int a_op, epilogue, out_format;
     int n_steps;                       // k-steps of the caller's MFMA shape
     long long M;                       // N * OH * OW
@@ -57,8 +58,8 @@ __device__ __forceinline__ void precise_rows(const PreciseArgs &p, long long m_b
             const uint32_t ohw_u = (uint32_t)(p.OH * p.OW), n = (uint32_t)m / ohw_u;
             const int rem = (int)((uint32_t)m - n * ohw_u);
             const int oh = (int)((uint32_t)rem / (uint32_t)p.OW), ow = rem - oh * p.OW;
-            ih0[mt] = oh * p.stride - p.pad;
-            iw0[mt] = ow * p.stride - p.pad;
+            ih0[mt] = oh * p.stride - p.pad_h;
+            iw0[mt] = ow * p.stride - p.pad_w;
             a_base[mt] = (uint32_t)(((((long long)n * img_rows + ih0[mt]) * (long long)p.W + iw0[mt]) * pix_floats) * 4);
         } else {
             ih0[mt] = iw0[mt] = -(1 << 20);       // every tap out of bounds: zeros
@@ -71,6 +72,8 @@ __device__ __forceinline__ void precise_rows(const PreciseArgs &p, long long m_b
 // (pixel m_base + mt * 16 + r, channel (chunk * NT + nt) * 16 + 4 q + i) -- a lane holds FOUR CONSECUTIVE CHANNELS of one
 // pixel: one 16-byte access per tile for NHWC tensors (ep_x, y), and for NCHW outputs the 16 lanes of a quarter write 16
 // consecutive pixels of a channel plane.  nrm: the fused GDN's gamma |acc| sums in the same layout (FUSED only).
+// Output scatter (o_H != 0; f32 NHWC, plain / bias / activation epilogues only: the host refuses the rest): the pixel's row of
+// y is that of its place in [N, o_H, o_W, Cout]; a pixel outside that tensor is dropped.
 template <int MT, int NT, bool FUSED>
 __device__ __forceinline__ void precise_epilogue(const PreciseArgs &p, const f32x4_t (&acc)[MT][NT],
                                                  const f32x4_t (&nrm)[FUSED ? MT : 1][FUSED ? NT : 1], long long m_base, int chunk,
@@ -83,6 +86,15 @@ __device__ __forceinline__ void precise_epilogue(const PreciseArgs &p, const f32
         if (m >= p.M) continue;
         const long long n_img = (uint32_t)m / (uint32_t)ohw;
         const long long pix = m - n_img * ohw;
+        long long y_row = m;                       // pixel index of the NHWC output
+        if constexpr (!FUSED) {
+            if (p.o_H != 0) {
+                const int oh = (int)((uint32_t)pix / (uint32_t)p.OW), ow = (int)pix - oh * p.OW;
+                const int yh = oh * p.o_sh + p.o_h0, yw = ow * p.o_sw + p.o_w0;
+                if (yh >= p.o_H || yw >= p.o_W) continue;
+                y_row = (n_img * p.o_H + yh) * p.o_W + yw;
+            }
+        }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const int c0 = (chunk * NT + nt) * 16 + 4 * q;
@@ -123,9 +135,17 @@ __device__ __forceinline__ void precise_epilogue(const PreciseArgs &p, const f32
             } else if (p.epilogue == SC2_EPI_BIAS) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] += bc[i];
+            } else if (p.epilogue == SC2_EPI_BIAS_RELU || p.epilogue == SC2_EPI_BIAS_LEAKY_RELU) {
+                // torch's CPU forms on the f32 value: relu v > 0 ? v : 0, leaky_relu v > 0 ? v : v * 0.01f (one f32 multiply)
+                const bool leaky = p.epilogue == SC2_EPI_BIAS_LEAKY_RELU;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float t = p.ep_beta ? v[i] + bc[i] : v[i];
+                    v[i] = t > 0.f ? t : (leaky ? t * 0.01f : 0.f);
+                }
             }
             if (p.out_format == SC2_OUT_F32_NHWC) {
-                float *dst = static_cast<float *>(p.y) + m * p.Cout + c0;
+                float *dst = static_cast<float *>(p.y) + y_row * p.Cout + c0;
                 if (vec4) {
                     *reinterpret_cast<f32x4_t *>(dst) = f32x4_t{v[0], v[1], v[2], v[3]};
                 } else {
@@ -154,16 +174,38 @@ inline int precise_chunk_channels(int Cout) { return Cout <= 32 ? 32 : (Cout <= 
 inline int precise_check_desc(const char *who, const sc2_conv_desc *d, const void *ep_x, const void *gamma, const void *ep_beta) {
     SC2_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cin % 4 == 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0,
                 SC2_ERR_INVALID_ARG, "%s: bad dims (Cin must be a multiple of 4)", who);
-    SC2_REQUIRE(d->stride_h == d->stride_w && d->pad_h == d->pad_w && d->stride_h > 0 && d->pad_h >= 0, SC2_ERR_UNSUPPORTED,
-                "%s: square stride / padding only", who);
-    SC2_REQUIRE(d->OH == (d->H + 2 * d->pad_h - d->KH) / d->stride_h + 1 && d->OW == (d->W + 2 * d->pad_w - d->KW) / d->stride_w + 1 &&
-                    d->OH > 0 && d->OW > 0,
-                SC2_ERR_INVALID_ARG, "%s: OH / OW do not match the geometry", who);
-    SC2_REQUIRE(d->out_H == 0, SC2_ERR_UNSUPPORTED, "%s: no output scatter", who);
+    SC2_REQUIRE(d->stride_h == d->stride_w && d->stride_h > 0, SC2_ERR_UNSUPPORTED, "%s: square stride only", who);
+    SC2_REQUIRE(d->pad_h >= 0 && d->pad_w >= 0, SC2_ERR_INVALID_ARG, "%s: negative padding", who);
+    const bool scatter = d->out_H != 0;
+    if (scatter) {
+        // transposed-convolution use, with the meaning sc2_conv2d_fwd gives the fields: OH / OW as given (rows past the padding
+        // formula read implicit zeros: the bounded activation loads), each pixel's place in [N, out_H, out_W, Cout] from the strides
+        // and offsets, pixels outside it dropped
+        SC2_REQUIRE(d->out_H > 0 && d->out_W > 0 && d->OH > 0 && d->OW > 0 && d->out_stride_h > 0 && d->out_stride_w > 0 &&
+                        d->out_off_h >= 0 && d->out_off_w >= 0,
+                    SC2_ERR_INVALID_ARG, "%s: bad output scatter", who);
+        // (32-bit row / column arithmetic in the kernels: oh * stride - pad, oh * out_stride + out_off)
+        SC2_REQUIRE((long long)d->OH * d->stride_h < (1 << 30) && (long long)d->OW * d->stride_w < (1 << 30) &&
+                        (long long)d->OH * d->out_stride_h + d->out_off_h < (1 << 30) && (long long)d->OW * d->out_stride_w + d->out_off_w < (1 << 30) &&
+                        (long long)d->N * d->out_H * d->out_W * d->Cout < (1ll << 33),
+                    SC2_ERR_UNSUPPORTED, "%s: scatter geometry too large for this kernel's index arithmetic", who);
+        SC2_REQUIRE(d->out_format == SC2_OUT_F32_NHWC, SC2_ERR_UNSUPPORTED, "%s: output scatter writes f32 NHWC only (out_format %d)", who,
+                    d->out_format);
+        SC2_REQUIRE(d->epilogue == SC2_EPI_NONE || d->epilogue == SC2_EPI_BIAS || d->epilogue == SC2_EPI_BIAS_RELU ||
+                        d->epilogue == SC2_EPI_BIAS_LEAKY_RELU,
+                    SC2_ERR_UNSUPPORTED, "%s: output scatter takes the plain, bias and activation epilogues only (epilogue %d)", who, d->epilogue);
+    } else {
+        SC2_REQUIRE(d->OH == (d->H + 2 * d->pad_h - d->KH) / d->stride_h + 1 && d->OW == (d->W + 2 * d->pad_w - d->KW) / d->stride_w + 1 &&
+                        d->OH > 0 && d->OW > 0,
+                    SC2_ERR_INVALID_ARG, "%s: OH / OW do not match the geometry", who);
+    }
     SC2_REQUIRE(d->a_op == SC2_AOP_NONE || d->a_op == SC2_AOP_ABS || d->a_op == SC2_AOP_SQUARE, SC2_ERR_INVALID_ARG, "%s: a_op", who);
     const bool fused = d->epilogue == SC2_EPI_FUSED_GDN || d->epilogue == SC2_EPI_FUSED_IGDN;
-    SC2_REQUIRE(d->epilogue == SC2_EPI_NONE || d->epilogue == SC2_EPI_GDN || d->epilogue == SC2_EPI_IGDN || d->epilogue == SC2_EPI_BIAS || fused,
+    const bool act = d->epilogue == SC2_EPI_BIAS_RELU || d->epilogue == SC2_EPI_BIAS_LEAKY_RELU;   // (ep_beta may be null: no bias)
+    SC2_REQUIRE(d->epilogue == SC2_EPI_NONE || d->epilogue == SC2_EPI_GDN || d->epilogue == SC2_EPI_IGDN || d->epilogue == SC2_EPI_BIAS || act || fused,
                 SC2_ERR_UNSUPPORTED, "%s: epilogue %d", who, d->epilogue);
+    SC2_REQUIRE(!act || d->out_format != SC2_OUT_I32_NCHW_SYM, SC2_ERR_INVALID_ARG,
+                "%s: symbols come straight from the accumulators (epilogue NONE)", who);
     SC2_REQUIRE(!fused || (d->Cout <= 96 && gamma && ep_beta), SC2_ERR_UNSUPPORTED,
                 "%s: the fused GDN needs every channel of a pixel in one chunk (Cout <= 96), gamma fragments and beta", who);
     // the fused norm GEMM walks the whole chunk width in k-steps of gamma fragments; gamma is packed as a 1x1 weight of K = Cout,
@@ -186,7 +228,8 @@ inline int precise_check_desc(const char *who, const sc2_conv_desc *d, const voi
 inline void precise_fill_args(PreciseArgs &a, const sc2_conv_desc *d, const float *x, const float *ep_x, const float *ep_beta, void *y) {
     a.x = x; a.ep_x = ep_x; a.ep_beta = ep_beta; a.y = y;
     a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.KH = d->KH; a.KW = d->KW;
-    a.stride = d->stride_h; a.pad = d->pad_h; a.OH = d->OH; a.OW = d->OW;
+    a.stride = d->stride_h; a.pad_h = d->pad_h; a.pad_w = d->pad_w; a.OH = d->OH; a.OW = d->OW;
+    a.o_H = d->out_H; a.o_W = d->out_W; a.o_sh = d->out_stride_h; a.o_sw = d->out_stride_w; a.o_h0 = d->out_off_h; a.o_w0 = d->out_off_w;
     a.a_op = d->a_op; a.epilogue = d->epilogue; a.out_format = d->out_format;
     a.M = (long long)d->N * d->OH * d->OW;
 }

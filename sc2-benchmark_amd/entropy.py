@@ -8,6 +8,7 @@ behaviour, but every tensor-sized computation runs in the HIP library (``hip.py`
 per-channel scalar work (reparametrisation of beta/gamma, softplus/tanh of the 58 bottleneck
 parameters per channel, the once-per-model CDF table build) uses torch ops.
 """
+import functools
 import math
 
 import numpy as np
@@ -94,6 +95,27 @@ def _raise_on_status(st, what):
         raise hip.Sc2Error('{}: rANS stream overflowed its maximum size'.format(what))
 
 
+def _precise_cached(mod, ns, make):
+    """make(pack) for the packer of `ns` parts (0: f32), cached on `mod` per (version of its weight, ns)."""
+    if ns not in (0, 2, 3):
+        raise hip.Sc2Error('precise kernels: ns must be 0 (f32), 2 or 3 (bf16 parts), got {!r}'.format(ns))
+    w = mod.weight
+    key = (w._version, w.device, w.data_ptr())
+    cache = mod.__dict__.setdefault('_precise_cache', {})
+    if cache.get('key') != key:
+        cache.clear()
+        cache['key'] = key
+    if ns not in cache:
+        with torch.no_grad():
+            cache[ns] = make((lambda t: hip.pack_conv_split(t, ns)) if ns else hip.pack_conv_f32)
+    return cache[ns]
+
+
+def _precise_conv(ns):
+    """The launcher of one precise convolution: hip.conv2d_f32_fwd (ns = 0) or hip.conv2d_split_fwd with ns parts."""
+    return functools.partial(hip.conv2d_split_fwd, ns=ns) if ns else hip.conv2d_f32_fwd
+
+
 class HipConv2d(nn.Conv2d):
     """nn.Conv2d(bias=False) parameter holder whose forward is the implicit-GEMM MFMA kernel.
 
@@ -131,6 +153,11 @@ class HipConv2d(nn.Conv2d):
             self._padw_key = key
         return self._padw
 
+    def precise_weight(self, ns=0):
+        """Fragment-major weights of the precise kernels: ns = 0 f32 (hip.pack_conv_f32), 2 / 3 bf16 parts (hip.pack_conv_split);
+        cached per (parameter version, ns)."""
+        return _precise_cached(self, ns, lambda pack: pack(self.weight))
+
     def forward_nhwc(self, x_nhwc, out_format=hip.OUT_BF16_NHWC):
         """x bf16 NHWC (channels possibly zero-padded beyond in_channels to a multiple of 8); a bias rides in the epilogue."""
         assert self.groups == 1 and self.dilation == (1, 1)
@@ -164,32 +191,52 @@ class HipConvTranspose2d(nn.ConvTranspose2d):
         key = (self.weight._version, self.weight.device, self.weight.data_ptr())
         if getattr(self, '_cls_key', None) != key:
             assert self.groups == 1 and self.dilation == (1, 1)
-            cin, cout, KH, KW = self.weight.shape          # ConvTranspose2d weight: [in, out, kh, kw]
-            sh, sw = self.stride
-            ph, pw = self.padding
-            wt = self.weight.detach().permute(1, 0, 2, 3)   # [out, in, kh, kw]: rows = output channels
-            if self._cout_pad() != cout:
-                wt = torch.cat([wt, wt.new_zeros((self._cout_pad() - cout,) + tuple(wt.shape[1:]))])
+            cout, cpad = self.out_channels, self._cout_pad()
             classes = []
-            for ch in range(sh):
-                rh = (ch + ph) % sh
-                khs = list(range(rh, KH, sh))
-                for cw in range(sw):
-                    rw = (cw + pw) % sw
-                    kws = list(range(rw, KW, sw))
-                    if not khs or not kws:
-                        raise hip.Sc2Error('HipConvTranspose2d: a stride-parity class without taps (k={} s={} p={})'
-                                           .format((KH, KW), (sh, sw), (ph, pw)))
-                    qh, qw = (ch + ph - rh) // sh, (cw + pw - rw) // sw
-                    pad_h, pad_w = len(khs) - 1 - qh, len(kws) - 1 - qw
-                    if pad_h < 0 or pad_w < 0:
-                        raise hip.Sc2Error('HipConvTranspose2d: unsupported geometry k={} s={} p={}'
-                                           .format((KH, KW), (sh, sw), (ph, pw)))
-                    sub = wt[:, :, khs][:, :, :, kws].flip(2, 3).contiguous()
-                    classes.append((ch, cw, len(khs), len(kws), pad_h, pad_w, hip.pack_conv_weight(sub)))
+            for c in hip.deconv_parity_classes(self.weight, self.stride, self.padding):
+                sub = c.sub if cpad == cout else torch.cat([c.sub, c.sub.new_zeros((cpad - cout,) + tuple(c.sub.shape[1:]))])
+                classes.append((c.off_h, c.off_w, len(c.khs), len(c.kws), c.pad_h, c.pad_w, hip.pack_conv_weight(sub)))
             self._cls = classes
             self._cls_key = key
         return self._cls
+
+    def _precise_classes(self, ns):
+        """The parity classes with their sub-filters packed for the precise kernels; cached per (parameter version, ns)."""
+        assert self.groups == 1 and self.dilation == (1, 1)
+        return _precise_cached(self, ns, lambda pack: [(c.off_h, c.off_w, len(c.khs), len(c.kws), c.pad_h, c.pad_w, pack(c.sub))
+                                                       for c in hip.deconv_parity_classes(self.weight, self.stride, self.padding)])
+
+    def forward_nhwc_precise(self, x_nhwc, ns=0, epilogue=hip.EPI_NONE, a_op=hip.AOP_NONE, out=None):
+        """The transposed convolution on the precise kernels: x f32 [N,H,W,Cin] (Cin % 4 == 0) -> f32 [N,OH,OW,Cout].  ns = 0: f32
+        operands (csrc/conv_f32.hip); 2 / 3: bf16 parts (csrc/conv_split.hip).  One launch per stride-parity class, each scattering
+        its rows into the one output with the bias and the activation (EPI_BIAS_RELU / EPI_BIAS_LEAKY_RELU) in its epilogue; every
+        output pixel belongs to exactly one class.  `out`: a dense f32 [N,OH,OW,Cout] tensor to write into."""
+        _require_device(x_nhwc, 'HipConvTranspose2d')
+        N, H, W, cin = x_nhwc.shape
+        if cin != self.in_channels or cin % 4:
+            raise hip.Sc2Error('HipConvTranspose2d (precise): input of {} channels for a layer of {} (a multiple of 4 is needed)'
+                               .format(cin, self.in_channels))
+        sh, sw = self.stride
+        OH = (H - 1) * sh - 2 * self.padding[0] + self.kernel_size[0] + self.output_padding[0]
+        OW = (W - 1) * sw - 2 * self.padding[1] + self.kernel_size[1] + self.output_padding[1]
+        cout = self.out_channels
+        bias = None if self.bias is None else self.bias.detach().float().contiguous()
+        if bias is not None and epilogue == hip.EPI_NONE:
+            epilogue = hip.EPI_BIAS
+        if out is None:
+            out = torch.empty((N, OH, OW, cout), dtype=torch.float32, device=x_nhwc.device)
+        elif tuple(out.shape) != (N, OH, OW, cout):
+            raise hip.Sc2Error('HipConvTranspose2d (precise): out is {}, the output {}'.format(tuple(out.shape), (N, OH, OW, cout)))
+        conv = _precise_conv(ns)
+        tag = (getattr(self, '_tag', None) or 'deconv') + ('.bf16x{}'.format(3 * (ns - 1)) if ns else '.f32')
+        for ch, cw, nkh, nkw, pad_h, pad_w, packed in self._precise_classes(ns):
+            rows = (OH - ch + sh - 1) // sh if OH > ch else 0
+            cols = (OW - cw + sw - 1) // sw if OW > cw else 0
+            if rows == 0 or cols == 0:
+                continue
+            conv(x_nhwc, packed, cout, nkh, nkw, 1, (pad_h, pad_w), a_op=a_op, epilogue=epilogue, ep_beta=bias,
+                 out_format=hip.OUT_F32_NHWC, tag=tag, scatter=(rows, cols, out, sh, sw, ch, cw))
+        return out
 
     def forward_nhwc(self, x_nhwc, epilogue=hip.EPI_NONE, ep_beta=None, out_format=hip.OUT_BF16_NHWC):
         """x bf16 [N,H,W,Cin] -> [N,(H-1)s-2p+k+op,(W-1)s-2p+k+op,Cout] (bf16, or f32 NHWC)."""
@@ -273,6 +320,51 @@ def run_hip_sequence(seq, x_nhwc, a_op=hip.AOP_NONE, last_out_format=hip.OUT_F32
                 hip.nchw_f32_to_nhwc_bf16(y32.float().contiguous())
         first = False
         i += 1
+    return h
+
+
+def run_hip_sequence_precise(seq, x_nhwc, ns=0, a_op=hip.AOP_NONE):
+    """run_hip_sequence on the precise kernels (`set_encoder_precision('f32' / 'bf16x3' / 'bf16x6')` of the hyperprior
+    bottlenecks): x f32 [N,H,W,C] (C % 4 == 0) through HipConv2d / HipConvTranspose2d layers on f32 NHWC activations, ns = 0 on
+    csrc/conv_f32.hip, 2 / 3 on csrc/conv_split.hip.  A ReLU / LeakyReLU(0.01) behind a layer runs in that layer's epilogue on the f32
+    value; `a_op` applies to the first layer's input.  The last layer writes f32 NCHW.  Any other module, or another slope, raises
+    Sc2Error: nothing here falls back to the bf16 kernels."""
+    _require_device(x_nhwc, 'run_hip_sequence_precise')
+    mods = list(seq)
+    conv = _precise_conv(ns)
+    sfx = '.bf16x{}'.format(3 * (ns - 1)) if ns else '.f32'
+    h = x_nhwc
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        nxt = mods[i + 1] if i + 1 < len(mods) else None
+        epi = hip.EPI_NONE
+        if isinstance(nxt, nn.ReLU):
+            epi = hip.EPI_BIAS_RELU
+        elif isinstance(nxt, nn.LeakyReLU):
+            if nxt.negative_slope != 0.01:
+                raise hip.Sc2Error('precise hyper transform: LeakyReLU slope {} (the kernels fuse 0.01)'.format(nxt.negative_slope))
+            epi = hip.EPI_BIAS_LEAKY_RELU
+        step = 2 if epi != hip.EPI_NONE else 1
+        last = i + step >= len(mods)
+        if not isinstance(m, (HipConv2d, HipConvTranspose2d)) or m.groups != 1 or m.dilation != (1, 1):
+            raise hip.Sc2Error('precise hyper transform: unsupported module {}'.format(m))
+        if h.shape[-1] != m.in_channels or m.in_channels % 4:
+            raise hip.Sc2Error('precise hyper transform: {} channels into {} (channel counts must be multiples of 4)'.format(h.shape[-1], m))
+        if isinstance(m, HipConv2d):
+            if m.stride[0] != m.stride[1]:
+                raise hip.Sc2Error('precise hyper transform: unsupported module {}'.format(m))
+            bias = m.bias_f32()
+            if bias is not None and epi == hip.EPI_NONE:
+                epi = hip.EPI_BIAS
+            h = conv(h, m.precise_weight(ns), m.out_channels, m.kernel_size[0], m.kernel_size[1], m.stride[0], tuple(m.padding),
+                     a_op=a_op if i == 0 else hip.AOP_NONE, epilogue=epi, ep_beta=bias,
+                     out_format=hip.OUT_F32_NCHW if last else hip.OUT_F32_NHWC, tag=(getattr(m, '_tag', None) or 'conv') + sfx)
+        else:
+            h = m.forward_nhwc_precise(h, ns, epi, a_op=a_op if i == 0 else hip.AOP_NONE)
+            if last:
+                h = h.permute(0, 3, 1, 2).contiguous()
+        i += step
     return h
 
 

@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and streams; every compute call 
 the C-ABI with raw pointers and the current HIP stream.  There is NO fallback: if the shared library
 is missing, or a tensor is not on a HIP device, the call raises.
 """
+import collections
 import ctypes
 import os
 
@@ -736,6 +737,39 @@ def conv2d_dgrad(gy_nhwc, weight, stride, pad, in_hw, out_dtype=torch.bfloat16, 
                 conv2d_fwd(gy_nhwc, packed, cin, len(khs), len(kws), 1, (pad_h, pad_w), out_format=fmt, tag='dgrad',
                            scatter=(rows, cols, gx, sh, sw, ch, cw))
     return gx
+
+
+ParityClass = collections.namedtuple('ParityClass', 'off_h off_w khs kws pad_h pad_w sub')
+
+
+def deconv_parity_classes(weight, stride, padding):
+    """A transposed convolution as stride-1 correlations, one per stride-parity class of the output (device-free: plain torch on
+    whatever device `weight` is).  weight: ConvTranspose2d's [Cin, Cout, KH, KW]; stride, padding: (h, w).  Output pixel
+    (off_h + sh * r, off_w + sw * c) of class (off_h, off_w) is the correlation of the input, zero-padded by (pad_h, pad_w) at the
+    top / left and as far as needed at the bottom / right, with `sub` [Cout, Cin, len(khs), len(kws)]: the taps khs x kws of the
+    filter that reach the class, flipped, at row r / column c.  A class has ceil((OH - off_h) / sh) rows.
+    -> [ParityClass(off_h, off_w, khs, kws, pad_h, pad_w, sub)], sh * sw entries."""
+    KH, KW = int(weight.shape[2]), int(weight.shape[3])
+    sh, sw = stride
+    ph, pw = padding
+    wt = weight.detach().permute(1, 0, 2, 3)   # [out, in, kh, kw]: rows = output channels
+    classes = []
+    for ch in range(sh):
+        rh = (ch + ph) % sh
+        khs = list(range(rh, KH, sh))
+        for cw in range(sw):
+            rw = (cw + pw) % sw
+            kws = list(range(rw, KW, sw))
+            if not khs or not kws:
+                raise Sc2Error('HipConvTranspose2d: a stride-parity class without taps (k={} s={} p={})'
+                               .format((KH, KW), (sh, sw), (ph, pw)))
+            qh, qw = (ch + ph - rh) // sh, (cw + pw - rw) // sw
+            pad_h, pad_w = len(khs) - 1 - qh, len(kws) - 1 - qw
+            if pad_h < 0 or pad_w < 0:
+                raise Sc2Error('HipConvTranspose2d: unsupported geometry k={} s={} p={}'.format((KH, KW), (sh, sw), (ph, pw)))
+            sub = wt[:, :, khs][:, :, :, kws].flip(2, 3).contiguous()
+            classes.append(ParityClass(ch, cw, khs, kws, pad_h, pad_w, sub))
+    return classes
 
 
 def conv_fused_gdn_supported(x_shape, cout, kh, kw, stride, pad, out_format=OUT_BF16_NHWC):
@@ -1594,18 +1628,31 @@ def pack_conv_f32(weight, cin_pad=None):
     return m.permute(0, 3, 1, 4, 2, 5).contiguous()       # [ch, s, nt, q, r, j]
 
 
-def _precise_conv_setup(x_shape, device, cout, kh, kw, stride, padding, a_op, epilogue, out_format, ep_x, ep_beta, out, kpad=0, k_order=0):
+def _precise_conv_setup(x_shape, device, cout, kh, kw, stride, padding, a_op, epilogue, out_format, ep_x, ep_beta, out, kpad=0, k_order=0,
+                        scatter=None):
     """What conv2d_f32_fwd and conv2d_split_fwd share: x_shape (N, H, W, Cin) -> (the ConvDesc, the output tensor per out_format; a
     symbol buffer passed as `out` is used in place).  ep_x: the GDN operand [N,OH,OW,Cout] (with a fused epilogue: the f32 kernel's
-    gamma fragments); ep_beta: [>= Cout]; both f32, dense."""
+    gamma fragments); ep_beta: [>= Cout]; both f32, dense.  stride / padding: int or (h, w) (the library takes a square stride only).
+    scatter: (rows, cols, out f32 [N,out_H,out_W,cout], stride_h, stride_w, off_h, off_w) as for conv2d_fwd -- the launch computes
+    rows x cols pixels per image and writes pixel (r, c) to (r*stride_h + off_h, c*stride_w + off_w) of `out`, which it returns."""
     N, H, W, Cin = x_shape
-    sh = stride[0] if isinstance(stride, (tuple, list)) else stride
-    ph = padding[0] if isinstance(padding, (tuple, list)) else padding
-    OH, OW = (H + 2 * ph - kh) // sh + 1, (W + 2 * ph - kw) // sh + 1
-    d = ConvDesc(N=N, H=H, W=W, Cin=Cin, Cout=cout, KH=kh, KW=kw, stride_h=sh, stride_w=sh, pad_h=ph, pad_w=ph, OH=OH, OW=OW,
-                 a_op=a_op, epilogue=epilogue, out_format=out_format, Kpad=kpad, Cout_pad=0, out_H=0, out_W=0, out_stride_h=0,
-                 out_stride_w=0, out_off_h=0, out_off_w=0, k_order=k_order)
-    if out_format == OUT_F32_NHWC:
+    sh, sw = (stride, stride) if isinstance(stride, int) else stride
+    ph, pw = (padding, padding) if isinstance(padding, int) else padding
+    OH, OW = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
+    sc = (0, 0, 0, 0, 0, 0)
+    if scatter is not None:
+        OH, OW, y, s_h, s_w, o_h, o_w = scatter
+        _dev(y, 'scatter output')
+        # (the dtype and layout of `out` are the caller's promise whatever out_format says: the library refuses the formats it
+        #  does not scatter)
+        assert y.dtype == torch.float32 and y.is_contiguous() and y.dim() == 4 and y.shape[0] == N and y.shape[3] == cout
+        sc = (y.shape[1], y.shape[2], s_h, s_w, o_h, o_w)
+    d = ConvDesc(N=N, H=H, W=W, Cin=Cin, Cout=cout, KH=kh, KW=kw, stride_h=sh, stride_w=sw, pad_h=ph, pad_w=pw, OH=OH, OW=OW,
+                 a_op=a_op, epilogue=epilogue, out_format=out_format, Kpad=kpad, Cout_pad=0, out_H=sc[0], out_W=sc[1], out_stride_h=sc[2],
+                 out_stride_w=sc[3], out_off_h=sc[4], out_off_w=sc[5], k_order=k_order)
+    if scatter is not None:
+        pass
+    elif out_format == OUT_F32_NHWC:
         y = torch.empty((N, OH, OW, cout), dtype=torch.float32, device=device)
     elif out_format == OUT_F32_NCHW:
         y = torch.empty((N, cout, OH, OW), dtype=torch.float32, device=device)
@@ -1628,11 +1675,13 @@ def _precise_conv_setup(x_shape, device, cout, kh, kw, stride, padding, a_op, ep
 
 
 def conv2d_f32_fwd(x_nhwc, w_frag, cout, kh, kw, stride, padding, a_op=AOP_NONE, epilogue=EPI_NONE, out_format=None,
-                   ep_x=None, ep_beta=None, out=None, tag=None, cin_real=0, x_is_nchw_rgb=False):
+                   ep_x=None, ep_beta=None, out=None, tag=None, cin_real=0, x_is_nchw_rgb=False, scatter=None):
     """x_nhwc: f32 [N,H,W,Cin] (Cin % 4 == 0) -> per out_format: OUT_F32_NHWC [N,OH,OW,Cout] (default), OUT_F32_NCHW
     [N,Cout,OH,OW], OUT_I32_NCHW_SYM int32 [N,Cout,OH,OW] (ep_beta = medians).  cin_real: the module's channel count when x_nhwc
     carries zero padding channels (3 of 4: the kernel skips the padding channel's products).  x_is_nchw_rgb: x_nhwc is the f32 NCHW
-    image [N,3,H,W] itself (w_frag packed for cin_pad 4 as always): the kernel reads the three planes in place."""
+    image [N,3,H,W] itself (w_frag packed for cin_pad 4 as always): the kernel reads the three planes in place.
+    padding: int or (h, w).  epilogue: also EPI_BIAS_RELU / EPI_BIAS_LEAKY_RELU (slope 0.01), ep_beta = the bias or None.
+    scatter: see _precise_conv_setup (OUT_F32_NHWC, plain / bias / activation epilogues)."""
     _dev(x_nhwc, 'x')
     assert x_nhwc.dtype == torch.float32 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
     assert w_frag.dtype == torch.float32 and w_frag.is_contiguous()
@@ -1644,7 +1693,7 @@ def conv2d_f32_fwd(x_nhwc, w_frag, cout, kh, kw, stride, padding, a_op=AOP_NONE,
     else:
         N, H, W, Cin = x_nhwc.shape
     d, y = _precise_conv_setup((N, H, W, Cin), x_nhwc.device, cout, kh, kw, stride, padding, a_op, epilogue, out_format,
-                               ep_x, ep_beta, out, kpad=int(cin_real or 0), k_order=1 if x_is_nchw_rgb else 0)
+                               ep_x, ep_beta, out, kpad=int(cin_real or 0), k_order=1 if x_is_nchw_rgb else 0, scatter=scatter)
     with _timed(tag or 'conv_f32'):
         _check(lib().sc2_conv2d_f32_fwd(ctypes.byref(d), _ptr(x_nhwc), _ptr(w_frag), _ptr(y), _ptr(ep_x), _ptr(ep_beta),
                                         _stream()), 'conv2d_f32_fwd')
@@ -1684,7 +1733,7 @@ def pack_conv_split(weight, ns, cin_pad=None):
 
 
 def conv2d_split_fwd(x_nhwc, w_frag, cout, kh, kw, stride, padding, ns, a_op=AOP_NONE, epilogue=EPI_NONE, out_format=None,
-                     ep_x=None, ep_beta=None, out=None, tag=None, cin_real=0, x_is_nchw_rgb=False):
+                     ep_x=None, ep_beta=None, out=None, tag=None, cin_real=0, x_is_nchw_rgb=False, scatter=None):
     """conv2d_f32_fwd's interface on the split-bf16 kernels (ns = 2: three bf16 products per k, ns = 3: six; w_frag and, for the
     fused epilogues, ep_x = gamma from pack_conv_split with the same ns).  x_is_nchw_rgb: x_nhwc is the f32 NCHW image; it goes
     through its NHWC copy (same result).  cin_real is accepted and ignored (the padding channel's products are exact zeros)."""
@@ -1708,7 +1757,7 @@ def conv2d_split_fwd(x_nhwc, w_frag, cout, kh, kw, stride, padding, ns, a_op=AOP
             if gamma.shape[0] != 1 or gamma.shape[1] != (cout + 31) // 32 or gamma.shape[3] != w_frag.shape[3]:
                 raise Sc2Error('conv2d_split_fwd: gamma {} was not packed as a 1x1 weight of {} channels'.format(tuple(gamma.shape), cout))
     d, y = _precise_conv_setup(tuple(x_nhwc.shape), x_nhwc.device, cout, kh, kw, stride, padding, a_op, epilogue, out_format,
-                               ep_x, ep_beta, out)
+                               ep_x, ep_beta, out, scatter=scatter)
     with _timed(tag or 'conv_split'):
         _check(lib().sc2_conv2d_split_fwd(ctypes.byref(d), int(ns), _ptr(x_nhwc), _ptr(w_frag), _ptr(y), _ptr(ep_x), _ptr(gamma),
                                           _ptr(ep_beta), _stream()), 'conv2d_split_fwd')

@@ -14,7 +14,7 @@ from torch import nn
 
 from . import hip
 from .entropy import (CompressionModel, GDN1, GaussianConditional, HipConv2d, HipConvTranspose2d, _require_device,
-                      get_scale_table, run_hip_sequence, update_registered_buffers)
+                      get_scale_table, run_hip_sequence, run_hip_sequence_precise, update_registered_buffers)
 
 LAYER_CLASS_DICT = dict()
 LAYER_FUNC_DICT = dict()
@@ -659,20 +659,61 @@ class SHPBasedResNetBottleneck(BaseBottleneck):
     synthesis_nhwc_tail = FPBasedResNetBottleneck.synthesis_nhwc_tail
     _last_conv = FPBasedResNetBottleneck._last_conv
     synthesis = FPBasedResNetBottleneck.synthesis
+    _f32_pack = FPBasedResNetBottleneck._f32_pack
+    _analysis_f32 = FPBasedResNetBottleneck._analysis_f32
     _hyper_abs = True       # h_a sees |y| (layer.py:641,675)
+
+    def set_encoder_precision(self, precision):
+        """The FP bottleneck's switch ('bf16' default, 'f32', 'bf16x3', 'bf16x6': FPBasedResNetBottleneck.set_encoder_precision),
+        here a property of the CODEC, not only of the encoder.  Three floating-point transforms decide the bytes of a hyperprior
+        stream: g_a the y symbols, h_a the z symbols, and h_s the CDF-row index of every y symbol (and MSHP's means) -- which the
+        DECODER rebuilds from the decoded z.  In the three precise modes all of them run on the precise kernels (csrc/conv_f32.hip /
+        conv_split.hip; the transposed convolutions of h_s as stride-parity classes, activations in the f32 epilogue, the
+        hyper-latent travelling as f32) in every no-grad path: encode, decode, the eval and updated-train forward, the likelihood
+        path without grad, stage_front / stage_coder.  g_s, the autograd training paths and 'bf16' are what they were.
+        A stream made in one mode is only guaranteed to decode in THAT mode: another mode's h_s may put a scale on the other side
+        of a scale-table boundary, and one wrong index desynchronises the range decoder.  Set the same mode on both ends."""
+        return FPBasedResNetBottleneck.set_encoder_precision(self, precision)
+
+    set_compute_dtype = set_encoder_precision
+
+    def _precise_ns(self):
+        """None in 'bf16' mode, else the bf16 parts per operand of the precise kernels (0: f32 operands)."""
+        if self.encoder_precision == 'bf16':
+            return None
+        return _SPLIT_PARTS.get(self.encoder_precision, 0)
 
     # ---- hyper transforms on the device --------------------------------------------------------- #
     def hyper_analysis(self, y):
         """z = h_a(|y|) (SHP) or h_a(y) (MSHP): f32 NCHW latent -> f32 NCHW hyper-latent."""
+        a_op = hip.AOP_ABS if self._hyper_abs else hip.AOP_NONE
+        ns = self._precise_ns()
+        if ns is not None:
+            return run_hip_sequence_precise(self.h_a, hip.nchw_f32_to_nhwc_f32(y.float()), ns, a_op=a_op)
         y_nhwc = hip.nchw_f32_to_nhwc_bf16(y.float().contiguous(), y.shape[1])
-        return run_hip_sequence(self.h_a, y_nhwc, a_op=hip.AOP_ABS if self._hyper_abs else hip.AOP_NONE)
+        return run_hip_sequence(self.h_a, y_nhwc, a_op=a_op)
 
     def hyper_synthesis(self, z_hat_nhwc):
-        """h_s(z_hat) on a bf16 NHWC hyper-latent -> f32 NCHW Gaussian parameters."""
+        """h_s(z_hat) on an NHWC hyper-latent (bf16; f32 in the precise modes: what _z_hat_nhwc / _z_hat_from_symbols return)
+        -> f32 NCHW Gaussian parameters."""
+        ns = self._precise_ns()
+        if ns is not None:
+            if z_hat_nhwc.dtype != torch.float32:
+                raise hip.Sc2Error('hyper_synthesis: mode {!r} takes the f32 hyper-latent'.format(self.encoder_precision))
+            return run_hip_sequence_precise(self.h_s, z_hat_nhwc, ns)
         return run_hip_sequence(self.h_s, z_hat_nhwc)
 
     def _z_hat_nhwc(self, z_hat):
+        if self._precise_ns() is not None:      # symbols + medians is not bf16-exact: the hyper-latent stays f32
+            return hip.nchw_f32_to_nhwc_f32(z_hat.float())
         return hip.nchw_f32_to_nhwc_bf16(z_hat.float().contiguous(), z_hat.shape[1])
+
+    def _z_hat_from_symbols(self, z_sym, z_shape):
+        """int32 z symbols [N, L*hz*wz] -> the dequantised hyper-latent as hyper_synthesis takes it."""
+        eb = self.entropy_bottleneck
+        if self._precise_ns() is not None:
+            return self._z_hat_nhwc(eb.dequantize_device(z_sym, tuple(z_shape), want_f32=True, want_nhwc=False)[0])
+        return eb.dequantize_device(z_sym, tuple(z_shape), want_f32=False, want_nhwc=True)[1]
 
     def _params(self, gaussian_params):
         """-> (scales_hat, means_hat or None)"""
@@ -688,8 +729,7 @@ class SHPBasedResNetBottleneck(BaseBottleneck):
         # the coder is lossless: z_hat = dequantize(symbols) is what decompress(compress(z)) returns (layer.py:643-645), so the
         # hyper-synthesis does not wait for the serial coder; both streams are then coded by whichever coder suits the batch
         z_sym = eb.symbols_device(z)
-        _, z_hat_nhwc = eb.dequantize_device(z_sym, tuple(z_shape), want_f32=False, want_nhwc=True)
-        scales_hat, means_hat = self._params(self.hyper_synthesis(z_hat_nhwc))
+        scales_hat, means_hat = self._params(self.hyper_synthesis(self._z_hat_from_symbols(z_sym, z_shape)))
         indices = self.gaussian_conditional.build_indexes(scales_hat)
         y_strings = self.gaussian_conditional.compress(y, indices, means=means_hat)
         z_strings = eb.compress_symbols(z_sym, int(z_shape[0]) * int(z_shape[1]))
@@ -702,7 +742,10 @@ class SHPBasedResNetBottleneck(BaseBottleneck):
         dev = eb._quantized_cdf.device
         if dev.type != 'cuda':
             raise hip.Sc2Error('{}.decode: module is on {}; HIP device required'.format(type(self).__name__, dev))
-        _, z_hat_nhwc = eb.decompress_to_device(strings[1], tuple(shape), want_f32=False, want_nhwc=True)
+        if self._precise_ns() is not None:     # the SAME mode as the encoder's: its h_s decides the indexes
+            z_hat_nhwc = self._z_hat_nhwc(eb.decompress_to_device(strings[1], tuple(shape), want_f32=True, want_nhwc=False)[0])
+        else:
+            _, z_hat_nhwc = eb.decompress_to_device(strings[1], tuple(shape), want_f32=False, want_nhwc=True)
         scales_hat, means_hat = self._params(self.hyper_synthesis(z_hat_nhwc))
         indices = self.gaussian_conditional.build_indexes(scales_hat)
         _, y_hat_nhwc = self.gaussian_conditional.decompress_to_device(strings[0], indices, means_hat, want_f32=False,
@@ -722,8 +765,7 @@ class SHPBasedResNetBottleneck(BaseBottleneck):
         eb, gc = self.entropy_bottleneck, self.gaussian_conditional
         z_shape = tuple(z.shape[-2:])
         z_sym = eb.symbols_device(z)
-        _, z_hat_nhwc = eb.dequantize_device(z_sym, z_shape, want_f32=False, want_nhwc=True)
-        scales_hat, means_hat = self._params(self.hyper_synthesis(z_hat_nhwc))
+        scales_hat, means_hat = self._params(self.hyper_synthesis(self._z_hat_from_symbols(z_sym, z_shape)))
         y_sym, idx = gc.symbols_indexes_device(y, scales_hat, means_hat)
         N = y.shape[0]
         return (y_sym.view(N, -1), idx.view(N, -1), z_sym), (tuple(y.shape[-2:]), z_shape)
@@ -739,8 +781,7 @@ class SHPBasedResNetBottleneck(BaseBottleneck):
         zb, zo, znb, zst = eb.encode_symbols_device(z_sym, hz * wz)
         yb, yo, ynb, yst = gc.encode_symbols_device(y_sym, idx)
         z_dec = eb.decode_symbols_device(zb, zo, znb, z_sym.shape[1], hz * wz)
-        _, z_hat_nhwc = eb.dequantize_device(z_dec, (hz, wz), want_f32=False, want_nhwc=True)
-        scales_hat, means_hat = self._params(self.hyper_synthesis(z_hat_nhwc))
+        scales_hat, means_hat = self._params(self.hyper_synthesis(self._z_hat_from_symbols(z_dec, (hz, wz))))
         idx2 = gc.build_indexes(scales_hat)
         y_dec, dst = gc.decode_symbols_device(yb, yo, ynb, idx2.view(N, -1))
         C = y_sym.shape[1] // (h * w)

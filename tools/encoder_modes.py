@@ -1,11 +1,14 @@
 """The four encoder precisions side by side on one box, in one process: the bench model at bs 256, 224 x 224.
 
-    python tools/encoder_modes.py [--rounds 3] [--reps 5] [--launches]
+    python tools/encoder_modes.py [--rounds 3] [--reps 5] [--launches] [--model fp | mshp | shp]
 
 The modes ('bf16', 'f32', 'bf16x3', 'bf16x6') are ALTERNATED for --rounds rounds, so that clock and thermal drift fall on all of
 them alike.  Per mode: the `stage_front` time per batch of every round (HIP events, as bench.py's precision_check), the symbol
 mismatch against the oracle's f32 CPU encoder on the first 64 images, the images whose symbols are all identical, and the bpp of
 the streams the device codes from them.  --launches adds the per-launch times of one extra pass (hip.KernelTimer).
+--model mshp | shp: the hyperprior bottlenecks instead (the mshp224 model of benchlib.workloads, or its scale-hyperprior twin),
+where the mode is a property of the codec (g_a, h_a and h_s): `stage_front` ms per batch, and against the oracle's f32 CPU chain
+the mismatch rates of z symbols, indexes and y symbols and the number of images with all three equal.
 Prints one JSON line."""
 import argparse
 import json
@@ -21,15 +24,101 @@ from sc2bench_amd import hip  # noqa: E402
 MODES = ('bf16', 'f32', 'bf16x3', 'bf16x6')
 
 
+def _shp_twin(dev):
+    """The scale-hyperprior twin of the mshp224 model: the same seed and operating point, the one-headed h_s tail scaled as a whole."""
+    import sc2bench_amd as S
+    torch.manual_seed(0)
+    bl = S.get_layer('SHPBasedResNetBottleneck')
+    with torch.no_grad():
+        eb = bl.entropy_bottleneck
+        q = torch.zeros(eb.channels, 1, 3)
+        for c in range(eb.channels):
+            q[c, 0, 0], q[c, 0, 1], q[c, 0, 2] = -(3 + c % 5), 0.25 * (c % 3), 4 + c % 7
+        eb.quantiles.copy_(q)
+        bl.g_a[4].weight.mul_(10.0)
+        bl.h_a[2].weight.mul_(4.0)
+        bl.h_s[4].weight.abs_().mul_(5.0)
+    bl.eval().to(dev)
+    bl.update()
+    return bl
+
+
+def main_hyper(args, dev):
+    from benchlib.model import synthetic_batch
+    from benchlib.workloads import build_workload
+    from oracle import cpu_ref as R
+    if args.model == 'mshp':
+        bl = build_workload('mshp224', dev, args.batch)[0].bottleneck_layer
+    else:
+        bl = _shp_twin(dev)
+    name = type(bl).__name__
+    mshp = name.startswith('MSHP')
+    x = synthetic_batch(args.batch, dev, seed=0)
+    n = min(32, args.batch)
+    ref = getattr(R, name)()
+    own = ref.state_dict()
+    ref.load_state_dict({k: v.detach().cpu() for k, v in bl.state_dict().items() if k in own and own[k].shape == v.shape}, strict=False)
+    ref.eval()
+    ref.update()
+    xc = x[:n].float().cpu()
+    with torch.no_grad():      # the oracle's f32 chain: what the reference's encode() computes before the coder
+        y = ref.g_a(xc)
+        z = ref.h_a(y if mshp else y.abs())
+        z_hat = ref.entropy_bottleneck.quantize(z, 'dequantize', ref._get_means(z))
+        params = ref.h_s(z_hat)
+        scales, means = params.chunk(2, 1) if mshp else (params, None)
+        want = (ref.entropy_bottleneck.symbols(z).int().reshape(n, -1), ref.gaussian_conditional.build_indexes(scales).int().reshape(n, -1),
+                ref.gaussian_conditional.quantize(y, 'symbols', means).int().reshape(n, -1))
+    out = {'what': '{}: codec precisions alternated in one process: stage_front ms per batch per round; z symbols, indexes and y symbols of '
+                   'the first {} images against the oracle\'s f32 CPU chain'.format(name, n), 'model': args.model, 'batch': args.batch,
+           'images_checked': n, 'rounds': args.rounds, 'reps_per_interval': args.reps, 'device': torch.cuda.get_device_name(dev), 'modes': {}}
+    with torch.no_grad():
+        for mode in MODES:
+            bl.set_encoder_precision(mode)
+            (y_sym, idx, z_sym), _ = bl.stage_front(x[:n])
+            diff = [a.cpu().reshape(n, -1) != b for a, b in zip((z_sym, idx, y_sym), want)]
+            same = ~(diff[0].any(dim=1) | diff[1].any(dim=1) | diff[2].any(dim=1))
+            out['modes'][mode] = {'z_symbol_mismatch_rate': diff[0].float().mean().item(), 'index_mismatch_rate': diff[1].float().mean().item(),
+                                  'y_symbol_mismatch_rate': diff[2].float().mean().item(),
+                                  'images_with_all_three_identical': int(same.sum().item()), 'stage_front_ms_per_batch': []}
+            bl.stage_front(x)        # packs the weights, warms the allocator
+        torch.cuda.synchronize(dev)
+        for _ in range(args.rounds):
+            for mode in MODES:
+                bl.set_encoder_precision(mode)
+                bl.stage_front(x)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(args.reps):
+                    bl.stage_front(x)
+                e1.record()
+                torch.cuda.synchronize(dev)
+                out['modes'][mode]['stage_front_ms_per_batch'].append(round(e0.elapsed_time(e1) / args.reps, 4))
+        if args.launches:
+            for mode in MODES:
+                bl.set_encoder_precision(mode)
+                torch.cuda.synchronize(dev)
+                with hip.KernelTimer() as kt:
+                    for _ in range(args.reps):
+                        bl.stage_front(x)
+                    torch.cuda.synchronize(dev)
+                out['modes'][mode]['launch_ms'] = {k: round(ms, 4) for k, (_, ms) in sorted(kt.summary().items())}
+    bl.set_encoder_precision('bf16')
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--reps', type=int, default=5, help='stage_front calls per timed interval')
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--launches', action='store_true')
+    ap.add_argument('--model', choices=('fp', 'mshp', 'shp'), default='fp', help='fp: the bench model (default); mshp / shp: the hyperprior bottlenecks')
     args = ap.parse_args()
     assert args.rounds >= 3
     dev = torch.device('cuda:0')
+    if args.model != 'fp':
+        return main_hyper(args, dev)
     model = bench.build_model(dev)
     x = bench.synthetic_batch(args.batch, dev)
     n = min(64, args.batch)
