@@ -160,6 +160,8 @@ enum sc2_conv_epilogue {
      * a_op = SC2_AOP_SQUARE and the 1x1 gamma GEMM, acc = gamma x^2 */
     SC2_EPI_GDN2 = 9,  /* y = ep_x * rsqrt(ep_beta[c] + acc)   (GDN, inverse=False) */
     SC2_EPI_IGDN2 = 10, /* y = ep_x * sqrt(ep_beta[c] + acc)    (GDN, inverse=True)  */
+    /* (sc2_conv2d_f32_fwd / sc2_conv2d_split_fwd take GDN2 as y = ep_x * (1.0f / sqrtf(ep_beta[c] + acc)), both operations
+     *  correctly rounded: see there) */
     /* sc2_gdn1_bwd_gemm only (round 5): the two GEMMs of the GDN1 backward with its element-wise halves in their epilogues.
      * n = ep_beta[c] + acc (acc = gamma |x|, a_op ABS), g = the gradient at the GDN's output, x = its input: */
     SC2_EPI_GDN1_BWD_PRE = 11,   /* ep_x = g, ep_x2 = x:  y2 = g / n (direct term),  y = -y2 * x / n  (d_norm) */
@@ -281,7 +283,8 @@ int sc2_conv1x1_pair_fwd(const void *o, const void *w3_frag, const float *b3, co
 /* f32 matrix cores (v_mfma_f32_16x16x4_f32: bit for bit a k-ordered f32 fma chain), for callers   */
 /* that need the symbols -- hence the byte streams -- the reference's f32 CPU path produces        */
 /* (nn.Conv2d + compressai GDN1 in f32, sc2bench/models/layer.py:475-483, quantised at :506).      */
-/* 1/16 of the bf16 matrix rate; `FPBasedResNetBottleneck.set_encoder_precision('f32')`.           */
+/* 1/16 of the bf16 matrix rate; `FPBasedResNetBottleneck.set_encoder_precision('f32')`; also the  */
+/* hyperprior bottlenecks and the input codecs of compression.py (all four transforms there).      */
 /* ------------------------------------------------------------------------------------------ */
 /* x: f32 NCHW [N,C,H,W] -> y: f32 NHWC [N,H,W,Cpad], channels >= C zero, Cpad % 4 == 0. */
 int sc2_nchw_f32_to_nhwc_f32(const float *x, float *y, int N, int C, int H, int W, int Cpad, void *stream);
@@ -296,6 +299,14 @@ int sc2_conv_f32_chunk_channels(int Cout);
  *          FUSED_GDN / FUSED_IGDN (Cout <= 96): the conv followed by GDN1 over its own output in one launch, `ep_x` = the
  *          effective gamma as the w_frag of a 1x1 conv Cout -> Cout (same packing), ep_beta = the effective beta; bit-identical
  *          to the two launches.
+ *          GDN2 / IGDN2 (compressai GDN, the squared form of the input codecs' g_a / g_s; a 1x1 launch with a_op = SQUARE, ep_x =
+ *          the GDN's input, ep_beta = the effective beta): norm = acc + ep_beta[c], r = sqrtf(norm), y = ep_x * (1.0f / r) (GDN2)
+ *          resp. y = ep_x * r (IGDN2) -- a correctly rounded f32 square root, a correctly rounded division and one multiply, no
+ *          reciprocal-square-root approximation.  (Upstream calls torch.rsqrt, which is not bit-defined: its CPU vector path and
+ *          its tail path differ on 0.57 % of random values; 1 / sqrt is reproducible and within an ulp of either.)  They need ep_x
+ *          and ep_beta (SC2_ERR_INVALID_ARG otherwise), write SC2_OUT_F32_NHWC or SC2_OUT_F32_NCHW but not the symbols, and are
+ *          refused with SC2_ERR_UNSUPPORTED together with output scatter.  There is no fused form of them: FUSED_* stays GDN1-only
+ *          (the codecs' N is 128 or 192, above the 96-channel chunk).
  *          BIAS_RELU / BIAS_LEAKY_RELU (the activations of the hyperprior transforms h_a / h_s): on the f32 value v = acc
  *          (+ ep_beta[c]; ep_beta may be NULL: no bias), v > 0 ? v : 0 resp. v > 0 ? v : v * 0.01f -- torch's CPU forms, one f32
  *          multiply; any out_format but the symbols.
@@ -303,7 +314,7 @@ int sc2_conv_f32_chunk_channels(int Cout);
  *          padding formula read implicit zeros) and output pixel (oh, ow) goes to (oh*out_stride_h + out_off_h, ow*out_stride_w +
  *          out_off_w) of y = f32 NHWC [N,out_H,out_W,Cout]; pixels outside it are dropped.  SC2_OUT_F32_NHWC only, with the
  *          epilogues NONE / BIAS / BIAS_RELU / BIAS_LEAKY_RELU: a transposed convolution is one such launch per stride-parity
- *          class (`HipConvTranspose2d.forward_nhwc_precise`).  Scatter with GDN / IGDN / FUSED_*, with another out_format, or a
+ *          class (`HipConvTranspose2d.forward_nhwc_precise`).  Scatter with GDN / IGDN / GDN2 / IGDN2 / FUSED_*, with another out_format, or a
  *          stride_h != stride_w returns SC2_ERR_UNSUPPORTED.
  * x      : f32 NHWC [N,H,W,Cin]; addressed through a 32-bit buffer descriptor: N*H*W*Cin*4 (N*H*W*12 for the NCHW image) must be
  *          below 0x7FF00000 bytes (SC2_ERR_UNSUPPORTED otherwise -- about 445 images of the 96-channel 112 x 112 map; the host side
@@ -311,7 +322,7 @@ int sc2_conv_f32_chunk_channels(int Cout);
  * w_frag : f32, [chunks][steps][NT][64 lanes][4] with cc = sc2_conv_f32_chunk_channels(Cout), NT = cc / 16, chunks =
  *          ceil(Cout / cc), steps = ceil(KH*KW*Cin / 16); entry (ch, s, nt, lane = q*16 + r, j) =
  *          W[ch*cc + nt*16 + r][k = 16 s + 4 q + j], k = (kh*KW + kw)*Cin + ci, zero beyond Cout / K.
- * ep_x   : f32 NHWC [N,OH,OW,Cout] for GDN / IGDN;  ep_beta : f32 [Cout] (beta, bias, or the medians for symbols)
+ * ep_x   : f32 NHWC [N,OH,OW,Cout] for GDN / IGDN / GDN2 / IGDN2;  ep_beta : f32 [Cout] (beta, bias, or the medians for symbols)
  * y      : SC2_OUT_F32_NHWC [N,OH,OW,Cout] / SC2_OUT_F32_NCHW / SC2_OUT_I32_NCHW_SYM (round_half_even(acc - ep_beta[c])). */
 int sc2_conv2d_f32_fwd(const sc2_conv_desc *d, const float *x, const float *w_frag, void *y, const float *ep_x,
                        const float *ep_beta, void *stream);
@@ -328,16 +339,18 @@ int sc2_conv2d_f32_fwd(const sc2_conv_desc *d, const float *x, const float *w_fr
 int sc2_conv_split_chunk_channels(int Cout);
 /* d       : as for sc2_conv2d_f32_fwd, but x is always f32 NHWC (k_order must be 0; Kpad / Cout_pad are ignored): Cin % 4 == 0,
  *           square stride, pad_h / pad_w independent.  a_op: NONE / ABS / SQUARE, applied to the f32 value before the split.
- *           epilogue: NONE, BIAS, BIAS_RELU, BIAS_LEAKY_RELU, GDN, IGDN, FUSED_GDN / FUSED_IGDN (a_op NONE, Cout <= 96 with
- *           ceil(Cout / 16) * 16 == the chunk width), in the operation order of sc2_conv2d_f32_fwd; the fused form is bit-identical
- *           to the two launches.  Output scatter (out_H != 0): exactly as for sc2_conv2d_f32_fwd -- both kernels run one copy of
+ *           epilogue: NONE, BIAS, BIAS_RELU, BIAS_LEAKY_RELU, GDN, IGDN, GDN2, IGDN2, FUSED_GDN / FUSED_IGDN (a_op NONE, Cout <= 96
+ *           with ceil(Cout / 16) * 16 == the chunk width), in the operation order of sc2_conv2d_f32_fwd; the fused form is
+ *           bit-identical to the two launches.  GDN2 / IGDN2: the rules of sc2_conv2d_f32_fwd word for word -- ep_x and ep_beta
+ *           needed, the two f32 output formats but not the symbols, SC2_ERR_UNSUPPORTED with output scatter, no fused form
+ *           (FUSED_* stays GDN1-only), sqrt and division correctly rounded.  Output scatter (out_H != 0): exactly as for sc2_conv2d_f32_fwd -- both kernels run one copy of
  *           the epilogue and of the descriptor rules (csrc/conv_precise.h).
  * n_parts : 2 or 3 (anything else: SC2_ERR_UNSUPPORTED); w_frag and gamma_frag must be packed for the same value.
  * x       : f32 NHWC [N,H,W,Cin], N*H*W*Cin*4 below 0x7FF00000 bytes (SC2_ERR_UNSUPPORTED otherwise)
  * w_frag  : bf16, [chunks][steps][n_parts][NT][64 lanes][8] with cc = sc2_conv_split_chunk_channels(Cout), NT = cc / 16, chunks =
  *           ceil(Cout / cc), steps = ceil(KH*KW*Cin / 32); entry (ch, s, part, nt, lane = q*16 + r, j) = part `part` of
  *           W[ch*cc + nt*16 + r][k = 32 s + 16 (j >> 2) + 4 q + (j & 3)], k = (kh*KW + kw)*Cin + ci, zero beyond Cout / K.
- * ep_x    : f32 NHWC [N,OH,OW,Cout] for GDN / IGDN (NULL otherwise)
+ * ep_x    : f32 NHWC [N,OH,OW,Cout] for GDN / IGDN / GDN2 / IGDN2 (NULL otherwise)
  * gamma_frag : FUSED_* only (NULL otherwise; unlike sc2_conv2d_f32_fwd, gamma does not travel in ep_x): the effective gamma as
  *           the w_frag of a 1x1 conv Cout -> Cout, same packing and n_parts
  * ep_beta : f32 [Cout] (beta, bias, or the medians for symbols)

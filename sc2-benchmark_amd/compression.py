@@ -10,13 +10,17 @@ g_s = 4 x ConvTranspose(k5, s2, p2, output_padding 1, bias) with 3 inverse GDN, 
 Every tensor-sized computation runs in the HIP library: the convolutions / transposed convolutions on the implicit-GEMM
 MFMA kernel (bias in the epilogue), GDN as a 1x1 GEMM on x^2 with rsqrt / sqrt fused in the epilogue, the entropy
 bottleneck and the range coder as in the supervised-compression bottleneck.
+
+`set_encoder_precision('f32' | 'bf16x3' | 'bf16x6')` (or the constructor's `encoder_precision=`) moves every transform of
+`FactorizedPrior`, `ScaleHyperprior` and `MeanScaleHyperprior` to the precise kernels (csrc/conv_f32.hip / conv_split.hip) on
+f32 activations: see `_PrecisionSwitch`.
 """
 import torch
 from torch import nn
 
 from . import hip
 from .entropy import (CompressionModel, EntropyBottleneck, GaussianConditional, GDN, HipConv2d, HipConvTranspose2d,
-                      _raise_on_status, _require_device, get_scale_table, update_registered_buffers)
+                      _raise_on_status, _require_device, get_scale_table, run_hip_transform_precise, update_registered_buffers)
 
 COMPRESSION_MODEL_CLASS_DICT = dict()
 COMPRESSION_MODEL_FUNC_DICT = dict()
@@ -50,16 +54,57 @@ def _run_transform(seq, x_nhwc, last_out_format):
     return h
 
 
+_SPLIT_PARTS = {'bf16x3': 2, 'bf16x6': 3}   # encoder precision -> bf16 parts per operand (csrc/conv_split.hip)
+
+
+class _PrecisionSwitch(object):
+    """`set_encoder_precision` of the input codecs: the four names (and the ValueError) of FPBasedResNetBottleneck's switch."""
+    encoder_precision = 'bf16'
+
+    def set_encoder_precision(self, precision):
+        """'bf16' (default): every transform with bf16 operands and bf16 activations on the implicit-GEMM kernel, as ever.
+        'f32': f32 operands on the f32 matrix cores (csrc/conv_f32.hip); 'bf16x3' / 'bf16x6': f32 activations and weights as
+        sums of two / three bf16 parts on the bf16 matrix cores (csrc/conv_split.hip).
+        As in the hyperprior bottlenecks the mode is a property of the CODEC: g_a decides the y symbols, h_a the z symbols, h_s
+        the CDF-row index of every y symbol (and the means), which the decoder rebuilds from the decoded z.  In the three precise
+        modes g_a, h_a, h_s AND g_s (the reconstruction is what a user of an image codec measures, and upstream's is f32) run on
+        the precise kernels in every path: forward, compress, decompress and FactorizedPrior's stage_front / stage_coder /
+        stage_back.  The squared-form GDN is norm = gamma x^2 + beta, sqrt, one division, one multiply, all correctly rounded
+        (csrc/conv_precise.h).  The hyper-latent, y_hat and the means travel as f32: neither symbols + medians nor symbols +
+        means is bf16-exact.
+        A stream made in one mode is only guaranteed to decode in THAT mode: another mode's h_s may put a scale on the other side
+        of a scale-table boundary, and one wrong index desynchronises the range decoder for the rest of the image.  Set the same
+        mode on both ends."""
+        if precision not in ('bf16', 'f32') + tuple(_SPLIT_PARTS):
+            raise ValueError("encoder precision must be 'bf16', 'f32', 'bf16x3' or 'bf16x6', got {!r}".format(precision))
+        self.encoder_precision = precision
+        return self
+
+    def _precise_ns(self):
+        """None in 'bf16' mode, else the bf16 parts per operand of the precise kernels (0: f32 operands)."""
+        if self.encoder_precision == 'bf16':
+            return None
+        return _SPLIT_PARTS.get(self.encoder_precision, 0)
+
+    def _nhwc(self, t):
+        """f32 NCHW -> the NHWC form this mode's transforms take: bf16, or f32 in the precise modes."""
+        if self._precise_ns() is not None:
+            return hip.nchw_f32_to_nhwc_f32(t.float().contiguous())
+        return hip.nchw_f32_to_nhwc_bf16(t.float().contiguous(), t.shape[1])
+
+
 @register_compression_model_class
-class FactorizedPrior(CompressionModel):
+class FactorizedPrior(_PrecisionSwitch, CompressionModel):
     """Factorized-prior model of Balle et al. 2018 as packaged by CompressAI (`compressai.models.FactorizedPrior`).
 
     :param N: channels of the transforms
     :param M: channels of the latent
+    :param encoder_precision: 'bf16' (default), 'f32', 'bf16x3' or 'bf16x6': `set_encoder_precision`
     """
 
-    def __init__(self, N, M, **kwargs):
+    def __init__(self, N, M, encoder_precision='bf16', **kwargs):
         super().__init__(entropy_bottleneck_channels=M)
+        self.set_encoder_precision(encoder_precision)
         self.g_a = nn.Sequential(
             conv(3, N), GDN(N),
             conv(N, N), GDN(N),
@@ -83,20 +128,28 @@ class FactorizedPrior(CompressionModel):
         return 2 ** 4
 
     # ---- transforms on the device ---------------------------------------------------------------- #
-    def analysis(self, x):
-        """g_a(x): f32 NCHW image batch -> f32 NCHW latent."""
+    def analysis(self, x, slice_bytes=0x7FF00000 - 1):
+        """g_a(x): f32 NCHW image batch -> f32 NCHW latent.  slice_bytes (precise modes): the largest f32 tensor of a launch."""
         _require_device(x, 'FactorizedPrior')
+        ns = self._precise_ns()
+        if ns is not None:      # the image as it is: ns = 0 reads the three planes in place
+            return run_hip_transform_precise(self.g_a, x.float().contiguous(), ns, x_is_nchw_rgb=True, slice_bytes=slice_bytes)
         x_nhwc = hip.nchw_f32_to_nhwc_bf16(x.float().contiguous(), 8)
         return _run_transform(self.g_a, x_nhwc, hip.OUT_F32_NCHW)
 
-    def synthesis_nhwc(self, y_hat_nhwc):
-        """g_s on a bf16 NHWC latent -> f32 NCHW reconstruction."""
+    def synthesis_nhwc(self, y_hat_nhwc, slice_bytes=0x7FF00000 - 1):
+        """g_s on an NHWC latent (bf16; f32 in the precise modes) -> f32 NCHW reconstruction."""
+        ns = self._precise_ns()
+        if ns is not None:
+            if y_hat_nhwc.dtype != torch.float32:
+                raise hip.Sc2Error('synthesis: mode {!r} takes the f32 latent'.format(self.encoder_precision))
+            return run_hip_transform_precise(self.g_s, y_hat_nhwc, ns, slice_bytes=slice_bytes)
         out = _run_transform(self.g_s, y_hat_nhwc, hip.OUT_F32_NHWC)
         return out.permute(0, 3, 1, 2).contiguous()
 
-    def synthesis(self, y_hat):
+    def synthesis(self, y_hat, **kwargs):
         _require_device(y_hat, 'FactorizedPrior')
-        return self.synthesis_nhwc(hip.nchw_f32_to_nhwc_bf16(y_hat.float().contiguous(), y_hat.shape[1]))
+        return self.synthesis_nhwc(self._nhwc(y_hat), **kwargs)
 
     # ---- CompressAI API ---------------------------------------------------------------------------- #
     def forward(self, x):
@@ -112,6 +165,9 @@ class FactorizedPrior(CompressionModel):
 
     def decompress(self, strings, shape):
         assert isinstance(strings, list) and len(strings) == 1
+        if self._precise_ns() is not None:     # symbols + medians is not bf16-exact: y_hat stays f32
+            y_hat = self.entropy_bottleneck.decompress_to_device(strings[0], tuple(shape), want_f32=True, want_nhwc=False)[0]
+            return {'x_hat': self.synthesis(y_hat).clamp_(0, 1)}
         _, y_hat_nhwc = self.entropy_bottleneck.decompress_to_device(strings[0], tuple(shape), want_f32=False, want_nhwc=True)
         x_hat = self.synthesis_nhwc(y_hat_nhwc).clamp_(0, 1)
         return {'x_hat': x_hat}
@@ -127,13 +183,19 @@ class FactorizedPrior(CompressionModel):
         eb = self.entropy_bottleneck
         hw = hw_shape[0] * hw_shape[1]
         buf, off, nb, st = eb.encode_symbols_device(sym, hw)
-        if dequantized:
+        if dequantized and self._precise_ns() is None:      # (the fused pass writes a bf16 y_hat: the precise modes hand on symbols)
             y_hat = eb.decode_dequantize_device(buf, off, nb, sym.shape[1], hw_shape)
             if y_hat is not None:
                 return y_hat, nb, st
         return eb.decode_symbols_device(buf, off, nb, sym.shape[1], hw), nb, st
 
     def stage_back(self, decoded, hw_shape):
+        if self._precise_ns() is not None:
+            if decoded.dtype != torch.int32:
+                raise hip.Sc2Error('stage_back: mode {!r} takes the decoded symbols, not a {} latent'.format(self.encoder_precision,
+                                                                                                             decoded.dtype))
+            y_hat = self.entropy_bottleneck.dequantize_device(decoded, hw_shape, want_f32=True, want_nhwc=False)[0]
+            return self.synthesis(y_hat).clamp_(0, 1)
         y_hat = decoded if decoded.dtype == torch.bfloat16 else self.entropy_bottleneck.dequantize_device(decoded, hw_shape)[1]
         return self.synthesis_nhwc(y_hat).clamp_(0, 1)
 
@@ -226,11 +288,13 @@ def _tag(prefix, seq):
         mod._tag = '{}.{}'.format(prefix, i)
 
 
-class _HyperpriorBase(CompressionModel):
-    """g_a / g_s as in FactorizedPrior, an EntropyBottleneck(N) on z and a GaussianConditional on y."""
+class _HyperpriorBase(_PrecisionSwitch, CompressionModel):
+    """g_a / g_s as in FactorizedPrior, an EntropyBottleneck(N) on z and a GaussianConditional on y.  `encoder_precision`:
+    'bf16' (default), 'f32', 'bf16x3' or 'bf16x6' (`set_encoder_precision`)."""
 
-    def __init__(self, N, M, **kwargs):
+    def __init__(self, N, M, encoder_precision='bf16', **kwargs):
         super().__init__(entropy_bottleneck_channels=N)
+        self.set_encoder_precision(encoder_precision)
         self.g_a = nn.Sequential(conv(3, N), GDN(N), conv(N, N), GDN(N), conv(N, N), GDN(N), conv(N, M))
         self.g_s = nn.Sequential(deconv(M, N), GDN(N, inverse=True), deconv(N, N), GDN(N, inverse=True),
                                  deconv(N, N), GDN(N, inverse=True), deconv(N, 3))
@@ -252,13 +316,24 @@ class _HyperpriorBase(CompressionModel):
 
     def hyper_analysis(self, y):
         """h_a(|y|) (scale hyperprior) or h_a(y): f32 NCHW y -> f32 NCHW z."""
-        y_nhwc = hip.nchw_f32_to_nhwc_bf16(y.float().contiguous(), y.shape[1])
-        return _run_biased(self.h_a, y_nhwc, a_op=hip.AOP_ABS if self._hyper_abs else hip.AOP_NONE)
+        a_op = hip.AOP_ABS if self._hyper_abs else hip.AOP_NONE
+        ns = self._precise_ns()
+        if ns is not None:
+            return run_hip_transform_precise(self.h_a, self._nhwc(y), ns, a_op=a_op)
+        return _run_biased(self.h_a, self._nhwc(y), a_op=a_op)
 
     def hyper_synthesis(self, z_hat_nhwc, out_format=hip.OUT_F32_NCHW):
+        """h_s on an NHWC hyper-latent (bf16; f32 in the precise modes) -> the Gaussian parameters."""
+        ns = self._precise_ns()
+        if ns is not None:
+            if z_hat_nhwc.dtype != torch.float32:
+                raise hip.Sc2Error('hyper_synthesis: mode {!r} takes the f32 hyper-latent'.format(self.encoder_precision))
+            return run_hip_transform_precise(self.h_s, z_hat_nhwc, ns, out_format=out_format)
         return _run_biased(self.h_s, z_hat_nhwc, last_out_format=out_format)
 
     def _z_hat_nhwc(self, z_strings, shape):
+        if self._precise_ns() is not None:      # symbols + medians is not bf16-exact: the hyper-latent stays f32
+            return self._nhwc(self.entropy_bottleneck.decompress_to_device(z_strings, tuple(shape), want_f32=True, want_nhwc=False)[0])
         return self.entropy_bottleneck.decompress_to_device(z_strings, tuple(shape), want_f32=False, want_nhwc=True)[1]
 
     def update(self, scale_table=None, force=False, update_quantiles=False):
@@ -289,7 +364,7 @@ class _HyperpriorBase(CompressionModel):
         y = self.analysis(x)
         z = self.hyper_analysis(y)
         z_hat, z_likelihoods = self.entropy_bottleneck(z)
-        scales_hat, means_hat = self._gaussian(self.hyper_synthesis(hip.nchw_f32_to_nhwc_bf16(z_hat.contiguous(), self.N)))
+        scales_hat, means_hat = self._gaussian(self.hyper_synthesis(self._nhwc(z_hat)))
         y_hat, y_likelihoods = self.gaussian_conditional(y, scales_hat, means=means_hat)
         x_hat = self.synthesis(y_hat)
         return {'x_hat': x_hat, 'likelihoods': {'y': y_likelihoods, 'z': z_likelihoods}}
@@ -307,6 +382,10 @@ class _HyperpriorBase(CompressionModel):
         assert isinstance(strings, list) and len(strings) == 2
         scales_hat, means_hat = self._gaussian(self.hyper_synthesis(self._z_hat_nhwc(strings[1], shape)))
         indexes = self.gaussian_conditional.build_indexes(scales_hat)
+        if self._precise_ns() is not None:     # symbols + means is not bf16-exact: y_hat stays f32
+            y_hat = self.gaussian_conditional.decompress_to_device(strings[0], indexes, means_hat, want_f32=True,
+                                                                   want_nhwc=False)[0]
+            return {'x_hat': self.synthesis(y_hat).clamp_(0, 1)}
         y_hat_nhwc = self.gaussian_conditional.decompress_to_device(strings[0], indexes, means_hat, want_f32=False,
                                                                     want_nhwc=True)[1]
         return {'x_hat': self.synthesis_nhwc(y_hat_nhwc).clamp_(0, 1)}
@@ -391,7 +470,18 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
     image, the y stream of an image = ONE rANS stream of its symbols in pixel-major, channel-minor order with per-symbol
     Gaussian indexes.  The hyper-params half of the first entropy_parameters layer runs for all pixels before the scan, in
     both directions.  Channel counts that are not multiples of 8 (10M/3, 8M/3 at M = 320) are zero-padded in the packed
-    weights and activations."""
+    weights and activations.
+
+    Only 'bf16': the context scan has bf16 operands, and a codec precise in g_a / h_a / h_s alone would promise bytes it cannot
+    keep.  `set_encoder_precision` with any other mode raises Sc2Error."""
+
+    def set_encoder_precision(self, precision):
+        super().set_encoder_precision(precision)     # (an unknown name: ValueError)
+        if precision != 'bf16':
+            self.encoder_precision = 'bf16'
+            raise hip.Sc2Error('JointAutoregressiveHierarchicalPriors: encoder precision {!r} is not supported -- the context scan '
+                               '(csrc/ar_context.hip) has bf16 operands; only \'bf16\''.format(precision))
+        return self
 
     def __init__(self, N=192, M=192, **kwargs):
         super().__init__(N, M, **kwargs)

@@ -6,6 +6,14 @@
 // The epilogue decides the bytes a user gets -- the reference's operation order (norm = beta + acc, IEEE division, one multiply:
 // compressai.layers.GDN1.forward) and the symbol rounding rintf(acc - median) -- so the modes 'f32', 'bf16x3' and 'bf16x6' code
 // the same stream from equal accumulators because they run this one copy of it.
+//
+// The squared-form GDN of the input codecs (compressai.layers.GDN: SC2_EPI_GDN2 / SC2_EPI_IGDN2, a 1x1 launch with a_op = SQUARE,
+// ep_x = the GDN's input, ep_beta = the effective beta) is norm = acc + beta[c], r = sqrtf(norm), then y = ep_x * r (IGDN2) or
+// y = ep_x * (1.0f / r) (GDN2): a correctly rounded square root, a correctly rounded division and one multiply -- never a
+// reciprocal-square-root instruction or intrinsic, and no fast-math flag on the files that include this.  Why 1 / sqrt and not the
+// reference's torch.rsqrt: the reference's rsqrt is not bit-defined.  On the CPU (torch 2.10, 4 M random values in (0, 100))
+// torch.rsqrt(x) differs from 1 / torch.sqrt(x) on 0.57 % of the values, and agrees on short tensors, which take the vectoriser's
+// tail path.  So there is no bit target; the device takes the form that is reproducible and within an ulp of either CPU path.
 #pragma once
 
 #include "sc2_common.h"
@@ -72,7 +80,7 @@ __device__ __forceinline__ void precise_rows(const PreciseArgs &p, long long m_b
 // (pixel m_base + mt * 16 + r, channel (chunk * NT + nt) * 16 + 4 q + i) -- a lane holds FOUR CONSECUTIVE CHANNELS of one
 // pixel: one 16-byte access per tile for NHWC tensors (ep_x, y), and for NCHW outputs the 16 lanes of a quarter write 16
 // consecutive pixels of a channel plane.  nrm: the fused GDN's gamma |acc| sums in the same layout (FUSED only).
-// Output scatter (o_H != 0; f32 NHWC, plain / bias / activation epilogues only: the host refuses the rest): the pixel's row of
+// Output scatter (o_H != 0; f32 NHWC, plain / bias / activation epilogues only: the host refuses the rest, GDN2 / IGDN2 included): the pixel's row of
 // y is that of its place in [N, o_H, o_W, Cout]; a pixel outside that tensor is dropped.
 template <int MT, int NT, bool FUSED>
 __device__ __forceinline__ void precise_epilogue(const PreciseArgs &p, const f32x4_t (&acc)[MT][NT],
@@ -117,7 +125,9 @@ __device__ __forceinline__ void precise_epilogue(const PreciseArgs &p, const f32
                     if (p.epilogue == SC2_EPI_FUSED_GDN) norm = 1.0f / norm;
                     v[i] = v[i] * norm;
                 }
-            } else if (p.epilogue == SC2_EPI_GDN || p.epilogue == SC2_EPI_IGDN) {
+            } else if (p.epilogue == SC2_EPI_GDN || p.epilogue == SC2_EPI_IGDN || p.epilogue == SC2_EPI_GDN2 || p.epilogue == SC2_EPI_IGDN2) {
+                const bool squared = p.epilogue == SC2_EPI_GDN2 || p.epilogue == SC2_EPI_IGDN2;
+                const bool divide = p.epilogue == SC2_EPI_GDN || p.epilogue == SC2_EPI_GDN2;
                 float xv[4];
                 if (vec4) {
                     const f32x4_t t = *reinterpret_cast<const f32x4_t *>(p.ep_x + m * p.Cout + c0);
@@ -128,8 +138,9 @@ __device__ __forceinline__ void precise_epilogue(const PreciseArgs &p, const f32
                 }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    float norm = v[i] + bc[i];                 // conv2d(|x|, gamma, beta): the bias joins the finished sum
-                    if (p.epilogue == SC2_EPI_GDN) norm = 1.0f / norm;   // IEEE division, then one multiply, as GDN1.forward
+                    float norm = v[i] + bc[i];                 // conv2d(|x| or x^2, gamma, beta): the bias joins the finished sum
+                    if (squared) norm = sqrtf(norm);           // correctly rounded (see the header comment: no rsqrt)
+                    if (divide) norm = 1.0f / norm;            // IEEE division, then one multiply, as GDN1.forward
                     v[i] = xv[i] * norm;
                 }
             } else if (p.epilogue == SC2_EPI_BIAS) {
@@ -202,7 +213,8 @@ inline int precise_check_desc(const char *who, const sc2_conv_desc *d, const voi
     SC2_REQUIRE(d->a_op == SC2_AOP_NONE || d->a_op == SC2_AOP_ABS || d->a_op == SC2_AOP_SQUARE, SC2_ERR_INVALID_ARG, "%s: a_op", who);
     const bool fused = d->epilogue == SC2_EPI_FUSED_GDN || d->epilogue == SC2_EPI_FUSED_IGDN;
     const bool act = d->epilogue == SC2_EPI_BIAS_RELU || d->epilogue == SC2_EPI_BIAS_LEAKY_RELU;   // (ep_beta may be null: no bias)
-    SC2_REQUIRE(d->epilogue == SC2_EPI_NONE || d->epilogue == SC2_EPI_GDN || d->epilogue == SC2_EPI_IGDN || d->epilogue == SC2_EPI_BIAS || act || fused,
+    const bool gdn = d->epilogue == SC2_EPI_GDN || d->epilogue == SC2_EPI_IGDN || d->epilogue == SC2_EPI_GDN2 || d->epilogue == SC2_EPI_IGDN2;
+    SC2_REQUIRE(d->epilogue == SC2_EPI_NONE || gdn || d->epilogue == SC2_EPI_BIAS || act || fused,
                 SC2_ERR_UNSUPPORTED, "%s: epilogue %d", who, d->epilogue);
     SC2_REQUIRE(!act || d->out_format != SC2_OUT_I32_NCHW_SYM, SC2_ERR_INVALID_ARG,
                 "%s: symbols come straight from the accumulators (epilogue NONE)", who);
@@ -215,7 +227,6 @@ inline int precise_check_desc(const char *who, const sc2_conv_desc *d, const voi
                 who, d->Cout, precise_chunk_channels(d->Cout));
     SC2_REQUIRE(d->out_format == SC2_OUT_F32_NHWC || d->out_format == SC2_OUT_F32_NCHW || d->out_format == SC2_OUT_I32_NCHW_SYM,
                 SC2_ERR_UNSUPPORTED, "%s: out_format %d", who, d->out_format);
-    const bool gdn = d->epilogue == SC2_EPI_GDN || d->epilogue == SC2_EPI_IGDN;
     SC2_REQUIRE(!gdn || (ep_x && ep_beta), SC2_ERR_INVALID_ARG, "%s: GDN epilogue needs ep_x and ep_beta", who);
     SC2_REQUIRE((d->epilogue != SC2_EPI_BIAS && d->out_format != SC2_OUT_I32_NCHW_SYM) || ep_beta, SC2_ERR_INVALID_ARG,
                 "%s: ep_beta (bias / medians) missing", who);

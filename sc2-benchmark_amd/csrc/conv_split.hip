@@ -305,7 +305,7 @@ extern "C" int sc2_conv2d_split_fwd(const sc2_conv_desc *d, int n_parts, const f
     if (const int rc = precise_check_desc("conv2d_split", d, ep_x, gamma_frag, ep_beta)) return rc;
     SC2_REQUIRE(d->k_order == 0, SC2_ERR_UNSUPPORTED, "conv2d_split: f32 NHWC input only");
     const bool fused = d->epilogue == SC2_EPI_FUSED_GDN || d->epilogue == SC2_EPI_FUSED_IGDN;
-    const bool gdn = d->epilogue == SC2_EPI_GDN || d->epilogue == SC2_EPI_IGDN;
+    const bool gdn = d->epilogue == SC2_EPI_GDN || d->epilogue == SC2_EPI_IGDN || d->epilogue == SC2_EPI_GDN2 || d->epilogue == SC2_EPI_IGDN2;
     SC2_REQUIRE(!fused || d->a_op == SC2_AOP_NONE, SC2_ERR_UNSUPPORTED, "conv2d_split: the fused GDN takes a_op NONE");
     const int cc = sc2_conv_split_chunk_channels(d->Cout);
     SplitArgs a;

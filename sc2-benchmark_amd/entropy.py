@@ -95,12 +95,15 @@ def _raise_on_status(st, what):
         raise hip.Sc2Error('{}: rANS stream overflowed its maximum size'.format(what))
 
 
-def _precise_cached(mod, ns, make):
-    """make(pack) for the packer of `ns` parts (0: f32), cached on `mod` per (version of its weight, ns)."""
+def _precise_cached(mod, ns, make, params=None):
+    """make(pack) for the packer of `ns` parts (0: f32), cached on `mod` per (version of its weight -- or of `params` --, ns)."""
     if ns not in (0, 2, 3):
         raise hip.Sc2Error('precise kernels: ns must be 0 (f32), 2 or 3 (bf16 parts), got {!r}'.format(ns))
-    w = mod.weight
-    key = (w._version, w.device, w.data_ptr())
+    if params is None:
+        w = mod.weight
+        key = (w._version, w.device, w.data_ptr())
+    else:
+        key = tuple((q._version, q.device, q.data_ptr()) for q in params)
     cache = mod.__dict__.setdefault('_precise_cache', {})
     if cache.get('key') != key:
         cache.clear()
@@ -368,6 +371,96 @@ def run_hip_sequence_precise(seq, x_nhwc, ns=0, a_op=hip.AOP_NONE):
     return h
 
 
+def _precise_geometry(mods, shape):
+    """The f32 NHWC maps (N, H, W, C) an nn.Sequential of HipConv2d / HipConvTranspose2d (+ modules that keep the shape) makes of
+    an input of `shape`, the input included."""
+    N, H, W, C = shape
+    maps = [(N, H, W, C)]
+    for m in mods:
+        if isinstance(m, HipConvTranspose2d):
+            H = (H - 1) * m.stride[0] - 2 * m.padding[0] + m.kernel_size[0] + m.output_padding[0]
+            W = (W - 1) * m.stride[1] - 2 * m.padding[1] + m.kernel_size[1] + m.output_padding[1]
+            C = m.out_channels
+        elif isinstance(m, HipConv2d):
+            H = (H + 2 * m.padding[0] - m.kernel_size[0]) // m.stride[0] + 1
+            W = (W + 2 * m.padding[1] - m.kernel_size[1]) // m.stride[1] + 1
+            C = m.out_channels
+        maps.append((N, H, W, C))
+    return maps
+
+
+def run_hip_transform_precise(seq, x, ns=0, a_op=hip.AOP_NONE, out_format=hip.OUT_F32_NCHW, x_is_nchw_rgb=False,
+                              slice_bytes=0x7FF00000 - 1):
+    """A whole transform of the input codecs (g_a / g_s / h_a / h_s of compression.py) on the precise kernels: an nn.Sequential
+    of HipConv2d / HipConvTranspose2d (biased or not), GDN / GDN1, ReLU and LeakyReLU(0.01) on f32 NHWC activations, ns = 0 on
+    csrc/conv_f32.hip, 2 / 3 on csrc/conv_split.hip.  An activation rides in the epilogue of the layer before it, a bias in its
+    layer's; a GDN is one 1x1 launch.  x: f32 [N,H,W,C] (C % 4 == 0), or with x_is_nchw_rgb the f32 NCHW image [N,3,H,W] itself
+    (ns = 0 reads the three planes in place, the split modes go through a 4-channel NHWC copy).  `a_op` applies to the first
+    layer's input.  The last layer writes `out_format` (OUT_F32_NCHW / OUT_F32_NHWC).  Every f32 tensor of a launch stays at or
+    below `slice_bytes` (the kernels address below 0x7FF00000 bytes): a larger batch runs as slices of the batch, sized from the
+    widest map of the transform.  Anything else raises Sc2Error: nothing here falls back to the bf16 kernels."""
+    _require_device(x, 'run_hip_transform_precise')
+    mods = list(seq)
+    if out_format not in (hip.OUT_F32_NCHW, hip.OUT_F32_NHWC):
+        raise hip.Sc2Error('precise transform: out_format {} (f32 NCHW or f32 NHWC)'.format(out_format))
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise hip.Sc2Error('precise transform: the input must be a 4-d f32 tensor, got {} {}'.format(tuple(x.shape), x.dtype))
+    if x_is_nchw_rgb and (x.shape[1] != 3 or not mods or not isinstance(mods[0], HipConv2d) or mods[0].in_channels != 3):
+        raise hip.Sc2Error('precise transform: the NCHW image form needs a 3-channel image into a 3-channel convolution')
+    x = x.contiguous()
+    N = x.shape[0]
+    shape = (N, x.shape[2], x.shape[3], 4) if x_is_nchw_rgb else tuple(x.shape)
+    per_image = 4 * max(h * w * c for _, h, w, c in _precise_geometry(mods, shape))
+    n_max = max(1, int(slice_bytes) // per_image)
+    if N > n_max:
+        return torch.cat([run_hip_transform_precise(mods, x[i:i + n_max], ns, a_op, out_format, x_is_nchw_rgb, slice_bytes)
+                          for i in range(0, N, n_max)])
+    conv = _precise_conv(ns)
+    sfx = '.bf16x{}'.format(3 * (ns - 1)) if ns else '.f32'
+    h = x
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        nxt = mods[i + 1] if i + 1 < len(mods) else None
+        first_a_op = a_op if i == 0 else hip.AOP_NONE
+        if isinstance(m, GDN1):
+            if first_a_op != hip.AOP_NONE:
+                raise hip.Sc2Error('precise transform: an input operand on a GDN')
+            last = i + 1 >= len(mods)
+            h = m.forward_nhwc_precise(h, ns, out_format=out_format if last else hip.OUT_F32_NHWC)
+            i += 1
+            continue
+        if not isinstance(m, (HipConv2d, HipConvTranspose2d)) or m.groups != 1 or m.dilation != (1, 1):
+            raise hip.Sc2Error('precise transform: unsupported module {}'.format(m))
+        epi = hip.EPI_NONE
+        if isinstance(nxt, nn.ReLU):
+            epi = hip.EPI_BIAS_RELU
+        elif isinstance(nxt, nn.LeakyReLU):
+            if nxt.negative_slope != 0.01:
+                raise hip.Sc2Error('precise transform: LeakyReLU slope {} (the kernels fuse 0.01)'.format(nxt.negative_slope))
+            epi = hip.EPI_BIAS_LEAKY_RELU
+        step = 2 if epi != hip.EPI_NONE else 1
+        last = i + step >= len(mods)
+        rgb = i == 0 and x_is_nchw_rgb
+        if not rgb and (h.shape[-1] != m.in_channels or m.in_channels % 4):
+            raise hip.Sc2Error('precise transform: {} channels into {} (channel counts must be multiples of 4)'.format(h.shape[-1], m))
+        if isinstance(m, HipConv2d):
+            if m.stride[0] != m.stride[1]:
+                raise hip.Sc2Error('precise transform: unsupported module {}'.format(m))
+            bias = m.bias_f32()
+            if bias is not None and epi == hip.EPI_NONE:
+                epi = hip.EPI_BIAS
+            h = conv(h, m.precise_weight(ns), m.out_channels, m.kernel_size[0], m.kernel_size[1], m.stride[0], tuple(m.padding),
+                     a_op=first_a_op, epilogue=epi, ep_beta=bias, out_format=out_format if last else hip.OUT_F32_NHWC,
+                     tag=(getattr(m, '_tag', None) or 'conv') + sfx, cin_real=m.in_channels, x_is_nchw_rgb=rgb)
+        else:
+            h = m.forward_nhwc_precise(h, ns, epi, a_op=first_a_op)
+            if last and out_format == hip.OUT_F32_NCHW:
+                h = h.permute(0, 3, 1, 2).contiguous()
+        i += step
+    return h
+
+
 class GDN1(nn.Module):
     """Simplified generalized divisive normalisation: y = x / (beta + gamma |x|); inverse: x * (...).
 
@@ -413,6 +506,27 @@ class GDN1(nn.Module):
             self._frag_key = key
         return self._frag
 
+    _precise_ops = (hip.AOP_ABS, hip.EPI_GDN, hip.EPI_IGDN)      # operand, epilogue, inverse epilogue of the precise 1x1 launch
+
+    def forward_nhwc_precise(self, x_f32_nhwc, ns=0, out_format=hip.OUT_F32_NHWC):
+        """The normalisation on the precise kernels: x f32 [N,H,W,C] (C % 4 == 0) -> f32 NHWC or NCHW.  ns = 0: f32 operands
+        (csrc/conv_f32.hip); 2 / 3: bf16 parts (csrc/conv_split.hip).  One 1x1 launch on |x| (GDN1) or x^2 (GDN) with the
+        effective gamma, packed once per (parameter version, ns); the epilogue adds the effective beta to the finished sum and,
+        for the squared form, takes a correctly rounded sqrt, then divides (or multiplies, inverse) -- csrc/conv_precise.h."""
+        _require_device(x_f32_nhwc, type(self).__name__)
+        C = self.in_channels
+        if x_f32_nhwc.dim() != 4 or x_f32_nhwc.shape[-1] != C or C % 4 or x_f32_nhwc.dtype != torch.float32:
+            raise hip.Sc2Error('{} (precise): f32 NHWC input of {} channels (a multiple of 4) expected, got {} {}'.format(
+                type(self).__name__, C, tuple(x_f32_nhwc.shape), x_f32_nhwc.dtype))
+        gamma, beta = _precise_cached(self, ns, lambda pack: (pack(self.gamma_reparam(self.gamma).float().reshape(C, C, 1, 1)),
+                                                              self.beta_reparam(self.beta).float().contiguous()),
+                                      params=(self.gamma, self.beta))
+        a_op, epi, epi_inv = self._precise_ops
+        x = x_f32_nhwc.contiguous()
+        return _precise_conv(ns)(x, gamma, C, 1, 1, 1, 0, a_op=a_op, epilogue=epi_inv if self.inverse else epi, ep_x=x,
+                                 ep_beta=beta, out_format=out_format,
+                                 tag=(getattr(self, '_tag', None) or 'gdn') + ('.bf16x{}'.format(3 * (ns - 1)) if ns else '.f32'))
+
     def forward_nhwc(self, x_nhwc, out_format=hip.OUT_BF16_NHWC):
         beta, gamma_packed = self.effective()
         return hip.conv2d_fwd(x_nhwc, gamma_packed, self.in_channels, 1, 1, 1, 0, a_op=hip.AOP_ABS,
@@ -432,6 +546,8 @@ class GDN(GDN1):
     of `bmshj2018_factorized`, which the reference builds at sc2bench/models/registry.py:73-80 for the neural input
     compression configs).  gamma x^2 is a 1x1 implicit GEMM on the matrix cores with the square applied to the
     operand fragments and rsqrt / sqrt fused in the epilogue."""
+
+    _precise_ops = (hip.AOP_SQUARE, hip.EPI_GDN2, hip.EPI_IGDN2)
 
     def forward_nhwc(self, x_nhwc, out_format=hip.OUT_BF16_NHWC):
         beta, gamma_packed = self.effective()

@@ -1,6 +1,6 @@
 """The four encoder precisions side by side on one box, in one process: the bench model at bs 256, 224 x 224.
 
-    python tools/encoder_modes.py [--rounds 3] [--reps 5] [--launches] [--model fp | mshp | shp]
+    python tools/encoder_modes.py [--rounds 3] [--reps 5] [--launches] [--model fp | mshp | shp | factorized | hyperprior | mean]
 
 The modes ('bf16', 'f32', 'bf16x3', 'bf16x6') are ALTERNATED for --rounds rounds, so that clock and thermal drift fall on all of
 them alike.  Per mode: the `stage_front` time per batch of every round (HIP events, as bench.py's precision_check), the symbol
@@ -9,6 +9,10 @@ the streams the device codes from them.  --launches adds the per-launch times of
 --model mshp | shp: the hyperprior bottlenecks instead (the mshp224 model of benchlib.workloads, or its scale-hyperprior twin),
 where the mode is a property of the codec (g_a, h_a and h_s): `stage_front` ms per batch, and against the oracle's f32 CPU chain
 the mismatch rates of z symbols, indexes and y symbols and the number of images with all three equal.
+--model factorized | hyperprior | mean: the neural input compression models of compression.py (FactorizedPrior, ScaleHyperprior,
+MeanScaleHyperprior at N = 128, M = 192, the operating point of tests/ref_split_input.py) on 128 x 192 images, where the mode covers
+g_a, h_a, h_s and g_s: ms per batch of `stage_front` (factorized) or `compress` (the hyperprior models: both transforms, the hyper
+transforms and the coders) and of `decompress`, and the same mismatch table against the oracle's f32 CPU chain on the first 8 images.
 Prints one JSON line."""
 import argparse
 import json
@@ -107,16 +111,104 @@ def main_hyper(args, dev):
     print(json.dumps(out))
 
 
+INPUT_MODELS = {'factorized': 'FactorizedPrior', 'hyperprior': 'ScaleHyperprior', 'mean': 'MeanScaleHyperprior'}
+
+
+def _timed_rounds(fn, set_mode, args, dev):
+    """ms per call of fn() per round, the modes alternated: -> {mode: [ms, ...]}"""
+    ms = {mode: [] for mode in MODES}
+    for _ in range(args.rounds):
+        for mode in MODES:
+            set_mode(mode)
+            fn()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.reps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize(dev)
+            ms[mode].append(round(e0.elapsed_time(e1) / args.reps, 4))
+    return ms
+
+
+def main_input(args, dev):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+    import ref_split_input as ri
+    import sc2bench_amd as S
+    name = INPUT_MODELS[args.model]
+    ref = ri.build(name)
+    m = S.COMPRESSION_MODEL_CLASS_DICT[name](ri.N_CH, ri.M_CH)
+    m.load_state_dict({k: v.clone() for k, v in ref.state_dict().items()})
+    m.eval().to(dev)
+    hyper = ri.has_hyper(ref)
+    n = min(8, args.batch)
+    xc = torch.rand(args.batch, 3, 128, 192, generator=torch.Generator().manual_seed(1234))
+    x = xc.to(dev)
+    want = [t.reshape(n, -1) for t in ri.int_tensors(ri.stages(ref, xc[:n], 'f32'))]
+    front = 'compress' if hyper else 'stage_front'
+    out = {'what': '{}: codec precisions alternated in one process: {} and decompress ms per batch per round; the integer tensors of the '
+                   'first {} images against the oracle\'s f32 CPU chain'.format(name, front, n), 'model': args.model, 'batch': args.batch,
+           'image': [128, 192], 'images_checked': n, 'rounds': args.rounds, 'reps_per_interval': args.reps,
+           'device': torch.cuda.get_device_name(dev), 'modes': {}}
+    enc = {}
+    with torch.no_grad():
+        for mode in MODES:
+            m.set_encoder_precision(mode)
+            y = m.analysis(x[:n])
+            if hyper:
+                gc = m.gaussian_conditional
+                e = m.compress(x[:n])
+                scales, means = m._gaussian(m.hyper_synthesis(m._z_hat_nhwc(e['strings'][1], e['shape'])))
+                got = (m.entropy_bottleneck.symbols_device(m.hyper_analysis(y)), gc.build_indexes(scales), gc.quantize(y, 'symbols', means))
+                names = ('z_symbol', 'index', 'y_symbol')
+            else:
+                got, names = (m.entropy_bottleneck.symbols_device(y),), ('y_symbol',)
+            diff = [a.cpu().int().reshape(n, -1) != b for a, b in zip(got, want)]
+            same = ~torch.stack([d.any(dim=1) for d in diff]).any(dim=0)
+            out['modes'][mode] = {'{}_mismatch_rate'.format(k): d.float().mean().item() for k, d in zip(names, diff)}
+            out['modes'][mode]['images_with_all_identical'] = int(same.sum().item())
+            enc[mode] = m.compress(x)          # packs the weights, warms the allocator; decompress decodes its own mode's streams
+            m.decompress(**enc[mode])
+        torch.cuda.synchronize(dev)
+        mode_now = []
+
+        def set_mode(mode):
+            m.set_encoder_precision(mode)
+            mode_now[:] = [mode]
+
+        for key, fn in (('{}_ms_per_batch'.format(front), (lambda: m.compress(x)) if hyper else (lambda: m.stage_front(x))),
+                        ('decompress_ms_per_batch', lambda: m.decompress(**enc[mode_now[0]]))):
+            for mode, ms in _timed_rounds(fn, set_mode, args, dev).items():
+                out['modes'][mode][key] = ms
+        if args.launches:
+            for mode in MODES:
+                set_mode(mode)
+                torch.cuda.synchronize(dev)
+                with hip.KernelTimer() as kt:
+                    m.decompress(**m.compress(x))
+                    torch.cuda.synchronize(dev)
+                out['modes'][mode]['launch_ms'] = {k: round(ms, 4) for k, (_, ms) in sorted(kt.summary().items())}
+    m.set_encoder_precision('bf16')
+    for key in ('{}_ms_per_batch'.format(front), 'decompress_ms_per_batch'):
+        base = out['modes']['bf16'][key]
+        for mode in MODES[1:]:
+            out['modes'][mode][key.replace('_ms_per_batch', '_over_bf16_per_round')] = [round(a / b, 3) for a, b in zip(out['modes'][mode][key], base)]
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--reps', type=int, default=5, help='stage_front calls per timed interval')
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--launches', action='store_true')
-    ap.add_argument('--model', choices=('fp', 'mshp', 'shp'), default='fp', help='fp: the bench model (default); mshp / shp: the hyperprior bottlenecks')
+    ap.add_argument('--model', choices=('fp', 'mshp', 'shp') + tuple(INPUT_MODELS), default='fp',
+                    help='fp: the bench model (default); mshp / shp: the hyperprior bottlenecks; factorized / hyperprior / mean: the input codecs')
     args = ap.parse_args()
     assert args.rounds >= 3
     dev = torch.device('cuda:0')
+    if args.model in INPUT_MODELS:
+        return main_input(args, dev)
     if args.model != 'fp':
         return main_hyper(args, dev)
     model = bench.build_model(dev)
