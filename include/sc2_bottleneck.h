@@ -725,7 +725,8 @@ int sc2_rans_decode_host(const sc2_rans_host_tables *tables, const uint8_t *in, 
  * Decoder: stream b at buf[b*stride + io_offset[b] ..+ io_nbytes[b]) (io_offset % 4 == 0); its rANS state and read position
  * live in st_x / st_pos between calls (initialised when pix0 == 0), so a scan may be split into pixel ranges.  status[b]:
  * bit 3 = a corrupt or truncated stream (no word outside the stream is read), bit 4 = the stream did not end where the last
- * pixel ended (state != 2^31 or words left over).  All M <= 512, 2M and C1p / C2p <= 1280. */
+ * pixel ended (state != 2^31 or words left over).  All M <= 512, 2M and C1p / C2p <= 1280.  The decoder keeps the CDF rows in
+ * LDS when they fit beside the step's vectors and searches them in device memory otherwise (same symbols either way). */
 typedef struct sc2_ar_scan_args {
     int32_t B, H, W, M, C1p, C2p;
     int32_t n_table, n_cdfs, cdf_stride, pix0, pix1, decode;
@@ -748,7 +749,8 @@ typedef struct sc2_ar_scan_args {
 int sc2_ar_scan(const sc2_ar_scan_args *args, void *stream);
 /* Resumable rANS decoder (the scan's decoder as a kernel of its own): decodes n_sym symbols per stream with explicit per-symbol
  * indexes [n_streams][n_sym], continuing from st_x / st_pos / status unless `first` (then it starts at the stream's first word).
- * `last`: also check that the stream ends here (status bit 4).  Same stream layout and status bits as sc2_ar_scan. */
+ * `last`: also check that the stream ends here (status bit 4).  Same stream layout and status bits as sc2_ar_scan, and bit 2 = an
+ * index outside [0, n_cdfs) (row 0 is decoded in its place); bits 2 and 3 set by one call stay set in the calls that continue it. */
 int sc2_rans_decode_resume(const uint8_t *buf, int64_t stride, const int32_t *io_offset, const int32_t *io_nbytes,
                            const int32_t *indexes, int n_streams, int64_t n_sym, const int32_t *cdfs, int n_cdfs,
                            int cdf_stride, const int32_t *cdf_sizes, const int32_t *offsets, int first, int last,

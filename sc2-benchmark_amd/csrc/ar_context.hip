@@ -17,6 +17,7 @@
 // Decoder: CompressAI's RansDecoder.decode_stream semantics (64-bit state, 32-bit words, 16-bit precision, 4-bit bypass
 // escapes), the search over the CDF row as an upper bound (identical in result to upstream's linear find_if over a strictly
 // increasing row).  The Gaussian table's rows are packed into LDS as u16 (the closing 65536 is implied by the row's end).
+// A table too long for LDS beside the step's vectors (a scale table reaching into the thousands) is searched in device memory.
 // State and read position are loaded from / stored to device memory at the ends of the pixel range: a scan may be split.
 // No word outside a stream's bytes is ever read (zeros are supplied past its end and the stream is flagged).
 #include <math.h>
@@ -32,6 +33,7 @@ constexpr int kPrecision = 16;
 constexpr int kBypassPrecision = 4;
 constexpr int kMaxBypassVal = (1 << kBypassPrecision) - 1;
 constexpr unsigned long long kRansL = 1ull << 31;
+constexpr int kStatusIndex = 4;    // a CDF-row index outside the table (the resumable decoder's explicit indexes)
 constexpr int kStatusCorrupt = 8;  // as rans.hip
 constexpr int kStatusTail = 16;
 constexpr int kMaxEscapeNibbles = 8;
@@ -92,7 +94,7 @@ __device__ __forceinline__ int ar_dec_symbol(ArDec &d, int size, int offset, Ent
         if (v > cum_freq) hi = mid; else lo = mid + 1;
     }
     int sidx = lo - 1;
-    if (sidx < 0) { sidx = 0; d.corrupt = kStatusCorrupt; }   // entry(0) != 0: not a table the encoder could have used
+    if (sidx < 0) { sidx = 0; d.corrupt |= kStatusCorrupt; }   // entry(0) != 0: not a table the encoder could have used
     const unsigned start = entry(sidx);
     const unsigned end = sidx + 1 >= size - 1 ? 65536u : entry(sidx + 1);
     const unsigned freq = end - start;
@@ -102,7 +104,7 @@ __device__ __forceinline__ int ar_dec_symbol(ArDec &d, int size, int offset, Ent
     if (value == max_value) {
         const int n_bypass = (int)ar_dec_get_bits(d);
         if (n_bypass > kMaxEscapeNibbles) {
-            d.corrupt = kStatusCorrupt;
+            d.corrupt |= kStatusCorrupt;
         } else {
             unsigned raw = 0;
             for (int j = 0; j < n_bypass; ++j) raw |= ar_dec_get_bits(d) << (j * kBypassPrecision);
@@ -186,7 +188,8 @@ __host__ __device__ inline LdsLayout ar_lds_layout(int M, int C1p, int C2p, int 
     return L;
 }
 
-template <bool DECODE>
+// CDF_LDS: the decoder's CDF rows are packed into LDS (otherwise each search reads a.cdfs in device memory).
+template <bool DECODE, bool CDF_LDS>
 __global__ __launch_bounds__(kThreads) void ar_scan_kernel(const sc2_ar_scan_args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int b = blockIdx.x;
@@ -210,9 +213,11 @@ __global__ __launch_bounds__(kThreads) void ar_scan_kernel(const sc2_ar_scan_arg
             }
         }
         __syncthreads();
-        for (int r = 0; r < a.n_cdfs; ++r) {
-            const int n = a.cdf_sizes[r] - 1, o = rows[r];
-            for (int j = threadIdx.x; j < n; j += kThreads) cdf16[o + j] = (uint16_t)a.cdfs[(long long)r * a.cdf_stride + j];
+        if (CDF_LDS) {
+            for (int r = 0; r < a.n_cdfs; ++r) {
+                const int n = a.cdf_sizes[r] - 1, o = rows[r];
+                for (int j = threadIdx.x; j < n; j += kThreads) cdf16[o + j] = (uint16_t)a.cdfs[(long long)r * a.cdf_stride + j];
+            }
         }
     }
     ArDec d;
@@ -271,9 +276,15 @@ __global__ __launch_bounds__(kThreads) void ar_scan_kernel(const sc2_ar_scan_arg
         if (DECODE && threadIdx.x == 0) {
             for (int c = 0; c < M; ++c) {
                 const int idx = s_idx[c];
-                const uint16_t *row = cdf16 + rows[idx];
-                s_sym[c] = ar_dec_symbol(d, rows[a.n_cdfs + idx], rows[2 * a.n_cdfs + idx],
-                                         [&](int j) { return (unsigned)row[j]; });
+                if (CDF_LDS) {
+                    const uint16_t *row = cdf16 + rows[idx];
+                    s_sym[c] = ar_dec_symbol(d, rows[a.n_cdfs + idx], rows[2 * a.n_cdfs + idx],
+                                             [&](int j) { return (unsigned)row[j]; });
+                } else {
+                    const int32_t *row = a.cdfs + (long long)idx * a.cdf_stride;
+                    s_sym[c] = ar_dec_symbol(d, rows[a.n_cdfs + idx], rows[2 * a.n_cdfs + idx],
+                                             [&](int j) { return (unsigned)row[j]; });
+                }
             }
         }
         __syncthreads();
@@ -313,11 +324,11 @@ __global__ __launch_bounds__(64) void rans_decode_resume_kernel(const uint8_t *b
     } else {
         d.x = st_x[s];
         d.pos = st_pos[s];
-        d.corrupt |= status[s] & kStatusCorrupt;
+        d.corrupt |= status[s] & (kStatusCorrupt | kStatusIndex);   // what an earlier call flagged stays flagged
     }
     for (long long i = 0; i < n_sym; ++i) {
         int idx = indexes[(long long)s * n_sym + i];
-        if (idx < 0 || idx >= n_cdfs) { d.corrupt |= 4; idx = 0; }
+        if (idx < 0 || idx >= n_cdfs) { d.corrupt |= kStatusIndex; idx = 0; }
         const int32_t *row = cdfs + (long long)idx * cdf_stride;
         symbols_out[(long long)s * n_sym + i] = ar_dec_symbol(d, cdf_sizes[idx], offsets[idx],
                                                               [&](int j) { return (unsigned)row[j]; });
@@ -354,18 +365,25 @@ extern "C" int sc2_ar_scan(const sc2_ar_scan_args *args, void *stream) {
         SC2_REQUIRE(a.y && a.symbols && a.indexes, SC2_ERR_INVALID_ARG, "ar_scan: encoding needs y, symbols and indexes");
     }
     if (a.pix0 == a.pix1 && !a.decode) return SC2_OK;
-    const LdsLayout L = ar_lds_layout(a.M, a.C1p, a.C2p, a.n_table, a.n_cdfs, entries, a.decode);
+    constexpr size_t kLdsBytes = 160 * 1024;
+    LdsLayout L = ar_lds_layout(a.M, a.C1p, a.C2p, a.n_table, a.n_cdfs, entries, a.decode);
+    const bool cdf_lds = !a.decode || (size_t)L.total_words * 4 <= kLdsBytes;
+    if (!cdf_lds) L = ar_lds_layout(a.M, a.C1p, a.C2p, a.n_table, a.n_cdfs, 0, 1);   // the rows' start / size / offset only
     const size_t lds = (size_t)L.total_words * 4;
-    SC2_REQUIRE(lds <= 160 * 1024, SC2_ERR_UNSUPPORTED, "ar_scan: %zu bytes of LDS needed (160 KiB available)", lds);
+    SC2_REQUIRE(lds <= kLdsBytes, SC2_ERR_UNSUPPORTED, "ar_scan: %zu bytes of LDS needed (160 KiB available)", lds);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (a.decode) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ar_scan_kernel<true>),
+    if (a.decode && cdf_lds) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ar_scan_kernel<true, true>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(ar_scan_kernel<true>, dim3(a.B), dim3(kThreads), lds, st, a);
+        hipLaunchKernelGGL((ar_scan_kernel<true, true>), dim3(a.B), dim3(kThreads), lds, st, a);
+    } else if (a.decode) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ar_scan_kernel<true, false>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL((ar_scan_kernel<true, false>), dim3(a.B), dim3(kThreads), lds, st, a);
     } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ar_scan_kernel<false>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ar_scan_kernel<false, false>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(ar_scan_kernel<false>, dim3(a.B), dim3(kThreads), lds, st, a);
+        hipLaunchKernelGGL((ar_scan_kernel<false, false>), dim3(a.B), dim3(kThreads), lds, st, a);
     }
     SC2_CHECK_LAUNCH();
     return SC2_OK;

@@ -2076,7 +2076,8 @@ def ar_scan(weights, p1, y_hat_pad, y_hat_nhwc, scale_table, scale_bound, y=None
 def rans_decode_resume(buf, off, nb, indexes, cdfs, cdf_sizes, offsets, state=None, last=True):
     """Decodes indexes.shape[1] more symbols of every stream (explicit per-symbol indexes), continuing from `state`
     (st_x i64 [N], st_pos i32 [N], status i32 [N]; None: start at each stream's first word).  -> (symbols, state); the
-    state's status carries the stream's error bits (8: corrupt / truncated, 16: `last` and the stream did not end there)."""
+    state's status carries the stream's error bits (4: an index outside the table, row 0 decoded in its place; 8: corrupt /
+    truncated; 16: `last` and the stream did not end there); 4 and 8 stay set in the calls that continue the stream."""
     for name, t in (('buf', buf), ('off', off), ('nb', nb), ('indexes', indexes), ('cdfs', cdfs), ('cdf_sizes', cdf_sizes),
                     ('offsets', offsets)):
         _dev(t, name)
