@@ -424,6 +424,16 @@ int sc2_conv1x1_win_supported(int Cin, int Cout, int stride);
 int sc2_conv1x1_win_fwd(const void *x, const void *w_frag, const float *bias, const void *residual, const void *mask, void *y, int N,
                         int H, int W, int Cin, int Cout, int stride, int relu, void *stream);
 
+/* The same 1x1 convolution + bias (+ residual) (+ ReLU) on the eight-wave, 256-channel form of the window-plane structure
+ * (conv1x1_w8.hip): the long-K layers that are plain compute-heavy GEMMs -- conv1 of layer3 / layer4, layer4's conv3 and the stride-2
+ * downsample layers of the torchvision Bottleneck blocks behind the bottleneck (sc2bench/models/backbone.py:235-254).  Tiles of 224
+ * output pixels x 256 channels, 128-channel slabs of the pixel operand as chunk planes in LDS, weights straight into registers,
+ * at most one workgroup per CU, successive tiles' K loops joined.  Arguments as sc2_conv1x1_win_fwd (the SAME w_frag stream) without
+ * `mask`; Cin % 128 == 0, Cout % 256 == 0, stride 1 | 2.  Results are bit-identical to sc2_conv1x1_win_fwd's. */
+int sc2_conv1x1_w8_supported(int Cin, int Cout, int stride);
+int sc2_conv1x1_w8_fwd(const void *x, const void *w_frag, const float *bias, const void *residual, void *y, int N, int H, int W,
+                       int Cin, int Cout, int stride, int relu, void *stream);
+
 /* 3x3 stride-1 pad-1 convolution + bias (+ ReLU) on 28 x 28 / 14 x 14 / 7 x 7 maps: conv2 + bn2 + ReLU of the torchvision
  * Bottleneck blocks of layer2 / layer3 / layer4 behind the bottleneck (sc2bench/models/backbone.py:235-254 runs them) at the
  * 224 x 224 operating point.  Tiles of 196 output pixels x 128 channels, zero-padded window planes in LDS, weights straight

@@ -52,6 +52,31 @@ def _win1_policy(cin, cout, stride):
     return (cin, cout, stride) in ((512, 128, 1), (2048, 512, 1), (512, 2048, 1), (512, 1024, 2))
 
 
+# (cin, cout, stride) of the layers the eight-wave 256-channel 1x1 kernel (conv1x1_w8.hip) takes by default: the tuples it was faster on
+# in EVERY one of five alternating rounds at bs 256, 224 x 224 (tools/head_times.py --w8-ab, profiles/r13_head_times_w8_ab.txt; ms per
+# launch, the five rounds' range):
+#   conv1 of layer3.1-5     (1024 -> 256)      0.0454 - 0.0460 -> 0.0416 - 0.0422   (from conv1x1_kres)
+#   conv1 of layer4.0       (1024 -> 512)      0.0796 - 0.0808 -> 0.0703 - 0.0710   (from conv1x1_kres)
+#   downsample of layer4    (1024 -> 2048 s2)  0.0815 - 0.0829 -> 0.0671 - 0.0676   (from conv1x1_kres)
+#   downsample of layer3    (512 -> 1024 s2)   0.1014 - 0.1029 -> 0.0812 - 0.0829   (from conv1x1_win)
+#   conv3 of layer4.0-2     (512 -> 2048)      0.0530 - 0.0539 -> 0.0478 - 0.0484   (from conv1x1_win)
+# stays where it is: conv1 of layer4.1-2 (2048 -> 512: 112 whole tiles on 256 CUs) 0.0434 - 0.0444 -> 0.0588 - 0.0593; and, outside the
+# kernel's brief but supported by it, conv3 of layer3 (256 -> 1024, HBM-bound) 0.0612 -> 0.0633 and layer2's downsample (256 -> 512 s2).
+_W8_TABLE = ((1024, 256, 1), (1024, 512, 1), (1024, 2048, 2), (512, 1024, 2), (512, 2048, 1))
+
+
+def _w8_policy(cin, cout, stride):
+    """Which 1x1 layers go to the eight-wave 256-channel 1x1 kernel (conv1x1_w8.hip), asked at every call.
+    hip.configure(conv1x1_w8=...) / bench.py --policy conv1x1_w8=...: '0' none, 'all' every supported layer (A/B, tools/head_times.py
+    --w8-ab), default '1' = the layers it measured faster on in every round."""
+    mode = str(hip.host_policy.conv1x1_w8)
+    if mode in ('0', 'False'):
+        return False
+    if mode == 'all':
+        return True
+    return (cin, cout, stride) in _W8_TABLE
+
+
 class ConvSpec(object):
     """What `_Conv` reads of an nn.Conv2d, for convolutions that exist only as a weight tensor."""
     bias = None
@@ -89,6 +114,16 @@ class _Conv(object):
         if self.k == (1, 1) and _win1_policy(conv.in_channels, conv.out_channels, self.stride[0]) and \
                 hip.conv1x1_win_supported(conv.in_channels, conv.out_channels, 1, 1, self.stride, self.pad):
             self.w_win1 = hip.pack_conv_win(w_folded)
+        # long-K 1x1 layers that are plain compute-heavy GEMMs: the eight-wave 256-channel kernel, on conv1x1_win's weight stream (not the
+        # bare data-gradient convolutions of frozen.py: the gradient paths stay where they are).  Which layers it runs is asked per call
+        # (_w8_policy), so hip.configure(conv1x1_w8=...) works on a built head; the stream is packed here only for the layers the policy
+        # in force selects, a layer switched in later packs its own at its first call (_w8_weights)
+        self.cin = conv.in_channels
+        self.w8_ok = bn is not None and self.k == (1, 1) and hip.conv1x1_w8_supported(conv.in_channels, conv.out_channels, 1, 1,
+                                                                                      self.stride, self.pad)
+        self.w_w8 = None
+        if self.w8_ok and _w8_policy(self.cin, self.cout, self.stride[0]):
+            self._w8_weights()
         # 3x3 stride-1 layers on 28 / 14 / 7 pixel maps (conv2 of every block at the 224 x 224 operating point): the
         # window-plane kernel; other map sizes stay on the implicit-GEMM tile kernel (decided per call, by the map size)
         self.w2d = w_folded.reshape(w_folded.shape[0], w_folded.shape[1]).to(torch.bfloat16) if self.k == (1, 1) else None
@@ -109,6 +144,11 @@ class _Conv(object):
                 raise hip.Sc2Error('the HIP head supports dilation on layers of <= 96 output channels only as 3x3 stride-1 with '
                                    'padding == dilation (got kernel {}, stride {}, padding {}, dilation {})'.format(
                                        self.k, self.stride, self.pad, self.dilation))
+
+    def _w8_weights(self):
+        if self.w_w8 is None:
+            self.w_w8 = self.w_win1 if self.w_win1 is not None else hip.pack_conv_win(self.w_folded)
+        return self.w_w8
 
     def _dilated(self, x, epilogue):
         d = self.dilation[0]
@@ -143,6 +183,12 @@ class _Conv(object):
                                       ep_x=ep_x, ep_beta=self.b, tag=self.tag, k_order=self.k_order, dilation=self.dilation)
             assert ep_x is None
             return self._dilated(x, epilogue)
+        if self.w8_ok and epilogue in (hip.EPI_BIAS, hip.EPI_BIAS_RELU, hip.EPI_BIAS_ADD_RELU) and \
+                _w8_policy(self.cin, self.cout, self.stride[0]) and \
+                max(x.numel(), x.shape[0] * x.shape[1] * x.shape[2] * self.cout) * 2 < 0x7FF00000:
+            return hip.conv1x1_w8_fwd(x, self._w8_weights(), self.b, stride=self.stride[0],
+                                      residual=ep_x if epilogue == hip.EPI_BIAS_ADD_RELU else None,
+                                      relu=epilogue != hip.EPI_BIAS, tag=self.tag)
         if self.w_win1 is not None and epilogue in (hip.EPI_BIAS, hip.EPI_BIAS_RELU, hip.EPI_BIAS_ADD_RELU) and \
                 max(x.numel(), x.shape[0] * x.shape[1] * x.shape[2] * self.cout) * 2 < 0x7FF00000:
             return hip.conv1x1_win_fwd(x, self.w_win1, self.b, stride=self.stride[0],

@@ -30,7 +30,7 @@ ABI_SYMBOLS = [
     'sc2_conv2d_fwd', 'sc2_gdn1_bwd_gemm', 'sc2_colsum_bf16', 'sc2_nchw_f32_to_nhwc_f32', 'sc2_conv_f32_chunk_channels', 'sc2_conv2d_f32_fwd',
     'sc2_conv_split_chunk_channels', 'sc2_conv2d_split_fwd',
     'sc2_conv2x2_gdn512_supported', 'sc2_conv2x2_gdn512_fwd', 'sc2_conv1x1_stream_supported', 'sc2_conv1x1_stream_mask_supported', 'sc2_conv1x1_stream_fwd', 'sc2_conv1x1_pair_supported', 'sc2_conv1x1_pair_fwd',
-    'sc2_conv0_gdn96_supported', 'sc2_conv0_gdn96_fwd', 'sc2_conv0_gdn96_nchw_fwd', 'sc2_conv2_gdn48_supported', 'sc2_conv2_gdn48_fwd', 'sc2_conv2x2_c48_supported', 'sc2_conv2x2_c48_fwd', 'sc2_conv1x1_kres_supported', 'sc2_conv1x1_kres_fwd', 'sc2_conv1x1_win_supported', 'sc2_conv1x1_win_fwd', 'sc2_conv3x3_win_supported', 'sc2_conv3x3_win_fwd', 'sc2_conv3x3s2_win_supported', 'sc2_conv3x3s2_win_fwd', 'sc2_conv2x2_win_supported', 'sc2_conv2x2_win_fwd', 'sc2_conv2x2_win_tail_supported', 'sc2_conv2x2_win_tail_fwd', 'sc2_conv2d_wgrad', 'sc2_gdn_bwd_pre', 'sc2_gdn_bwd_post', 'sc2_gdn1_rows_supported', 'sc2_gdn1_rows_fwd', 'sc2_gdn1_rows_bwd',
+    'sc2_conv0_gdn96_supported', 'sc2_conv0_gdn96_fwd', 'sc2_conv0_gdn96_nchw_fwd', 'sc2_conv2_gdn48_supported', 'sc2_conv2_gdn48_fwd', 'sc2_conv2x2_c48_supported', 'sc2_conv2x2_c48_fwd', 'sc2_conv1x1_kres_supported', 'sc2_conv1x1_kres_fwd', 'sc2_conv1x1_win_supported', 'sc2_conv1x1_win_fwd', 'sc2_conv1x1_w8_supported', 'sc2_conv1x1_w8_fwd', 'sc2_conv3x3_win_supported', 'sc2_conv3x3_win_fwd', 'sc2_conv3x3s2_win_supported', 'sc2_conv3x3s2_win_fwd', 'sc2_conv2x2_win_supported', 'sc2_conv2x2_win_fwd', 'sc2_conv2x2_win_tail_supported', 'sc2_conv2x2_win_tail_fwd', 'sc2_conv2d_wgrad', 'sc2_gdn_bwd_pre', 'sc2_gdn_bwd_post', 'sc2_gdn1_rows_supported', 'sc2_gdn1_rows_fwd', 'sc2_gdn1_rows_bwd',
     'sc2_eb_forward', 'sc2_eb_backward', 'sc2_eb_bits_partial_len', 'sc2_eb_symbols', 'sc2_eb_dequantize',
     'sc2_gc_forward', 'sc2_gc_backward', 'sc2_gc_symbols_indexes', 'sc2_gc_dequantize',
     'sc2_pmf_to_quantized_cdf',
@@ -95,6 +95,7 @@ class HostPolicy(object):
     conv1x1_pair = True        # conv3 + next block's conv1 in one launch
     conv_c48 = True            # streaming last encoder conv
     conv1x1_win = '1'          # window-plane 1x1 kernel: '0' none, '1' the layers it measured faster on, 'all'
+    conv1x1_w8 = '1'           # eight-wave 256-channel 1x1 kernel: '0' none, '1' the layers it measured faster on (head._w8_policy), 'all'
     conv_dilation = True       # dilated layers through the descriptor's dilation (False: phase grids)
     fc_kernel = True           # dedicated classifier kernel
     dense_head = True          # DeepLab / FCN heads and the FPN on the library's kernels in bf16 eval
@@ -228,6 +229,8 @@ def lib():
     L.sc2_conv2x2_c48_supported.argtypes = [i32, i32, i32, i32]
     L.sc2_conv2x2_c48_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     L.sc2_conv1x1_win_fwd.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
+    L.sc2_conv1x1_w8_supported.argtypes = [i32, i32, i32]
+    L.sc2_conv1x1_w8_fwd.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]
     L.sc2_conv3x3s2_win_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]
     L.sc2_conv2x2_win_supported.argtypes = [i32, i32, i32, i32, i32]
     L.sc2_conv2x2_win_fwd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]
@@ -1319,6 +1322,41 @@ def conv1x1_win_fwd(x_nhwc, w_frag, bias, stride=1, residual=None, relu=False, t
     with _timed(tag or 'conv1x1_win'):
         _check(lib().sc2_conv1x1_win_fwd(_ptr(x_nhwc), _ptr(w_frag), _ptr(bias), _ptr(residual), _ptr(mask), _ptr(out), N, H, W, Cin,
                                          cout, stride, 1 if relu else 0, _stream()), 'conv1x1_win_fwd')
+    return out
+
+
+def conv1x1_w8_supported(cin, cout, kh, kw, stride, pad):
+    """True if this 1x1 conv can run on the eight-wave 256-channel 1x1 kernel (Cin % 128 == 0, Cout % 256 == 0, stride 1 or 2)."""
+    sh, sw = (stride, stride) if isinstance(stride, int) else stride
+    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    return (kh, kw, ph, pw) == (1, 1, 0, 0) and sh == sw and bool(lib().sc2_conv1x1_w8_supported(cin, cout, sh))
+
+
+def conv1x1_w8_fwd(x_nhwc, w_frag, bias, stride=1, residual=None, relu=False, tag=None, out=None):
+    """y = act(conv1x1(x) + bias [+ residual]) on the eight-wave 256-channel 1x1 kernel (conv1x1_w8.hip); bf16 NHWC in / out;
+    w_frag = pack_conv_win(w.reshape(Cout, Cin, 1, 1)), the stream of conv1x1_win_fwd, whose results it reproduces bit for bit.
+    out: a contiguous bf16 tensor of the output's size to write into (default: a new one)."""
+    for t, name in ((x_nhwc, 'x'), (w_frag, 'w_frag'), (bias, 'bias')):
+        _dev(t, name)
+    assert x_nhwc.dtype == torch.bfloat16 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
+    N, H, W, Cin = x_nhwc.shape
+    cout = w_frag.shape[1] * 16
+    assert w_frag.dtype == torch.bfloat16 and w_frag.is_contiguous() and tuple(w_frag.shape) == (Cin // 32, cout // 16, 64, 8)
+    assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == cout
+    stride = int(stride)
+    shape = (N, (H - 1) // stride + 1, (W - 1) // stride + 1, cout)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.bfloat16, device=x_nhwc.device)
+    else:
+        _dev(out, 'out')
+        assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.numel() == N * shape[1] * shape[2] * cout
+        out = out.view(shape)
+    if residual is not None:
+        _dev(residual, 'residual')
+        assert residual.dtype == torch.bfloat16 and residual.is_contiguous() and tuple(residual.shape) == tuple(out.shape)
+    with _timed(tag or 'conv1x1_w8'):
+        _check(lib().sc2_conv1x1_w8_fwd(_ptr(x_nhwc), _ptr(w_frag), _ptr(bias), _ptr(residual), _ptr(out), N, H, W, Cin, cout, stride,
+                                        1 if relu else 0, _stream()), 'conv1x1_w8_fwd')
     return out
 
 

@@ -30,7 +30,7 @@ ENV = {
     'SC2_CONV0_FUSED': ('conv0_fused', _ON), 'SC2_CONV2_FUSED': ('conv2_fused', _ON), 'SC2_CONV_KRES': ('conv_kres', _INT),
     'SC2_CONV_WIN': ('conv_win', _ON), 'SC2_CONV_WIN_S2': ('conv_win_s2', _ON), 'SC2_CONV2X2_WIN': ('conv2x2_win', _ON),
     'SC2_W2_TAIL': ('w2_tail', _ON), 'SC2_CONV_STREAM': ('conv_stream', _ON), 'SC2_CONV1X1_PAIR': ('conv1x1_pair', _ON),
-    'SC2_CONV_C48': ('conv_c48', _ON), 'SC2_CONV1X1_WIN': ('conv1x1_win', str), 'SC2_CONV_DILATION': ('conv_dilation', _ON),
+    'SC2_CONV_C48': ('conv_c48', _ON), 'SC2_CONV1X1_WIN': ('conv1x1_win', str), 'SC2_CONV1X1_W8': ('conv1x1_w8', str), 'SC2_CONV_DILATION': ('conv_dilation', _ON),
     'SC2_FC_KERNEL': ('fc_kernel', _ON), 'SC2_DENSE_HEAD': ('dense_head', _ON), 'SC2_RANS_FUSED_DQ': ('rans_fused_dq', _ON),
     'SC2_HOST_CODER_MAX_STREAMS': ('host_coder_max_streams', _INT),
 }
