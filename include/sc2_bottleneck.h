@@ -199,7 +199,10 @@ typedef struct sc2_conv_desc {
     int32_t out_format;            /* enum sc2_conv_out                                          */
     int32_t Kpad;                  /* row pitch (elements) of the packed weights, % 64 == 0      */
     int32_t Cout_pad;              /* rows of the packed weight matrix (>= Cout, % 128 == 0 or
-                                      == tile width; see sc2_conv_weight_rows)                   */
+                                      == tile width; see sc2_conv_weight_rows.  The squared-form
+                                      GDN (SC2_AOP_SQUARE with SC2_EPI_GDN2 / SC2_EPI_IGDN2) has
+                                      128-row tiles only: with Cout <= 96 it takes gamma zero-padded
+                                      to Cout_pad = 128 rows)                                     */
     /* Output scatter, for the data gradient of a strided conv (one launch per stride-parity class).  out_H == 0:
      * dense output [N,OH,OW,Cout].  Otherwise OH/OW are taken as given (rows past the symmetric-padding formula
      * see implicit zeros) and output pixel (oh, ow) is written to (oh*out_stride_h + out_off_h,
@@ -736,7 +739,13 @@ int sc2_rans_decode_host(const sc2_rans_host_tables *tables, const uint8_t *in, 
  * live in st_x / st_pos between calls (initialised when pix0 == 0), so a scan may be split into pixel ranges.  status[b]:
  * bit 3 = a corrupt or truncated stream (no word outside the stream is read), bit 4 = the stream did not end where the last
  * pixel ended (state != 2^31 or words left over).  All M <= 512, 2M and C1p / C2p <= 1280.  The decoder keeps the CDF rows in
- * LDS when they fit beside the step's vectors and searches them in device memory otherwise (same symbols either way). */
+ * LDS when they fit beside the step's vectors and searches them in device memory otherwise (same symbols either way).
+ * sc2_ar_scan_f32: the same struct, the same step, checks and error codes, with wc / w1 / w2 / w3 read as `const float *`:
+ * k-major F32 matrices of the shapes and zero padding above, each 8-byte aligned (a lane loads two adjacent outputs' weights as
+ * one 8-byte value).  The products are then those of the unrounded f32 weights; the reduction order, the biases / p1, the table
+ * search, rint, the decoder and the resumable state are shared code.  A stream decodes only with the weight form (and the weights)
+ * that encoded it: one scale on the other side of a table boundary, or one mean that rounds y the other way, changes every
+ * later pixel of the image. */
 typedef struct sc2_ar_scan_args {
     int32_t B, H, W, M, C1p, C2p;
     int32_t n_table, n_cdfs, cdf_stride, pix0, pix1, decode;
@@ -757,6 +766,7 @@ typedef struct sc2_ar_scan_args {
     float *gaussian_params;   /* nullable: f32 [B][H*W][2M], each pixel's scales then means as the step computed them */
 } sc2_ar_scan_args;
 int sc2_ar_scan(const sc2_ar_scan_args *args, void *stream);
+int sc2_ar_scan_f32(const sc2_ar_scan_args *args, void *stream);
 /* Resumable rANS decoder (the scan's decoder as a kernel of its own): decodes n_sym symbols per stream with explicit per-symbol
  * indexes [n_streams][n_sym], continuing from st_x / st_pos / status unless `first` (then it starts at the stream's first word).
  * `last`: also check that the stream ends here (status bit 4).  Same stream layout and status bits as sc2_ar_scan, and bit 2 = an

@@ -13,8 +13,11 @@ bottleneck and the range coder as in the supervised-compression bottleneck.
 
 `set_encoder_precision('f32' | 'bf16x3' | 'bf16x6')` (or the constructor's `encoder_precision=`) moves every transform of
 `FactorizedPrior`, `ScaleHyperprior` and `MeanScaleHyperprior` to the precise kernels (csrc/conv_f32.hip / conv_split.hip) on
-f32 activations: see `_PrecisionSwitch`.
+f32 activations: see `_PrecisionSwitch`.  `JointAutoregressiveHierarchicalPriors` (`mbt2018`) takes them once its serial context scan
+reads f32 weights (`set_scan_precision('f32')`, a switch of its own): see the class.
 """
+import functools
+
 import torch
 from torch import nn
 
@@ -246,6 +249,10 @@ def bmshj2018_factorized(quality, metric='mse', pretrained=False, progress=True,
 # hyperprior models (compressai.models.google: ScaleHyperprior, MeanScaleHyperprior,
 # JointAutoregressiveHierarchicalPriors) -- the architecture is [recalled] from CompressAI 1.2.x, not read from an install
 # --------------------------------------------------------------------------------------------- #
+def _pad8(c):
+    return (c + 7) // 8 * 8
+
+
 def _run_biased(seq, x_nhwc, a_op=hip.AOP_NONE, last_out_format=hip.OUT_F32_NCHW):
     """An nn.Sequential of biased HipConv2d / HipConvTranspose2d with ReLU / LeakyReLU(0.01) in between (the h_a / h_s
     transforms of the hyperprior models) on bf16 NHWC activations: bias and activation ride in the conv's epilogue.  `a_op`
@@ -268,15 +275,24 @@ def _run_biased(seq, x_nhwc, a_op=hip.AOP_NONE, last_out_format=hip.OUT_F32_NCHW
         if isinstance(m, HipConvTranspose2d):
             if i == 0 and a_op != hip.AOP_NONE:
                 raise hip.Sc2Error('_run_biased: an input operand on a transposed convolution')
+            if h.shape[-1] != m.in_channels:
+                raise hip.Sc2Error('_run_biased: {} channels into {}'.format(h.shape[-1], m))
             kfmt = hip.OUT_F32_NHWC if fmt == hip.OUT_F32_NCHW else fmt
-            h = m.forward_nhwc(h, hip.EPI_NONE if epi == hip.EPI_BIAS else epi, None, out_format=kfmt)
+            # an output width that is no multiple of 8 (3M/2 = 60 at M = 40) stays zero-padded for the convolution behind it
+            h = m.forward_nhwc(h, hip.EPI_NONE if epi == hip.EPI_BIAS else epi, None, out_format=kfmt, keep_pad=not last)
             if fmt == hip.OUT_F32_NCHW:
                 h = h.permute(0, 3, 1, 2).contiguous()
         elif isinstance(m, HipConv2d):
-            assert m.bias is not None and h.shape[-1] == m.in_channels
-            h = hip.conv2d_fwd(h, m.packed_weight(), m.out_channels, m.kernel_size[0], m.kernel_size[1], m.stride,
+            assert m.bias is not None
+            if h.shape[-1] == m.in_channels:
+                w, order = m.packed_weight(), m.k_order()
+            elif h.shape[-1] == _pad8(m.in_channels):       # zero channels from the padded layer before: zero weight columns
+                w, order = m.padded_weight(h.shape[-1]), hip.K_TAP_MAJOR
+            else:
+                raise hip.Sc2Error('_run_biased: {} channels into {}'.format(h.shape[-1], m))
+            h = hip.conv2d_fwd(h, w, m.out_channels, m.kernel_size[0], m.kernel_size[1], m.stride,
                                m.padding, a_op=a_op if i == 0 else hip.AOP_NONE, epilogue=epi, ep_beta=m.bias_f32(),
-                               out_format=fmt, tag=getattr(m, '_tag', None), k_order=m.k_order())
+                               out_format=fmt, tag=getattr(m, '_tag', None), k_order=order)
         else:
             raise hip.Sc2Error('_run_biased: unsupported module {}'.format(type(m).__name__))
         i += 1 if epi == hip.EPI_BIAS else 2
@@ -455,10 +471,6 @@ class MaskedConv2d(HipConv2d):
         return self._masked_packed
 
 
-def _pad8(c):
-    return (c + 7) // 8 * 8
-
-
 @register_compression_model_class
 class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
     """Joint autoregressive and hierarchical priors of Minnen et al. 2018 (`compressai.models.
@@ -472,18 +484,41 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
     both directions.  Channel counts that are not multiples of 8 (10M/3, 8M/3 at M = 320) are zero-padded in the packed
     weights and activations.
 
-    Only 'bf16': the context scan has bf16 operands, and a codec precise in g_a / h_a / h_s alone would promise bytes it cannot
-    keep.  `set_encoder_precision` with any other mode raises Sc2Error."""
+    Two precision switches, neither a parameter or buffer (state dicts are what they were):
+    `set_scan_precision('bf16' | 'f32')` (kwarg `scan_precision`): the weight form of the serial scan.  'bf16' (default) reads the
+    four matrices rounded to bf16, 'f32' reads them unrounded (sc2_ar_scan_f32: the same step code, twice the weight bytes per
+    step).  The scan's precision is a codec property of its own: an f32 scan with bf16 transforms is a self-consistent codec.
+    `set_encoder_precision` (kwarg `encoder_precision`): as on the other input codecs, but a precise mode ('f32' / 'bf16x3' /
+    'bf16x6') is refused with Sc2Error while the scan is 'bf16' -- a codec precise in g_a / h_a / h_s alone would promise bytes it
+    cannot keep -- and `set_scan_precision('bf16')` is refused while a precise mode is set.  In the precise modes g_a, h_a, h_s, g_s,
+    the hyper-params half of entropy_parameters' first layer (p1) and `forward`'s context convolution and entropy_parameters run
+    on the precise kernels with f32 NHWC activations; the scan is the f32 one in all three (it is VALU code: there is no matrix
+    product to split).  A stream decodes only under the two settings that made it."""
+    scan_precision = 'bf16'
 
-    def set_encoder_precision(self, precision):
-        super().set_encoder_precision(precision)     # (an unknown name: ValueError)
-        if precision != 'bf16':
-            self.encoder_precision = 'bf16'
-            raise hip.Sc2Error('JointAutoregressiveHierarchicalPriors: encoder precision {!r} is not supported -- the context scan '
-                               '(csrc/ar_context.hip) has bf16 operands; only \'bf16\''.format(precision))
+    def set_scan_precision(self, precision):
+        """'bf16' (default) or 'f32': the weight form the serial scan of compress / decompress reads.  -> self."""
+        if precision not in ('bf16', 'f32'):
+            raise ValueError("scan precision must be 'bf16' or 'f32', got {!r}".format(precision))
+        if precision == 'bf16' and self.encoder_precision != 'bf16':
+            raise hip.Sc2Error('JointAutoregressiveHierarchicalPriors: encoder precision {!r} needs the f32 context scan; set the '
+                               "encoder precision to 'bf16' first".format(self.encoder_precision))
+        self.scan_precision = precision
         return self
 
-    def __init__(self, N=192, M=192, **kwargs):
+    def set_encoder_precision(self, precision):
+        previous = self.encoder_precision
+        super().set_encoder_precision(precision)     # (an unknown name: ValueError)
+        if precision != 'bf16' and self.scan_precision != 'f32':
+            self.encoder_precision = previous
+            raise hip.Sc2Error('JointAutoregressiveHierarchicalPriors: encoder precision {!r} is not supported while the context scan '
+                               "(csrc/ar_context.hip) has bf16 operands; set_scan_precision('f32') lifts this".format(precision))
+        return self
+
+    def __init__(self, N=192, M=192, scan_precision='bf16', **kwargs):
+        if scan_precision not in ('bf16', 'f32'):
+            raise ValueError("scan precision must be 'bf16' or 'f32', got {!r}".format(scan_precision))
+        self.__dict__['scan_precision'] = scan_precision     # before the base class sets encoder_precision, whatever the kwarg order
         super().__init__(N, M, **kwargs)
         self.h_a = nn.Sequential(conv(M, N, stride=1, kernel_size=3), nn.LeakyReLU(inplace=True), conv(N, N),
                                  nn.LeakyReLU(inplace=True), conv(N, N))
@@ -503,13 +538,11 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
         return 2 ** (4 + 2)
 
     # ---- packed weights (once per parameter version)
-    def _packed(self):
+    def _padded_f32(self):
+        """The f32 matrices every pack is cut from: entropy_parameters' 1x1 weights zero-padded to C1p / C2p (w1p [C1p, 4M], w2p
+        [C2p, C1p], w3p [2M, C2p], b1 [C1p], b2 [C2p]) and the masked context weights k-major (wc [12M, 2M], k = tap * M + channel)."""
         ep = self.entropy_parameters
         cp = self.context_prediction
-        params = [cp.weight, cp.bias, cp.mask] + [p for i in (0, 2, 4) for p in (ep[i].weight, ep[i].bias)]
-        key = tuple((p._version, p.data_ptr(), p.device) for p in params)
-        if self.__dict__.get('_packed_key') == key:
-            return self._packed_cache
         M = self.M
         C1, C2 = ep[0].out_channels, ep[2].out_channels
         C1p, C2p = _pad8(C1), _pad8(C2)
@@ -531,28 +564,89 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
             mw = cp.masked_weight().float()                          # [2M, M, 5, 5]
             taps = [(ky, kx) for ky in range(2) for kx in range(5)] + [(2, 0), (2, 1)]
             wc = torch.cat([mw[:, :, ky, kx].t() for ky, kx in taps], 0)   # [12M, 2M], k = tap * M + channel
-            pk = {
-                'C1p': C1p, 'C2p': C2p,
-                # the parallel path: 1x1 convs on the packed-weight kernels (zero rows / columns for the padding)
-                'ep1': hip.pack_conv_weight(w1p.reshape(C1p, 4 * M, 1, 1)), 'eb1': b1.contiguous(),
-                'ep2': hip.pack_conv_weight(w2p.reshape(C2p, C1p, 1, 1)), 'eb2': b2.contiguous(),
-                'ep3': hip.pack_conv_weight(w3p.reshape(2 * M, C2p, 1, 1)), 'eb3': ep[4].bias.detach().float().contiguous(),
-                # the hyper-params half of layer 1, for all pixels before the scan
-                'ep1a': hip.pack_conv_weight(w1p[:, :2 * M].contiguous().reshape(C1p, 2 * M, 1, 1)),
-                # the scan: k-major bf16
-                'scan': {'wc': wc.to(torch.bfloat16).contiguous(), 'bc': cp.bias.detach().float().contiguous(),
-                         'w1': w1p[:, 2 * M:].t().to(torch.bfloat16).contiguous(),
-                         'w2': w2p.t().to(torch.bfloat16).contiguous(), 'b2': b2.contiguous(),
-                         'w3': w3p.t().to(torch.bfloat16).contiguous(), 'b3': ep[4].bias.detach().float().contiguous()},
-            }
-        self._packed_cache = pk
-        self._packed_key = key
+        return {'C1p': C1p, 'C2p': C2p, 'w1p': w1p, 'w2p': w2p, 'w3p': w3p, 'b1': b1, 'b2': b2, 'wc': wc, 'mw': mw}
+
+    def _packed(self, scan_f32=False):
+        """The packed weights of the current parameter versions.  scan_f32: also 'scan_f32', the scan's matrices masked, k-major and
+        UNROUNDED (built when first asked for, dropped with the rest when a parameter changes)."""
+        ep = self.entropy_parameters
+        cp = self.context_prediction
+        params = [cp.weight, cp.bias, cp.mask] + [p for i in (0, 2, 4) for p in (ep[i].weight, ep[i].bias)]
+        key = tuple((p._version, p.data_ptr(), p.device) for p in params)
+        if self.__dict__.get('_packed_key') != key:
+            M = self.M
+            f = self._padded_f32()
+            C1p, C2p, w1p, w2p, w3p, b1, b2, wc = (f[k] for k in ('C1p', 'C2p', 'w1p', 'w2p', 'w3p', 'b1', 'b2', 'wc'))
+            with torch.no_grad():
+                pk = {
+                    'C1p': C1p, 'C2p': C2p,
+                    # the parallel path: 1x1 convs on the packed-weight kernels (zero rows / columns for the padding)
+                    'ep1': hip.pack_conv_weight(w1p.reshape(C1p, 4 * M, 1, 1)), 'eb1': b1.contiguous(),
+                    'ep2': hip.pack_conv_weight(w2p.reshape(C2p, C1p, 1, 1)), 'eb2': b2.contiguous(),
+                    'ep3': hip.pack_conv_weight(w3p.reshape(2 * M, C2p, 1, 1)), 'eb3': ep[4].bias.detach().float().contiguous(),
+                    # the hyper-params half of layer 1, for all pixels before the scan
+                    'ep1a': hip.pack_conv_weight(w1p[:, :2 * M].contiguous().reshape(C1p, 2 * M, 1, 1)),
+                    # the scan: k-major bf16
+                    'scan': {'wc': wc.to(torch.bfloat16).contiguous(), 'bc': cp.bias.detach().float().contiguous(),
+                             'w1': w1p[:, 2 * M:].t().to(torch.bfloat16).contiguous(),
+                             'w2': w2p.t().to(torch.bfloat16).contiguous(), 'b2': b2.contiguous(),
+                             'w3': w3p.t().to(torch.bfloat16).contiguous(), 'b3': ep[4].bias.detach().float().contiguous()},
+                }
+            self._packed_cache = pk
+            self._packed_key = key
+        pk = self._packed_cache
+        if scan_f32 and 'scan_f32' not in pk:
+            f = self._padded_f32()
+            bf = pk['scan']
+            pk['scan_f32'] = {'wc': f['wc'].contiguous(), 'bc': bf['bc'], 'w1': f['w1p'][:, 2 * self.M:].t().contiguous(),
+                              'w2': f['w2p'].t().contiguous(), 'b2': bf['b2'], 'w3': f['w3p'].t().contiguous(), 'b3': bf['b3']}
         return pk
 
+    def _scan_weights(self):
+        """The scan's weight dict in the form `scan_precision` names."""
+        if self.scan_precision == 'f32':
+            return self._packed(scan_f32=True)['scan_f32']
+        return self._packed()['scan']
+
+    def _precise_pack(self, name):
+        """Fragment-major weights of the precise kernels in the current mode for one of 'ctx' (masked 5x5), 'ep1', 'ep2', 'ep3'
+        (padded 1x1) and 'ep1a' (the hyper-params half of layer 1); built when first needed, kept with the pack."""
+        ns = self._precise_ns()
+        if ns is None:
+            raise hip.Sc2Error('JointAutoregressiveHierarchicalPriors: no precise weights in mode {!r}'.format(self.encoder_precision))
+        if self.M % 4:
+            raise hip.Sc2Error('JointAutoregressiveHierarchicalPriors: mode {!r} needs M to be a multiple of 4, got {}'.format(
+                self.encoder_precision, self.M))
+        pk = self._packed()
+        if (name, ns) not in pk:
+            f = self._padded_f32()
+            M = self.M
+            w = {'ctx': lambda: f['mw'], 'ep1': lambda: f['w1p'].reshape(f['C1p'], 4 * M, 1, 1),
+                 'ep2': lambda: f['w2p'].reshape(f['C2p'], f['C1p'], 1, 1), 'ep3': lambda: f['w3p'].reshape(2 * M, f['C2p'], 1, 1),
+                 'ep1a': lambda: f['w1p'][:, :2 * M].contiguous().reshape(f['C1p'], 2 * M, 1, 1)}[name]()
+            with torch.no_grad():
+                pk[(name, ns)] = hip.pack_conv_split(w, ns) if ns else hip.pack_conv_f32(w)
+        return pk[(name, ns)]
+
+    def _precise_conv(self, h, name, cout, k, pad, epilogue, bias, out_format, tag):
+        """One launch of the precise kernels of the current mode on an f32 NHWC map."""
+        ns = self._precise_ns()
+        conv = functools.partial(hip.conv2d_split_fwd, ns=ns) if ns else hip.conv2d_f32_fwd
+        sfx = '.bf16x{}'.format(3 * (ns - 1)) if ns else '.f32'
+        return conv(h, self._precise_pack(name), cout, k, k, 1, pad, epilogue=epilogue, ep_beta=bias, out_format=out_format,
+                    tag=tag + sfx)
+
     def entropy_parameters_nhwc(self, params_nhwc, ctx_nhwc):
-        """entropy_parameters(cat(params, ctx)) on bf16 NHWC maps -> f32 NCHW gaussian params [B, 2M, H, W]."""
+        """entropy_parameters(cat(params, ctx)) on bf16 NHWC maps (f32 NHWC in the precise modes) -> f32 NCHW gaussian params
+        [B, 2M, H, W]."""
         pk = self._packed()
         h = torch.cat([params_nhwc, ctx_nhwc], dim=3).contiguous()
+        if self._precise_ns() is not None:       # f32 NHWC maps, LeakyReLU in the epilogue, the padded widths kept
+            if h.dtype != torch.float32:
+                raise hip.Sc2Error('entropy_parameters: mode {!r} takes f32 maps'.format(self.encoder_precision))
+            h = self._precise_conv(h, 'ep1', pk['C1p'], 1, 0, hip.EPI_BIAS_LEAKY_RELU, pk['eb1'], hip.OUT_F32_NHWC, 'entropy_parameters.0')
+            h = self._precise_conv(h, 'ep2', pk['C2p'], 1, 0, hip.EPI_BIAS_LEAKY_RELU, pk['eb2'], hip.OUT_F32_NHWC, 'entropy_parameters.2')
+            return self._precise_conv(h, 'ep3', 2 * self.M, 1, 0, hip.EPI_BIAS, pk['eb3'], hip.OUT_F32_NCHW, 'entropy_parameters.4')
         h = hip.conv2d_fwd(h, pk['ep1'], pk['C1p'], 1, 1, 1, 0, epilogue=hip.EPI_BIAS_LEAKY_RELU, ep_beta=pk['eb1'],
                            tag='entropy_parameters.0')
         h = hip.conv2d_fwd(h, pk['ep2'], pk['C2p'], 1, 1, 1, 0, epilogue=hip.EPI_BIAS_LEAKY_RELU, ep_beta=pk['eb2'],
@@ -561,8 +655,11 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
                               out_format=hip.OUT_F32_NCHW, tag='entropy_parameters.4')
 
     def context_nhwc(self, y_hat):
-        """context_prediction(y_hat) over the whole map: f32 NCHW y_hat -> bf16 NHWC [B, H, W, 2M]."""
+        """context_prediction(y_hat) over the whole map: f32 NCHW y_hat -> bf16 NHWC [B, H, W, 2M] (f32 NHWC in the precise modes)."""
         cp = self.context_prediction
+        if self._precise_ns() is not None:
+            return self._precise_conv(self._nhwc(y_hat), 'ctx', 2 * self.M, 5, 2, hip.EPI_BIAS, cp.bias_f32(), hip.OUT_F32_NHWC,
+                                      'context_prediction')
         x = hip.nchw_f32_to_nhwc_bf16(y_hat.float().contiguous(), self.M)
         return hip.conv2d_fwd(x, cp.packed_weight(), 2 * self.M, 5, 5, 1, 2, epilogue=hip.EPI_BIAS, ep_beta=cp.bias_f32(),
                               tag='context_prediction', k_order=cp.k_order())
@@ -571,7 +668,10 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
         y = self.analysis(x)
         z = self.hyper_analysis(y)
         z_hat, z_likelihoods = self.entropy_bottleneck(z)
-        params = self.hyper_synthesis(hip.nchw_f32_to_nhwc_bf16(z_hat.contiguous(), self.N), out_format=hip.OUT_BF16_NHWC)
+        if self._precise_ns() is not None:
+            params = self.hyper_synthesis(self._nhwc(z_hat), out_format=hip.OUT_F32_NHWC)
+        else:
+            params = self.hyper_synthesis(hip.nchw_f32_to_nhwc_bf16(z_hat.contiguous(), self.N), out_format=hip.OUT_BF16_NHWC)
         y_hat = self.gaussian_conditional.quantize(y, 'noise' if self.training else 'dequantize')
         gaussian_params = self.entropy_parameters_nhwc(params, self.context_nhwc(y_hat))
         scales_hat, means_hat = gaussian_params.chunk(2, 1)
@@ -580,12 +680,22 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
         return {'x_hat': x_hat, 'likelihoods': {'y': y_likelihoods, 'z': z_likelihoods}}
 
     # ---- the serial scan
+    def hyper_params_term(self, params_nhwc):
+        """p1 = W1[:, :2M] . params + b1, the hyper-params half of entropy_parameters' first layer for every pixel, zero-padded to
+        C1p: bf16 NHWC params (f32 NHWC in the precise modes: one precise 1x1 launch on the f32 params) -> f32 [B, H, W, C1p]."""
+        pk = self._packed()
+        if self._precise_ns() is not None:
+            if params_nhwc.dtype != torch.float32:
+                raise hip.Sc2Error('hyper_params_term: mode {!r} takes the f32 params'.format(self.encoder_precision))
+            return self._precise_conv(params_nhwc, 'ep1a', pk['C1p'], 1, 0, hip.EPI_BIAS, pk['eb1'], hip.OUT_F32_NHWC,
+                                      'entropy_parameters.0.params')
+        return hip.conv2d_fwd(params_nhwc, pk['ep1a'], pk['C1p'], 1, 1, 1, 0, epilogue=hip.EPI_BIAS, ep_beta=pk['eb1'],
+                              out_format=hip.OUT_F32_NHWC, tag='entropy_parameters.0.params')
+
     def _scan_inputs(self, z_hat_nhwc):
         """-> (p1 f32 [B, H, W, C1p], y_hat_pad f32 zeros [B, H+2, W+4, M]) for the y grid of 4x z's size."""
-        pk = self._packed()
-        params = self.hyper_synthesis(z_hat_nhwc, out_format=hip.OUT_BF16_NHWC)
-        p1 = hip.conv2d_fwd(params, pk['ep1a'], pk['C1p'], 1, 1, 1, 0, epilogue=hip.EPI_BIAS, ep_beta=pk['eb1'],
-                            out_format=hip.OUT_F32_NHWC, tag='entropy_parameters.0.params')
+        precise = self._precise_ns() is not None
+        p1 = self.hyper_params_term(self.hyper_synthesis(z_hat_nhwc, out_format=hip.OUT_F32_NHWC if precise else hip.OUT_BF16_NHWC))
         B, H, W, _ = p1.shape
         y_hat_pad = torch.zeros((B, H + 2, W + 4, self.M), dtype=torch.float32, device=p1.device)
         return p1, y_hat_pad
@@ -597,7 +707,7 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
         return gc
 
     def compress_device(self, x, gaussian_params=None):
-        """-> dict(y, symbols, indexes [B, H*W*M] pixel-major, y_hat_pad, z_strings, shape) with the scan done on the device."""
+        """-> dict(y, symbols, indexes [B, H*W*M] pixel-major, y_hat_pad, p1, z_strings, shape) with the scan done on the device."""
         gc = self._check_tables()
         y = self.analysis(x)
         z = self.hyper_analysis(y)
@@ -609,9 +719,9 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
                              '{}'.format(tuple(y.shape[-2:]), (H, W), self.downsampling_factor))
         sym = torch.empty((B, H * W * self.M), dtype=torch.int32, device=y.device)
         idx = torch.empty_like(sym)
-        hip.ar_scan(self._packed()['scan'], p1, y_hat_pad, None, gc.scale_table.float().contiguous(), gc._scale_bound,
+        hip.ar_scan(self._scan_weights(), p1, y_hat_pad, None, gc.scale_table.float().contiguous(), gc._scale_bound,
                     y=y.float().contiguous(), symbols=sym, indexes=idx, gaussian_params=gaussian_params)
-        return {'y': y, 'symbols': sym, 'indexes': idx, 'y_hat_pad': y_hat_pad, 'z_strings': z_strings,
+        return {'y': y, 'symbols': sym, 'indexes': idx, 'y_hat_pad': y_hat_pad, 'p1': p1, 'z_strings': z_strings,
                 'shape': z.size()[-2:]}
 
     def compress(self, x):
@@ -621,6 +731,7 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
 
     def decompress_device(self, strings, shape, gaussian_params=None, chunks=1):
         """-> (y_hat_pad f32 [B, H+2, W+4, M], y_hat bf16 NHWC [B, H, W, M], symbols [B, H*W*M]); raises on a corrupt stream.
+        In the precise encoder modes y_hat is None: g_s takes the f32 interior of y_hat_pad, and the scan writes no bf16 copy.
         `chunks` > 1 splits the scan into that many launches over consecutive pixel ranges (the decoder state carries over)."""
         assert isinstance(strings, list) and len(strings) == 2
         gc = self._check_tables()
@@ -635,12 +746,12 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
                'offsets': offset.int().contiguous(), 'cdf_entries': int(cdf_len.sum().item()) - cdf_len.numel(),
                'st_x': torch.zeros(B, dtype=torch.int64, device=dev), 'st_pos': torch.zeros(B, dtype=torch.int32, device=dev),
                'status': torch.zeros(B, dtype=torch.int32, device=dev)}
-        y_hat = torch.empty((B, H, W, self.M), dtype=torch.bfloat16, device=dev)
+        y_hat = torch.empty((B, H, W, self.M), dtype=torch.bfloat16, device=dev) if self._precise_ns() is None else None
         sym = torch.empty((B, H * W * self.M), dtype=torch.int32, device=dev)
         n = H * W
         bounds = [n * i // chunks for i in range(chunks + 1)]
         for i in range(chunks):
-            hip.ar_scan(self._packed()['scan'], p1, y_hat_pad, y_hat, gc.scale_table.float().contiguous(), gc._scale_bound,
+            hip.ar_scan(self._scan_weights(), p1, y_hat_pad, y_hat, gc.scale_table.float().contiguous(), gc._scale_bound,
                         symbols=sym, decode=dec, pix=(bounds[i], bounds[i + 1]), gaussian_params=gaussian_params)
         what = 'JointAutoregressiveHierarchicalPriors.decompress'
         _raise_on_status(dec['status'] & ~16, what)   # bit 4 (16): the scan's own end-of-stream check
@@ -649,7 +760,9 @@ class JointAutoregressiveHierarchicalPriors(MeanScaleHyperprior):
         return y_hat_pad, y_hat, sym
 
     def decompress(self, strings, shape):
-        _, y_hat, _ = self.decompress_device(strings, shape)
+        y_hat_pad, y_hat, _ = self.decompress_device(strings, shape)
+        if self._precise_ns() is not None:      # symbols + means is not bf16-exact: g_s takes the f32 y_hat
+            y_hat = y_hat_pad[:, 2:, 2:y_hat_pad.shape[2] - 2, :].contiguous()
         return {'x_hat': self.synthesis_nhwc(y_hat).clamp_(0, 1)}
 
 

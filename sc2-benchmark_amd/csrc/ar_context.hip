@@ -20,6 +20,10 @@
 // A table too long for LDS beside the step's vectors (a scale table reaching into the thousands) is searched in device memory.
 // State and read position are loaded from / stored to device memory at the ends of the pixel range: a scan may be split.
 // No word outside a stream's bytes is ever read (zeros are supplied past its end and the stream is flagged).
+//
+// Two weight forms, one step: sc2_ar_scan reads the four matrices as bf16, sc2_ar_scan_f32 as f32 (same k-major shapes, same zero
+// padding).  The kernel is a template on the weight type; only the load of a weight pair differs, so the f32 form is as
+// deterministic and batch invariant, and its encoder and decoder run the same step code too.
 #include <math.h>
 
 #include "sc2_common.h"
@@ -126,25 +130,59 @@ __device__ __forceinline__ int ar_dec_status(const ArDec &d, bool last) {
 __device__ __forceinline__ float bf_lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
 __device__ __forceinline__ float bf_hi(uint32_t w) { return __builtin_bit_cast(float, w & 0xFFFF0000u); }
 
-// out[n] = act(sum_k in[k] W[k][n] (+ bias[n]) (+ add[n])), N even, W k-major bf16 with row length N.  `in` and `out` in LDS,
-// `part` = kSplit * N floats of LDS.  Ends with a barrier: `out` is visible to the whole workgroup.
-__device__ void ar_gemv(const float *in, int K, const uint16_t *__restrict__ W, int N, const float *__restrict__ bias,
+// The two weight forms.  A lane loads the weights of two adjacent outputs as ONE value: a 4-byte pair of bf16 (Wt = uint16_t) or
+// an 8-byte pair of f32 (Wt = float; N is even, so every row starts on an 8-byte boundary of an 8-byte aligned matrix).
+template <class Wt> struct ArPair;
+template <> struct ArPair<uint16_t> {
+    using type = uint32_t;
+    static __device__ __forceinline__ float lo(uint32_t w) { return bf_lo(w); }
+    static __device__ __forceinline__ float hi(uint32_t w) { return bf_hi(w); }
+};
+template <> struct ArPair<float> {
+    using type = float2;
+    static __device__ __forceinline__ float lo(const float2 &w) { return w.x; }
+    static __device__ __forceinline__ float hi(const float2 &w) { return w.y; }
+};
+
+// out[n] = act(sum_k in[k] W[k][n] (+ bias[n]) (+ add[n])), N even, W k-major bf16 or f32 with row length N.  `in` and `out` in
+// LDS, `part` = kSplit * N floats of LDS.  Ends with a barrier: `out` is visible to the whole workgroup.
+template <class Wt>
+__device__ void ar_gemv(const float *in, int K, const Wt *__restrict__ W, int N, const float *__restrict__ bias,
                         const float *__restrict__ add, bool leaky, float *out, float *part) {
+    using Pair = ArPair<Wt>;
+    using pair_t = typename Pair::type;
     const int P = N >> 1;
     const int kc = (K + kSplit - 1) / kSplit;
-    const uint32_t *W2 = reinterpret_cast<const uint32_t *>(W);
+    const pair_t *W2 = reinterpret_cast<const pair_t *>(W);
     for (int u = threadIdx.x; u < P * kSplit; u += kThreads) {
         const int s = u / P, p = u - s * P;
         const int k0 = s * kc, k1 = min(K, k0 + kc);
         float a0 = 0.f, a1 = 0.f;
-        const uint32_t *wp = W2 + (long long)k0 * P + p;
+        const pair_t *wp = W2 + (long long)k0 * P + p;
+        int k = k0;
+        if (sizeof(Wt) == 4) {
+            // f32 weights: the eight 8-byte loads of a block are issued before its first fmaf (left to itself the compiler waited
+            // for every load of the encoder's loop before issuing the next: one load in flight, 5 x the step time).  Same sums, same order.
+            for (; k + 8 <= k1; k += 8) {
+                pair_t w[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) w[j] = wp[(long long)j * P];
+                wp += 8LL * P;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float xv = in[k + j];
+                    a0 = fmaf(xv, Pair::lo(w[j]), a0);
+                    a1 = fmaf(xv, Pair::hi(w[j]), a1);
+                }
+            }
+        }
 #pragma unroll 8
-        for (int k = k0; k < k1; ++k) {
-            const uint32_t w = *wp;
+        for (; k < k1; ++k) {
+            const pair_t w = *wp;
             wp += P;
             const float xv = in[k];
-            a0 = fmaf(xv, bf_lo(w), a0);
-            a1 = fmaf(xv, bf_hi(w), a1);
+            a0 = fmaf(xv, Pair::lo(w), a0);
+            a1 = fmaf(xv, Pair::hi(w), a1);
         }
         part[s * N + 2 * p] = a0;
         part[s * N + 2 * p + 1] = a1;
@@ -189,7 +227,8 @@ __host__ __device__ inline LdsLayout ar_lds_layout(int M, int C1p, int C2p, int 
 }
 
 // CDF_LDS: the decoder's CDF rows are packed into LDS (otherwise each search reads a.cdfs in device memory).
-template <bool DECODE, bool CDF_LDS>
+// Wt: the type of the four weight matrices, uint16_t (bf16 bits) or float; everything but the weight load is the same code.
+template <bool DECODE, bool CDF_LDS, class Wt = uint16_t>
 __global__ __launch_bounds__(kThreads) void ar_scan_kernel(const sc2_ar_scan_args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int b = blockIdx.x;
@@ -235,10 +274,10 @@ __global__ __launch_bounds__(kThreads) void ar_scan_kernel(const sc2_ar_scan_arg
 
     const int PW = W + 4;
     float *yp = a.y_hat_pad + (long long)b * (H + 2) * PW * M;
-    const uint16_t *wc = static_cast<const uint16_t *>(a.wc);
-    const uint16_t *w1 = static_cast<const uint16_t *>(a.w1);
-    const uint16_t *w2 = static_cast<const uint16_t *>(a.w2);
-    const uint16_t *w3 = static_cast<const uint16_t *>(a.w3);
+    const Wt *wc = static_cast<const Wt *>(a.wc);
+    const Wt *w1 = static_cast<const Wt *>(a.w1);
+    const Wt *w2 = static_cast<const Wt *>(a.w2);
+    const Wt *w3 = static_cast<const Wt *>(a.w3);
     const float *bc = static_cast<const float *>(a.bc), *b2 = static_cast<const float *>(a.b2),
                 *b3 = static_cast<const float *>(a.b3), *p1 = static_cast<const float *>(a.p1);
     uint16_t *yo = static_cast<uint16_t *>(a.y_hat_nhwc);
@@ -338,9 +377,8 @@ __global__ __launch_bounds__(64) void rans_decode_resume_kernel(const uint8_t *b
     status[s] = ar_dec_status(d, last != 0);
 }
 
-}  // namespace
-
-extern "C" int sc2_ar_scan(const sc2_ar_scan_args *args, void *stream) {
+template <class Wt>
+int ar_scan_launch(const sc2_ar_scan_args *args, void *stream) {
     SC2_REQUIRE(args, SC2_ERR_INVALID_ARG, "ar_scan: null arguments");
     const sc2_ar_scan_args &a = *args;
     SC2_REQUIRE(a.B > 0 && a.H > 0 && a.W > 0 && a.M > 0 && a.M <= 512, SC2_ERR_INVALID_ARG, "ar_scan: bad dims");
@@ -352,6 +390,9 @@ extern "C" int sc2_ar_scan(const sc2_ar_scan_args *args, void *stream) {
                 "ar_scan: pixel range [%d, %d) outside %d x %d", a.pix0, a.pix1, a.H, a.W);
     SC2_REQUIRE(a.wc && a.bc && a.w1 && a.p1 && a.w2 && a.b2 && a.w3 && a.b3 && a.scale_table && a.y_hat_pad,
                 SC2_ERR_INVALID_ARG, "ar_scan: null weight / map argument");
+    // the f32 form loads a pair of adjacent weights as one 8-byte value (sc2_ar_scan's checks are what they were)
+    SC2_REQUIRE(sizeof(Wt) != 4 || ((uintptr_t)a.wc | (uintptr_t)a.w1 | (uintptr_t)a.w2 | (uintptr_t)a.w3) % 8 == 0,
+                SC2_ERR_INVALID_ARG, "ar_scan: the f32 weight matrices must be 8-byte aligned");
     SC2_REQUIRE(a.n_table >= 1 && a.n_table <= 256 && a.scale_bound > 0.f, SC2_ERR_INVALID_ARG, "ar_scan: scale table");
     long long entries = 0;
     if (a.decode) {
@@ -373,21 +414,27 @@ extern "C" int sc2_ar_scan(const sc2_ar_scan_args *args, void *stream) {
     SC2_REQUIRE(lds <= kLdsBytes, SC2_ERR_UNSUPPORTED, "ar_scan: %zu bytes of LDS needed (160 KiB available)", lds);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (a.decode && cdf_lds) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ar_scan_kernel<true, true>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ar_scan_kernel<true, true, Wt>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((ar_scan_kernel<true, true>), dim3(a.B), dim3(kThreads), lds, st, a);
+        hipLaunchKernelGGL((ar_scan_kernel<true, true, Wt>), dim3(a.B), dim3(kThreads), lds, st, a);
     } else if (a.decode) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ar_scan_kernel<true, false>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ar_scan_kernel<true, false, Wt>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((ar_scan_kernel<true, false>), dim3(a.B), dim3(kThreads), lds, st, a);
+        hipLaunchKernelGGL((ar_scan_kernel<true, false, Wt>), dim3(a.B), dim3(kThreads), lds, st, a);
     } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ar_scan_kernel<false, false>),
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&ar_scan_kernel<false, false, Wt>),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((ar_scan_kernel<false, false>), dim3(a.B), dim3(kThreads), lds, st, a);
+        hipLaunchKernelGGL((ar_scan_kernel<false, false, Wt>), dim3(a.B), dim3(kThreads), lds, st, a);
     }
     SC2_CHECK_LAUNCH();
     return SC2_OK;
 }
+
+}  // namespace
+
+extern "C" int sc2_ar_scan(const sc2_ar_scan_args *args, void *stream) { return ar_scan_launch<uint16_t>(args, stream); }
+
+extern "C" int sc2_ar_scan_f32(const sc2_ar_scan_args *args, void *stream) { return ar_scan_launch<float>(args, stream); }
 
 extern "C" int sc2_rans_decode_resume(const uint8_t *buf, int64_t stride, const int32_t *io_offset, const int32_t *io_nbytes,
                                       const int32_t *indexes, int n_streams, int64_t n_sym, const int32_t *cdfs, int n_cdfs,

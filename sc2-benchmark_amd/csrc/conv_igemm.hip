@@ -154,7 +154,11 @@ int conv2d_fwd_impl(const sc2_conv_desc *d, const void *x, const void *w_packed,
     const int K = d->KH * d->KW * d->Cin;
     SC2_REQUIRE(d->Kpad == sc2_conv_weight_pitch(K), SC2_ERR_INVALID_ARG, "conv2d: Kpad %d != %d", d->Kpad,
                 sc2_conv_weight_pitch(K));
-    SC2_REQUIRE(d->Cout_pad == sc2_conv_weight_rows(d->Cout), SC2_ERR_INVALID_ARG, "conv2d: Cout_pad %d != %d",
+    // (the squared-form GDN has 128-row tiles only: a narrow one, Cout <= 96, may bring its gamma zero-padded to 128 packed rows;
+    //  every read of ep_x / ep_beta and every store is guarded by n < Cout)
+    const bool narrow_sq = d->Cout_pad == 128 && d->Cout <= 96 &&
+                           (d->a_op == SC2_AOP_SQUARE || d->epilogue == SC2_EPI_GDN2 || d->epilogue == SC2_EPI_IGDN2);
+    SC2_REQUIRE(d->Cout_pad == sc2_conv_weight_rows(d->Cout) || narrow_sq, SC2_ERR_INVALID_ARG, "conv2d: Cout_pad %d != %d",
                 d->Cout_pad, sc2_conv_weight_rows(d->Cout));
     SC2_REQUIRE(d->a_op >= SC2_AOP_NONE && d->a_op <= SC2_AOP_SQUARE, SC2_ERR_INVALID_ARG, "conv2d: bad a_op");
     SC2_REQUIRE(d->k_order >= 0 && d->k_order <= 7 && (!(d->k_order & SC2_K_SLAB_MAJOR) || d->Cin % 32 == 0) &&

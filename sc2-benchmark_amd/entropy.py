@@ -241,8 +241,9 @@ class HipConvTranspose2d(nn.ConvTranspose2d):
                  out_format=hip.OUT_F32_NHWC, tag=tag, scatter=(rows, cols, out, sh, sw, ch, cw))
         return out
 
-    def forward_nhwc(self, x_nhwc, epilogue=hip.EPI_NONE, ep_beta=None, out_format=hip.OUT_BF16_NHWC):
-        """x bf16 [N,H,W,Cin] -> [N,(H-1)s-2p+k+op,(W-1)s-2p+k+op,Cout] (bf16, or f32 NHWC)."""
+    def forward_nhwc(self, x_nhwc, epilogue=hip.EPI_NONE, ep_beta=None, out_format=hip.OUT_BF16_NHWC, keep_pad=False):
+        """x bf16 [N,H,W,Cin] -> [N,(H-1)s-2p+k+op,(W-1)s-2p+k+op,Cout] (bf16, or f32 NHWC).  keep_pad: return the dense map of
+        Cout rounded up to a multiple of 8 channels the kernels write (the padding channels are zero: zero weights, zero bias)."""
         N, H, W, _ = x_nhwc.shape
         sh, sw = self.stride
         OH = (H - 1) * sh - 2 * self.padding[0] + self.kernel_size[0] + self.output_padding[0]
@@ -271,7 +272,7 @@ class HipConvTranspose2d(nn.ConvTranspose2d):
                 hip.conv2d_fwd(x_nhwc, packed, cpad, nkh, nkw, 1, (pad_h, pad_w), epilogue=epilogue, ep_beta=ep_beta,
                                out_format=out_format, tag=getattr(self, '_tag', None),
                                scatter=(rows, cols, out, sh, sw, ch, cw))
-        return out if cpad == cout else out[..., :cout]
+        return out if cpad == cout or keep_pad else out[..., :cout]
 
     def forward(self, x, output_size=None):
         _require_device(x, 'HipConvTranspose2d')
@@ -548,6 +549,22 @@ class GDN(GDN1):
     operand fragments and rsqrt / sqrt fused in the epilogue."""
 
     _precise_ops = (hip.AOP_SQUARE, hip.EPI_GDN2, hip.EPI_IGDN2)
+
+    def effective(self):
+        """As GDN1.effective(); a narrow layer (C <= 96) packs gamma zero-padded to 128 rows: the squared-form kernels have
+        128-row tiles only (csrc/conv_igemm.hip), and every channel past C is guarded there."""
+        C = self.in_channels
+        if C > 96:
+            return super().effective()
+        key = (self.beta._version, self.gamma._version, self.gamma.device, self.gamma.data_ptr())
+        if getattr(self, '_eff_key', None) != key:
+            with torch.no_grad():
+                beta = self.beta_reparam(self.beta).float().contiguous()
+                gamma = torch.zeros((128, C, 1, 1), dtype=self.gamma.dtype, device=self.gamma.device)
+                gamma[:C] = self.gamma_reparam(self.gamma).reshape(C, C, 1, 1)
+                self._eff = (beta, hip.pack_conv_weight(gamma))
+            self._eff_key = key
+        return self._eff
 
     def forward_nhwc(self, x_nhwc, out_format=hip.OUT_BF16_NHWC):
         beta, gamma_packed = self.effective()

@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     'sc2_pmf_to_quantized_cdf',
     'sc2_rans_max_bytes', 'sc2_rans_workspace_bytes', 'sc2_rans_encode_batch', 'sc2_rans_decode_batch', 'sc2_rans_decode_dequantize_batch', 'sc2_rans_decode_dequantize_batch_ev',
     'sc2_mse_partial_len', 'sc2_mse_sum_bf16', 'sc2_mse_grad_bf16', 'sc2_relu_bwd_bf16', 'sc2_relu_bwd_mse_bf16',
-    'sc2_ar_scan', 'sc2_rans_decode_resume',
+    'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
 ]
 
@@ -275,6 +275,7 @@ def lib():
     L.sc2_relu_bwd_bf16.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp]
     L.sc2_relu_bwd_mse_bf16.argtypes = [vp, vp, vp, vp, ctypes.c_longlong, i32, vp, vp]
     L.sc2_ar_scan.argtypes = [ctypes.POINTER(ArScanArgs), vp]
+    L.sc2_ar_scan_f32.argtypes = [ctypes.POINTER(ArScanArgs), vp]
     L.sc2_rans_decode_resume.argtypes = [vp, i64, vp, vp, vp, i32, i64, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.sc2_rans_host_tables_create.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp)]
     L.sc2_rans_host_tables_destroy.argtypes = [vp]
@@ -2048,7 +2049,9 @@ def ar_scan(weights, p1, y_hat_pad, y_hat_nhwc, scale_table, scale_bound, y=None
             pix=None, gaussian_params=None):
     """One scan over pixels pix = (pix0, pix1) of the B x H x W latent (all of it by default).
 
-    weights: dict wc / bc / w1 / w2 / b2 / w3 / b3 (bf16 k-major, f32 biases; see sc2_ar_scan_args); p1: f32 [B,H,W,C1p];
+    weights: dict wc / bc / w1 / w2 / b2 / w3 / b3 (k-major matrices, f32 biases; see sc2_ar_scan_args); the four matrices are
+    all bf16 (sc2_ar_scan) or all f32 (sc2_ar_scan_f32, timing tags ar_scan.enc.f32 / ar_scan.dec.f32): the dtype routes, and a
+    mixed dict raises Sc2Error before any launch.  p1: f32 [B,H,W,C1p];
     y_hat_pad: f32 [B,H+2,W+4,M] (updated in place); y_hat_nhwc: bf16 [B,H,W,M] or None.
     Encoder: y f32 [B,M,H,W], symbols / indexes i32 [B,H*W*M] (written).  Decoder: decode = dict buf / off / nb / cdfs /
     cdf_sizes / offsets / cdf_entries / st_x / st_pos / status (device tensors; state updated in place), symbols optional.
@@ -2058,9 +2061,14 @@ def ar_scan(weights, p1, y_hat_pad, y_hat_nhwc, scale_table, scale_bound, y=None
     assert tuple(y_hat_pad.shape) == (B, H + 2, W + 4, M) and y_hat_pad.dtype == torch.float32 and y_hat_pad.is_contiguous()
     assert p1.dtype == torch.float32 and p1.is_contiguous()
     C2p = weights['w2'].shape[1]
+    wdtypes = set(weights[name].dtype for name in ('wc', 'w1', 'w2', 'w3'))
+    if len(wdtypes) != 1 or not wdtypes <= {torch.bfloat16, torch.float32}:
+        raise Sc2Error('ar_scan: wc / w1 / w2 / w3 must be all bf16 or all f32, got {}'.format(
+            ', '.join('{} {}'.format(name, weights[name].dtype) for name in ('wc', 'w1', 'w2', 'w3'))))
+    wdtype = wdtypes.pop()
     for name in ('wc', 'bc', 'w1', 'w2', 'b2', 'w3', 'b3'):
         t = _dev(weights[name], name)
-        assert t.is_contiguous() and t.dtype == (torch.bfloat16 if name[0] == 'w' else torch.float32), name
+        assert t.is_contiguous() and t.dtype == (wdtype if name[0] == 'w' else torch.float32), name
     assert tuple(weights['wc'].shape) == (12 * M, 2 * M) and tuple(weights['w1'].shape) == (2 * M, C1p)
     assert tuple(weights['w2'].shape) == (C1p, C2p) and tuple(weights['w3'].shape) == (C2p, 2 * M)
     for t in (p1, y_hat_pad, scale_table):
@@ -2107,8 +2115,9 @@ def ar_scan(weights, p1, y_hat_pad, y_hat_nhwc, scale_table, scale_bound, y=None
                           ('cdf_sizes', 'cdf_sizes'), ('offsets', 'offsets'), ('st_x', 'st_x'), ('st_pos', 'st_pos'),
                           ('status', 'status')):
             setattr(a, name, d[key].data_ptr())
-    with _timed('ar_scan.{}'.format('dec' if decode is not None else 'enc')):
-        _check(lib().sc2_ar_scan(ctypes.byref(a), _stream()), 'ar_scan')
+    f32 = wdtype == torch.float32
+    with _timed('ar_scan.{}{}'.format('dec' if decode is not None else 'enc', '.f32' if f32 else '')):
+        _check((lib().sc2_ar_scan_f32 if f32 else lib().sc2_ar_scan)(ctypes.byref(a), _stream()), 'ar_scan')
 
 
 def rans_decode_resume(buf, off, nb, indexes, cdfs, cdf_sizes, offsets, state=None, last=True):
