@@ -777,6 +777,42 @@ int sc2_rans_decode_resume(const uint8_t *buf, int64_t stride, const int32_t *io
                            uint64_t *st_x, int32_t *st_pos, int32_t *status, int32_t *symbols_out, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* CR+BQ baseline (csrc/bq.hip): the 8-bit affine quantizer of `SimpleQuantizer` / `SimpleDequantizer`  */
+/* (sc2bench/transforms/misc.py:181-231 -> torchdistill tensor_util.quantize_tensor / dequantize_tensor) */
+/* and the two pooling layers of `larger_resnet_bottleneck` (sc2bench/models/layer.py:108-153).          */
+/* Plain grid-size kernels, no atomics; every result below is defined to the bit.                        */
+/* ------------------------------------------------------------------------------------------ */
+/* x: f32, n_seg contiguous segments of n_per_seg elements (n_seg = 1: the reference's per-tensor quantization; n_seg = N: one
+ * scale per image).  Per segment, in f32 and in this order, each step rounded once:
+ *   scale = (max - min) / 255;  izp = 0 - min / scale;  zero_point = (int)clamp(izp, 0, 255);
+ *   q = u8(rint(clamp(zero_point + x / scale, 0, 255)))          (rint: half to even; both divisions correctly rounded)
+ * min / max as torch.min / torch.max (a NaN makes both NaN).  status[seg] bit 1: izp is NaN (a NaN in the segment, or an all-zero
+ * segment: 0 / 0) -- the reference raises ValueError from int(nan) there; q of that segment is 0.  A non-zero constant segment is
+ * no error (scale 0, IEEE infinities: codes all 255 with zero point 0, or all 0 with zero point 255).
+ * Two launches: per-workgroup (min, max) pairs into partial [sc2_bq_partial_len(n_seg, n_per_seg)] f32, then every workgroup reduces
+ * its segment's pairs again and quantizes its share.  q: u8 in x's order; scale f32 / zero_point i32 / status i32: [n_seg]. */
+long long sc2_bq_partial_len(long long n_seg, long long n_per_seg);
+int sc2_bq_quantize(const float *x, uint8_t *q, float *scale, int32_t *zero_point, int32_t *status, float *partial, long long n_seg,
+                    long long n_per_seg, void *stream);
+/* y = scale[seg] * ((float)q - (float)zero_point[seg]): one exact subtraction, one multiply; y f32 in q's order.  scale and
+ * zero_point are DEVICE arrays [n_seg]. */
+int sc2_bq_dequantize(const uint8_t *q, const float *scale, const int32_t *zero_point, float *y, long long n_seg, long long n_per_seg,
+                      void *stream);
+/* The same from u8 NCHW codes [N,C,H,W] to a bf16 NHWC map [N,H,W,Cpad] (Cpad % 8 == 0, channels >= C exact zeros), with an optional
+ * per-channel affine (a, b: f32 [C], both or neither -- the decoder's leading eval-mode BatchNorm2d) and ReLU:
+ * relu(fmaf(a_c, scale * (q - zp), b_c)) in f32, rounded to bf16 once.  per_sample: scale / zero_point are [N], else [1]. */
+int sc2_bq_dequantize_nhwc(const uint8_t *q, const float *scale, const int32_t *zero_point, int per_sample, const float *a,
+                           const float *b, int relu, void *y, int N, int C, int H, int W, int Cpad, void *stream);
+/* nn.MaxPool2d + eval-mode nn.BatchNorm2d + ReLU on a bf16 NHWC map (layer.py:133-135): sc2_maxpool_nhwc's window walk, then
+ * relu(fmaf(a_c, max, b_c)) in f32 rounded to bf16 once -- the affine AFTER the max (a_c may be negative).  a, b: f32 [C], 16-byte
+ * aligned; C % 8 == 0. */
+int sc2_maxpool_affine_relu_nhwc(const void *x, void *y, const float *a, const float *b, int N, int H, int W, int C, int KH, int KW,
+                                 int stride_h, int stride_w, int pad_h, int pad_w, void *stream);
+/* nn.AvgPool2d(kernel, stride, no padding) on a bf16 NHWC map (layer.py:149: kernel 2, stride 1): f32 sum over the window in
+ * row-major order, times 1 / kernel^2, rounded to bf16 once.  x [N,H,W,C] -> y [N,OH,OW,C], C % 8 == 0. */
+int sc2_avgpool2d_nhwc(const void *x, void *y, int N, int H, int W, int C, int kernel, int stride, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Diagnostics (csrc/diag.hip; no product path calls these).                                    */
 /* ------------------------------------------------------------------------------------------ */
 /* The shader clock the chip holds while OTHER kernels run: `n_workgroups` probe waves (one per workgroup; launch >= 8 so that

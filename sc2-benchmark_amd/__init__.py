@@ -6,18 +6,19 @@ repository root loads it under the module name ``sc2bench_amd``.
 from . import hip  # noqa: F401
 from .analysis import ANALYZER_CLASS_DICT, AnalyzableModule, FileSizeAccumulator, FileSizeAnalyzer  # noqa: F401
 from .backbone import (BACKBONE_CLASS_DICT, BACKBONE_FUNC_DICT, MODEL_DICT, FeatureExtractionBackbone,  # noqa: F401
-                       SplittableResNet, UpdatableBackbone, check_if_updatable, get_backbone, splittable_resnet)
+                       SplittableResNet, UpdatableBackbone, check_if_updatable, custom_resnet50, get_backbone, splittable_resnet)
 from .entropy import (CompressionModel, EntropyBottleneck, GDN1, GaussianConditional, HipConv2d,  # noqa: F401
                       HipConvTranspose2d, LowerBound, NonNegativeParametrizer, get_scale_table)
 from .layer import (LAYER_CLASS_DICT, LAYER_FUNC_DICT, BaseBottleneck, EntropyBottleneckLayer,  # noqa: F401
-                    FPBasedResNetBottleneck, MSHPBasedResNetBottleneck, SHPBasedResNetBottleneck, get_layer,
-                    register_layer_class, register_layer_func)
+                    FPBasedResNetBottleneck, MSHPBasedResNetBottleneck, SHPBasedResNetBottleneck, SimpleBottleneck, get_layer,
+                    larger_resnet_bottleneck, register_layer_class, register_layer_func)
 from .loss import BppLoss  # noqa: F401
 from .compression import (COMPRESSION_MODEL_CLASS_DICT, COMPRESSION_MODEL_FUNC_DICT, FactorizedPrior,  # noqa: F401
                           JointAutoregressiveHierarchicalPriors, MeanScaleHyperprior, ScaleHyperprior,
                           bmshj2018_factorized, bmshj2018_hyperprior, get_compression_model, mbt2018, mbt2018_mean)
 from .entropy import GDN  # noqa: F401
-from .transforms import AdaptivePad, PILImageModule, PILTensorModule  # noqa: F401
+from .transforms import (AdaptivePad, PILImageModule, PILTensorModule, QuantizedTensor, SimpleDequantizer,  # noqa: F401
+                         SimpleQuantizer, dequantize_tensor, quantize_tensor)
 from .wrapper import (WRAPPER_CLASS_DICT, CodecFeatureCompressionClassifier, CodecInputCompressionClassifier,  # noqa: F401
                       EntropicClassifier, NeuralInputCompressionClassifier, SplitClassifier, wrap_model)
 

@@ -284,8 +284,9 @@ class SplittableResNet(UpdatableBackbone):
         return self._hip_head
 
     def head(self, x):
+        # (a head that starts at layer3 -- the CR+BQ baseline's -- is built from whichever layers exist, like one with layer2)
         if (self.compute_dtype == 'bf16' and self.use_hip_head and not self.training and x.is_cuda
-                and x.dtype == torch.bfloat16 and self.layer2 is not None):
+                and x.dtype == torch.bfloat16 and (self.layer2 is not None or (self.layer3 is not None and self.layer4 is not None))):
             x_nhwc = x.permute(0, 2, 3, 1).contiguous()   # a view when x is channels_last (the decoder's output)
             return self._hip_head_for_eval().forward(x_nhwc, with_pool=self.avgpool is not None)
         if self.layer2 is not None:
@@ -491,6 +492,18 @@ def splittable_resnet(bottleneck_config, resnet_name='resnet50', inplanes=None, 
         load_ckpt(org_model_ckpt_file_path_or_url, model=resnet_model, strict=org_ckpt_strict)
     return SplittableResNet(bottleneck_layer, resnet_model, inplanes, skips_avgpool, skips_fc,
                             pre_transform, analysis_config, short_module_names=short_module_names)
+
+
+def custom_resnet50(bottleneck_channel=12, bottleneck_idx=7, compressor=None, decompressor=None, short_module_names=None, **kwargs):
+    """The reference's hub entry of the CR+BQ baseline (hubconf.py:16-35): ResNet-50 whose stem .. layer2 are replaced by
+    `larger_resnet_bottleneck`; by default layer3, layer4, avgpool and fc follow."""
+    if short_module_names is None:
+        short_module_names = ['layer3', 'layer4', 'avgpool', 'fc']
+    bottleneck_config = {'key': 'larger_resnet_bottleneck',
+                         'kwargs': {'bottleneck_channel': bottleneck_channel, 'bottleneck_idx': bottleneck_idx,
+                                    'compressor_transform': compressor, 'decompressor_transform': decompressor}}
+    return splittable_resnet(bottleneck_config, resnet_name='resnet50', skips_avgpool='avgpool' not in short_module_names,
+                             skips_fc='fc' not in short_module_names, short_module_names=short_module_names, **kwargs)
 
 
 def get_backbone(cls_or_func_name, **kwargs):

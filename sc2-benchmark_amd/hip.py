@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     'sc2_rans_max_bytes', 'sc2_rans_workspace_bytes', 'sc2_rans_encode_batch', 'sc2_rans_decode_batch', 'sc2_rans_decode_dequantize_batch', 'sc2_rans_decode_dequantize_batch_ev',
     'sc2_mse_partial_len', 'sc2_mse_sum_bf16', 'sc2_mse_grad_bf16', 'sc2_relu_bwd_bf16', 'sc2_relu_bwd_mse_bf16',
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
+    'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
 ]
 
@@ -277,6 +278,13 @@ def lib():
     L.sc2_ar_scan.argtypes = [ctypes.POINTER(ArScanArgs), vp]
     L.sc2_ar_scan_f32.argtypes = [ctypes.POINTER(ArScanArgs), vp]
     L.sc2_rans_decode_resume.argtypes = [vp, i64, vp, vp, vp, i32, i64, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.sc2_bq_partial_len.argtypes = [i64, i64]
+    L.sc2_bq_partial_len.restype = i64
+    L.sc2_bq_quantize.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, vp]
+    L.sc2_bq_dequantize.argtypes = [vp, vp, vp, vp, i64, i64, vp]
+    L.sc2_bq_dequantize_nhwc.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
+    L.sc2_maxpool_affine_relu_nhwc.argtypes = [vp, vp, vp, vp] + [i32] * 10 + [vp]
+    L.sc2_avgpool2d_nhwc.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp]
     L.sc2_rans_host_tables_create.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp)]
     L.sc2_rans_host_tables_destroy.argtypes = [vp]
     L.sc2_rans_host_tables_destroy.restype = None
@@ -942,6 +950,114 @@ def maxpool_nhwc(x_nhwc, kernel, stride, pad, tag=None):
     with _timed(tag or 'maxpool'):
         _check(lib().sc2_maxpool_nhwc(_ptr(x_nhwc), _ptr(out), N, H, W, C, kh, kw, sh, sw, ph, pw, _stream()), 'maxpool_nhwc')
     return out
+
+
+def maxpool_affine_relu_nhwc(x_nhwc, a, b, kernel, stride, pad, tag=None):
+    """nn.MaxPool2d (floor mode) + a per-channel affine (an eval-mode BatchNorm2d: a, b f32 [C]) + ReLU on a bf16 NHWC map
+    [N,H,W,C], C % 8 == 0 -> [N,OH,OW,C]: relu(fma(a_c, max, b_c)) in f32, rounded to bf16 once.  The affine follows the max."""
+    _dev(x_nhwc, 'x')
+    assert x_nhwc.dtype == torch.bfloat16 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
+    N, H, W, C = x_nhwc.shape
+    for t in (_dev(a, 'a'), _dev(b, 'b')):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C
+    (kh, kw), (sh, sw), (ph, pw) = [(v, v) if isinstance(v, int) else tuple(v) for v in (kernel, stride, pad)]
+    out = torch.empty((N, (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1, C), dtype=torch.bfloat16, device=x_nhwc.device)
+    with _timed(tag or 'maxpool_affine_relu'):
+        _check(lib().sc2_maxpool_affine_relu_nhwc(_ptr(x_nhwc), _ptr(out), _ptr(a), _ptr(b), N, H, W, C, kh, kw, sh, sw, ph, pw, _stream()),
+               'maxpool_affine_relu_nhwc')
+    return out
+
+
+def avgpool2d_nhwc(x_nhwc, kernel, stride, tag=None):
+    """nn.AvgPool2d(kernel, stride) without padding on a bf16 NHWC map [N,H,W,C], C % 8 == 0 -> [N,OH,OW,C] (f32 sum in window
+    order, times 1 / kernel^2, rounded once)."""
+    _dev(x_nhwc, 'x')
+    assert x_nhwc.dtype == torch.bfloat16 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
+    N, H, W, C = x_nhwc.shape
+    kernel, stride = int(kernel), int(stride)
+    if not (0 < kernel <= min(H, W) and stride > 0):
+        raise ValueError('avgpool2d_nhwc: kernel {} / stride {} on a {}x{} map'.format(kernel, stride, H, W))
+    out = torch.empty((N, (H - kernel) // stride + 1, (W - kernel) // stride + 1, C), dtype=torch.bfloat16, device=x_nhwc.device)
+    with _timed(tag or 'avgpool2d'):
+        _check(lib().sc2_avgpool2d_nhwc(_ptr(x_nhwc), _ptr(out), N, H, W, C, kernel, stride, _stream()), 'avgpool2d_nhwc')
+    return out
+
+
+# --------------------------------------------------------------------------------------------- #
+# CR+BQ baseline: 8-bit affine quantizer (csrc/bq.hip)
+# --------------------------------------------------------------------------------------------- #
+def bq_quantize(x, per_sample=False, tag=None):
+    """torchdistill's `quantize_tensor(x, 8)` on the device.  x: f32, any shape (made contiguous) -> (q u8 like x, scale f32 [S],
+    zero_point i32 [S], status i32 [S]) with S = 1 (the whole tensor, the reference's behaviour) or, `per_sample`, S = x.shape[0]
+    (one scale per image).  status bit 1: the reference would raise ValueError (a NaN, or an all-zero segment).  Nothing here
+    synchronises: the four results are device tensors."""
+    _dev(x, 'x')
+    assert x.dtype == torch.float32 and x.numel() > 0
+    x = x.contiguous()
+    assert not per_sample or x.dim() >= 1
+    n_seg = int(x.shape[0]) if per_sample else 1
+    n_per_seg = x.numel() // n_seg
+    q = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    scale = torch.empty(n_seg, dtype=torch.float32, device=x.device)
+    zs = torch.empty((2, n_seg), dtype=torch.int32, device=x.device)    # one buffer: bq_read_params brings both in one copy
+    zero_point, status = zs[0], zs[1]
+    partial = torch.empty(int(lib().sc2_bq_partial_len(n_seg, n_per_seg)), dtype=torch.float32, device=x.device)
+    with _timed(tag or 'bq.quantize'):
+        _check(lib().sc2_bq_quantize(_ptr(x), _ptr(q), _ptr(scale), _ptr(zero_point), _ptr(status), _ptr(partial), n_seg, n_per_seg,
+                                     _stream()), 'bq_quantize')
+    return q, scale, zero_point, status
+
+
+def bq_read_params(zero_point, status):
+    """(zero points, statuses) of one `bq_quantize` call as Python lists: one device-to-host copy (the call's only synchronisation)"""
+    base = zero_point._base
+    if base is None or base is not status._base or base.shape != (2, zero_point.numel()):
+        base = torch.stack([zero_point, status])
+    host = base.tolist()
+    return host[0], host[1]
+
+
+def _bq_params(q, scale, zero_point):
+    """scale (f32 tensor, 0-dim or [S]) and zero_point (int, or integer tensor [S]) as device arrays beside q: (scale, zp, S)"""
+    scale = _dev(scale, 'scale').detach().reshape(-1).to(torch.float32).contiguous()
+    if isinstance(zero_point, torch.Tensor):
+        zp = zero_point.to(device=q.device, dtype=torch.int32).reshape(-1).contiguous()
+    else:       # a Python int (the reference's form): a fill launch, no copy from the host
+        zp = torch.full((1,), int(zero_point), dtype=torch.int32, device=q.device)
+    if scale.numel() != zp.numel() or scale.numel() not in (1, q.shape[0] if q.dim() else 1):
+        raise ValueError('bq_dequantize: {} scales and {} zero points for codes of shape {}'.format(
+            scale.numel(), zp.numel(), tuple(q.shape)))
+    return scale, zp, scale.numel()
+
+
+def bq_dequantize(q, scale, zero_point, out_format=OUT_F32_NCHW, affine=None, relu=False, cpad=None, tag=None):
+    """torchdistill's `dequantize_tensor`: scale * (q.float() - zero_point), scale and zero point read from device memory.
+    scale: f32 tensor, 0-dim / [1] (per tensor) or [q.shape[0]] (per image); zero_point: int or integer tensor likewise.
+    out_format OUT_F32_NCHW -> f32 like q (any shape).  OUT_BF16_NHWC (q: u8 [N,C,H,W]) -> bf16 [N,H,W,cpad] with channels zero-padded
+    to `cpad` (default: the next multiple of 8), after the optional `affine` = (a, b) f32 [C] and `relu`: relu(fma(a, v, b))."""
+    _dev(q, 'q')
+    assert q.dtype == torch.uint8 and q.numel() > 0
+    q = q.contiguous()
+    scale, zp, n_seg = _bq_params(q, scale, zero_point)
+    if out_format == OUT_F32_NCHW:
+        assert affine is None and not relu
+        y = torch.empty(q.shape, dtype=torch.float32, device=q.device)
+        with _timed(tag or 'bq.dequantize'):
+            _check(lib().sc2_bq_dequantize(_ptr(q), _ptr(scale), _ptr(zp), _ptr(y), n_seg, q.numel() // n_seg, _stream()), 'bq_dequantize')
+        return y
+    assert out_format == OUT_BF16_NHWC and q.dim() == 4
+    N, C, H, W = q.shape
+    cpad = (C + 7) // 8 * 8 if cpad is None else int(cpad)
+    a = b = None
+    if affine is not None:
+        a, b = affine
+        for t in (_dev(a, 'a'), _dev(b, 'b')):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C
+    y = torch.empty((N, H, W, cpad), dtype=torch.bfloat16, device=q.device)
+    with _timed(tag or 'bq.dequantize'):
+        _check(lib().sc2_bq_dequantize_nhwc(_ptr(q), _ptr(scale), _ptr(zp), 1 if n_seg > 1 else 0, _ptr(a), _ptr(b),
+                                            1 if relu else 0, _ptr(y), N, C, H, W, cpad, _stream()), 'bq_dequantize_nhwc')
+    return y
 
 
 def bn_train_fwd(x_nhwc, gamma, beta, running_mean, running_var, momentum, eps, relu, residual=None, tag=None):

@@ -900,6 +900,231 @@ class MSHPBasedResNetBottleneck(SHPBasedResNetBottleneck):
         return self._forward2train(x)
 
 
+# ------------------------------------------------------------------------------------------------------------------ CR+BQ
+def _bn_affine(bn):
+    """eval-mode BatchNorm2d as y = a * x + b: (a, b) f32 [C]"""
+    var, mean = bn.running_var.detach().float(), bn.running_mean.detach().float()
+    gamma = bn.weight.detach().float() if bn.weight is not None else torch.ones_like(var)
+    beta = bn.bias.detach().float() if bn.bias is not None else torch.zeros_like(var)
+    a = gamma * torch.rsqrt(var + bn.eps)
+    return a.contiguous(), (beta - mean * a).contiguous()
+
+
+def _pad_dim(t, dim, size):
+    if t.shape[dim] == size:
+        return t
+    shape = list(t.shape)
+    shape[dim] = size - t.shape[dim]
+    return torch.cat([t, t.new_zeros(shape)], dim)
+
+
+def _sole_transform(module, cls):
+    """`module` if it is a `cls`, the member of a one-transform `Compose` if that is one, else None"""
+    if isinstance(module, cls):
+        return module
+    members = getattr(module, 'transforms', None)
+    if isinstance(members, (list, tuple)) and len(members) == 1 and isinstance(members[0], cls):
+        return members[0]
+    return None
+
+
+# the module sequence of `larger_resnet_bottleneck`: (type, (in, out, kernel, stride, padding) of a conv) -- None: the bottleneck width
+_BQ_SEQUENCE = (('conv', (3, 64, 7, 2, 3)), ('bn', 64), ('relu',), ('maxpool',), ('bn', 64), ('relu',),
+                ('conv', (64, None, 2, 2, 1)), ('bn', None), ('relu',),
+                ('conv', (None, 512, 2, 1, 1)), ('bn', 512), ('relu',), ('conv', (512, 512, 2, 1, 1)), ('bn', 512), ('relu',),
+                ('conv', (512, 512, 2, 1, 0)), ('bn', 512), ('relu',), ('conv', (512, 512, 2, 1, 0)), ('avgpool',))
+
+
+class _BqHipPlan(object):
+    """Eval-mode `larger_resnet_bottleneck` on the library's kernels: every BatchNorm2d folded into the convolution in front of
+    it (bf16 weights, f32 bias, ReLU in the epilogue) except the two that follow no convolution -- the one behind the max-pool
+    (`hip.maxpool_affine_relu_nhwc`) and, for bottleneck_idx 7, the decoder's first (`hip.bq_dequantize`'s affine)."""
+
+    def __init__(self, mods, idx, channels):
+        from .head import ConvSpec, _Conv
+        self.idx, self.channels = idx, channels
+        self.cpad = (channels + 7) // 8 * 8
+        w = _pad_dim(mods[0].weight.detach().float(), 1, 8)       # 3 input channels -> 8 (zeros): 16-byte channel runs
+        self.stem = _Conv(ConvSpec(w, mods[0].stride, mods[0].padding), mods[1], 'bq.stem')
+        mp = mods[3]
+        self.pool = (mp.kernel_size, mp.stride, mp.padding)
+        self.pool_affine = _bn_affine(mods[4])
+        # the bottleneck convolution: output channels zero-padded to a multiple of 8 (the kernels' granularity); its norm layer
+        # belongs to the encoder only when bottleneck_idx is 9
+        w = mods[6].weight.detach().float()
+        bias = torch.zeros(self.cpad, dtype=torch.float32, device=w.device)
+        if idx == 9:
+            a, b = _bn_affine(mods[7])
+            w = w * a.reshape(-1, 1, 1, 1)
+            bias[:channels] = b
+        self.conv_z = _Conv(ConvSpec(_pad_dim(w, 0, self.cpad), mods[6].stride, mods[6].padding), None, 'bq.conv_z')
+        self.conv_z.b = bias
+        self.dq_affine = _bn_affine(mods[7]) if idx == 7 else None
+        w = _pad_dim(mods[9].weight.detach().float(), 1, self.cpad)
+        self.dec = [_Conv(ConvSpec(w, mods[9].stride, mods[9].padding), mods[10], 'bq.dec0'),
+                    _Conv(mods[12], mods[13], 'bq.dec1'), _Conv(mods[15], mods[16], 'bq.dec2'), _Conv(mods[18], None, 'bq.dec3')]
+        ap = mods[19]
+        self.avgpool = (int(ap.kernel_size if isinstance(ap.kernel_size, int) else ap.kernel_size[0]),
+                        int(ap.stride if isinstance(ap.stride, int) else ap.stride[0]))
+
+    def analysis(self, x):
+        """f32 NCHW images -> the latent the compressor sees: f32 [N, channels, h, w]"""
+        h = hip.nchw_f32_to_nhwc_bf16(x.float().contiguous(), 8, tag='bq.layout')
+        h = self.stem(h, hip.EPI_BIAS_RELU)
+        h = hip.maxpool_affine_relu_nhwc(h, self.pool_affine[0], self.pool_affine[1], *self.pool, tag='bq.pool')
+        c = self.conv_z
+        z = hip.conv2d_fwd(h, c.w, c.cout, c.k[0], c.k[1], c.stride, c.pad, epilogue=hip.EPI_BIAS_RELU if self.idx == 9 else hip.EPI_NONE,
+                           ep_beta=c.b, out_format=hip.OUT_F32_NCHW, tag=c.tag, k_order=c.k_order)
+        return z if self.cpad == self.channels else z[:, :self.channels].contiguous()
+
+    def synthesis(self, q_x, output_format):
+        """QuantizedTensor (u8 codes on the device) -> decoder output: bf16 [N, 512, H, W] as a view of NHWC memory, or f32 NCHW"""
+        h = hip.bq_dequantize(q_x.tensor, q_x.scale, q_x.zero_point, out_format=hip.OUT_BF16_NHWC, affine=self.dq_affine,
+                              relu=self.idx == 7, cpad=self.cpad)
+        for conv in self.dec[:3]:
+            h = conv(h, hip.EPI_BIAS_RELU)
+        h = self.dec[3](h, hip.EPI_NONE)
+        h = hip.avgpool2d_nhwc(h, self.avgpool[0], self.avgpool[1], tag='bq.avgpool')
+        if output_format == 'bf16_nhwc':
+            return h.permute(0, 3, 1, 2)
+        return hip.nhwc_bf16_to_nchw_f32(h)
+
+
+class SimpleBottleneck(nn.Module):
+    """Encoder / decoder pair whose encoder output is the bottleneck (layer.py:41-105): encoder -> compressor (if given) ->
+    decompressor (if given) -> decoder in eval mode, encoder -> decoder in training mode.
+
+    A `larger_resnet_bottleneck` split at 7 or 9 with at most 16 bottleneck channels runs its eval forward on a device tensor
+    on the library's kernels (`analysis`, `_BqHipPlan`); every other geometry, training mode, grad mode and CPU tensors run the
+    torch modules.  `output_format` ('f32_nchw' | 'bf16_nhwc', set by the backbone's `set_compute_dtype`) is what `decode`
+    hands to the task head on a device tensor in eval mode."""
+
+    def __init__(self, encoder, decoder, compressor=None, decompressor=None):
+        super().__init__()
+        self.encoder = encoder
+        self.decoder = decoder
+        self.compressor = compressor
+        self.decompressor = decompressor
+        self.output_format = 'f32_nchw'
+        self.bottleneck_idx = None      # set by the builders whose module sequence the HIP path knows
+        self._bq_plan = None
+
+    def _hip_geometry(self):
+        """(modules, idx, channels) when encoder + decoder are `larger_resnet_bottleneck`'s sequence in eval mode split at 7 / 9"""
+        idx = self.bottleneck_idx
+        if idx not in (7, 9) or not isinstance(self.encoder, nn.Sequential) or not isinstance(self.decoder, nn.Sequential):
+            return None
+        mods = list(self.encoder) + list(self.decoder)
+        if len(self.encoder) != idx or len(mods) != len(_BQ_SEQUENCE):
+            return None
+        channels = mods[6].out_channels if isinstance(mods[6], nn.Conv2d) else 0
+        if not 0 < channels <= 16:
+            return None
+        for m, want in zip(mods, _BQ_SEQUENCE):
+            if want[0] == 'conv':
+                geo = tuple(channels if v is None else v for v in want[1])
+                if not (type(m) is nn.Conv2d and m.bias is None and m.groups == 1 and m.dilation == (1, 1) and
+                        (m.in_channels, m.out_channels) == geo[:2] and m.kernel_size == (geo[2],) * 2 and
+                        m.stride == (geo[3],) * 2 and m.padding == (geo[4],) * 2):
+                    return None
+            elif want[0] == 'bn':
+                if not (type(m) is nn.BatchNorm2d and not m.training and m.track_running_stats and m.running_mean is not None and
+                        m.num_features == (channels if want[1] is None else want[1])):
+                    return None
+            elif want[0] == 'relu':
+                if type(m) is not nn.ReLU:
+                    return None
+            elif want[0] == 'maxpool':
+                if not (type(m) is nn.MaxPool2d and m.dilation in (1, (1, 1)) and not m.ceil_mode and not m.return_indices):
+                    return None
+            elif not (type(m) is nn.AvgPool2d and m.padding in (0, (0, 0)) and not m.ceil_mode and m.divisor_override is None and
+                      m.kernel_size in (2, (2, 2)) and m.stride in (1, (1, 1))):
+                return None
+        return mods, idx, channels
+
+    def _hip_plan(self, x):
+        """the folded HIP form for this call, or None: eval mode without grad on a device tensor, a known geometry"""
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and not self.training and not torch.is_grad_enabled()):
+            return None
+        geometry = self._hip_geometry()
+        if geometry is None:
+            return None
+        # rebuilt when a parameter or buffer changes: in place (its version) or replaced (its address), as SplittableResNet's head
+        tensors = list(self.encoder.parameters()) + list(self.encoder.buffers()) + list(self.decoder.parameters()) + \
+            list(self.decoder.buffers())
+        key = tuple((t._version, t.data_ptr()) for t in tensors) + (geometry[1], str(x.device))
+        if self._bq_plan is None or self._bq_plan[0] != key:
+            with torch.inference_mode(False), torch.no_grad():
+                self._bq_plan = (key, _BqHipPlan(*geometry))
+        return self._bq_plan[1]
+
+    def analysis(self, x):
+        """the encoder's output, in front of the compressor"""
+        plan = self._hip_plan(x)
+        return plan.analysis(x) if plan is not None else self.encoder(x)
+
+    def encode(self, x):
+        z = self.analysis(x)
+        if self.compressor is not None:
+            z = self.compressor(z)
+        return {'z': z}
+
+    def decode(self, z):
+        from .transforms import QuantizedTensor, SimpleDequantizer
+        codes = z.tensor if isinstance(z, QuantizedTensor) else None
+        plan = self._hip_plan(codes) if codes is not None and codes.dtype == torch.uint8 else None
+        dequantizer = _sole_transform(self.decompressor, SimpleDequantizer) if plan is not None else None
+        if dequantizer is not None and dequantizer.num_bits != 16 and codes.dim() == 4 and codes.shape[1] == plan.channels:
+            return plan.synthesis(z, self.output_format)
+        if self.decompressor is not None:
+            z = self.decompressor(z)
+        y = self.decoder(z)
+        if self.output_format == 'bf16_nhwc' and y.is_cuda and not self.training and not torch.is_grad_enabled():
+            y = y.to(dtype=torch.bfloat16, memory_format=torch.channels_last)     # what the bf16 task head takes
+        return y
+
+    def forward(self, x):
+        if not self.training:
+            return self.decode(**self.encode(x))
+        return self.decoder(self.encoder(x))
+
+    def update(self):
+        """nothing to update: this layer has no entropy model (kept for the callers that update every bottleneck)"""
+        import logging
+        logging.getLogger(__name__).info('This module has no updatable parameters for entropy coding')
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state['_bq_plan'] = None          # packed device weights of a cache do not belong in a pickle
+        return state
+
+
+@register_layer_func
+def larger_resnet_bottleneck(bottleneck_channel=12, bottleneck_idx=7, compressor_transform=None, decompressor_transform=None):
+    """ResNet-50/-101/-152 compatible bottleneck of Matsubara et al.'s head network distillation (layer.py:108-153): 20 modules,
+    the first `bottleneck_idx` of them the encoder.  Same signature as the reference (its `ghnd-bq` configs pass an
+    `output_channel` this builder does not take, and fail with the same TypeError here)."""
+    width = bottleneck_channel
+
+    def conv(cin, cout, stride=1, padding=0, kernel=2):
+        return nn.Conv2d(cin, cout, kernel_size=kernel, stride=stride, padding=padding, bias=False)
+
+    def norm_relu(c):
+        return [nn.BatchNorm2d(c), nn.ReLU(inplace=True)]
+
+    stack = [conv(3, 64, stride=2, padding=3, kernel=7)] + norm_relu(64)
+    stack += [nn.MaxPool2d(kernel_size=3, stride=2, padding=1)] + norm_relu(64)
+    stack += [conv(64, width, stride=2, padding=1)] + norm_relu(width)
+    stack += [conv(width, 512, padding=1)] + norm_relu(512)
+    stack += [conv(512, 512, padding=1)] + norm_relu(512)
+    stack += [conv(512, 512)] + norm_relu(512)
+    stack += [conv(512, 512), nn.AvgPool2d(kernel_size=2, stride=1)]
+    layer = SimpleBottleneck(nn.Sequential(*stack[:bottleneck_idx]), nn.Sequential(*stack[bottleneck_idx:]),
+                             compressor_transform, decompressor_transform)
+    layer.bottleneck_idx = bottleneck_idx
+    return layer
+
+
 def get_layer(cls_or_func_name, **kwargs):
     """Gets a layer module by registered class or function name (layer.py:820-835)."""
     if cls_or_func_name in LAYER_CLASS_DICT:

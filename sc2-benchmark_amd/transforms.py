@@ -10,8 +10,12 @@ image; `config.resolve` maps `torchvision.transforms.<Name>` here).
 * `AdaptivePad` -- sc2bench/transforms/misc.py:105-154 (tests 'equal_side', otherwise pads right and bottom).
 * `Compose`, `Resize`, `CenterCrop`, `ToTensor`, `Normalize`, `RandomResizedCrop`, `RandomHorizontalFlip` -- torchvision
   semantics on PIL images / tensors, PIL + torch only.
-These run on the host (PIL codecs are host code in the reference too); they are callers of the hot path, not part of it.
+* `SimpleQuantizer` / `SimpleDequantizer` -- misc.py:181-231, the 8-bit affine quantizer of the CR+BQ baseline, with
+  torchdistill's `QuantizedTensor` / `quantize_tensor` / `dequantize_tensor` (tensor_util) restated here.  On a device tensor the
+  8-bit form runs on the library's kernels (csrc/bq.hip), on a CPU tensor on torch ops; both give the same bits.
+Everything else runs on the host (PIL codecs are host code in the reference too): callers of the hot path, not part of it.
 """
+import collections
 import math
 import random
 from io import BytesIO
@@ -268,6 +272,86 @@ class AdaptivePad(nn.Module):
 class ClearTargetTransform(nn.Module):
     def forward(self, sample, *args):
         return sample, list()
+
+
+# torchdistill.common.tensor_util.QuantizedTensor: module-level, so that FileSizeAnalyzer can pickle it
+QuantizedTensor = collections.namedtuple('QuantizedTensor', ['tensor', 'scale', 'zero_point'])
+
+
+def _nan_zero_point():
+    # what the reference's `int(zero_point)` raises when the zero point is NaN (a NaN in the tensor, or an all-zero one: 0 / 0)
+    raise ValueError('cannot convert float NaN to integer')
+
+
+def quantize_tensor(x, num_bits=8, per_sample=False):
+    """torchdistill's `quantize_tensor` (Jacob et al., asymmetric, unsigned): f32 arithmetic, in this order --
+    scale = (max - min) / (2^bits - 1); zero_point = int(clamp(0 - min / scale, 0, 2^bits - 1));
+    q = (zero_point + x / scale).clamp(0, 2^bits - 1).round().byte().  -> QuantizedTensor(q, scale 0-dim tensor on x's device,
+    zero_point Python int).  A positive tensor therefore saturates (zero point 0): the reference's behaviour, kept.
+    `per_sample=True` (not in the reference): one scale and zero point per x[i] -- what the reference's batch-size-1 evaluation
+    computes for each image -- as tensors [N] (zero_point int32).
+    An f32 tensor on the device with num_bits 8 runs on `hip.bq_quantize`; its one device-to-host read brings the zero point(s)
+    and the status.  Everything else runs the same steps as torch ops."""
+    q_max = 2.0 ** num_bits - 1.0
+    if x.is_cuda and num_bits == 8 and x.dtype == torch.float32 and x.numel() > 0:
+        from . import hip
+        q, scale, zero_point, status = hip.bq_quantize(x.detach(), per_sample=per_sample)
+        zp_host, st_host = hip.bq_read_params(zero_point, status)
+        if any(st_host):
+            _nan_zero_point()
+        if per_sample:
+            return QuantizedTensor(tensor=q, scale=scale, zero_point=zero_point)
+        return QuantizedTensor(tensor=q, scale=scale.reshape(()), zero_point=zp_host[0])
+    rows = x.detach().reshape(x.shape[0] if per_sample else 1, -1)
+    low, high = rows.min(dim=1).values, rows.max(dim=1).values
+    scale = (high - low) / q_max
+    first = 0.0 - low / scale
+    if bool(torch.isnan(first).any()):
+        _nan_zero_point()
+    zero_point = first.clamp(0.0, q_max).to(torch.int32)       # (truncation toward zero, as int())
+    q = zero_point.to(rows.dtype).unsqueeze(1) + rows / scale.unsqueeze(1)
+    q = q.clamp_(0.0, q_max).round_().to(torch.uint8).reshape(x.shape)
+    if per_sample:
+        return QuantizedTensor(tensor=q, scale=scale, zero_point=zero_point)
+    return QuantizedTensor(tensor=q, scale=scale.reshape(()), zero_point=int(zero_point[0]))
+
+
+def dequantize_tensor(q_x):
+    """torchdistill's `dequantize_tensor`: scale * (q.float() - zero_point); takes both forms `quantize_tensor` returns."""
+    q, scale, zero_point = q_x.tensor, q_x.scale, q_x.zero_point
+    if q.is_cuda and q.dtype == torch.uint8 and q.numel() > 0 and isinstance(scale, torch.Tensor) and scale.is_cuda:
+        from . import hip
+        return hip.bq_dequantize(q, scale, zero_point)
+    if isinstance(zero_point, torch.Tensor) and zero_point.dim() > 0:
+        shape = (-1,) + (1,) * (q.dim() - 1)
+        return scale.reshape(shape) * (q.float() - zero_point.to(q.device).reshape(shape).float())
+    return scale * (q.float() - zero_point)
+
+
+@register_misc_transform_module
+class SimpleQuantizer(nn.Module):
+    """num_bits 16: `z.half()`; num_bits 8: `quantize_tensor` (misc.py:181-205).  `per_sample` (not in the reference, default off):
+    one scale per image of a batch."""
+
+    def __init__(self, num_bits, per_sample=False):
+        super().__init__()
+        self.num_bits = num_bits
+        self.per_sample = per_sample
+
+    def forward(self, z):
+        return z.half() if self.num_bits == 16 else quantize_tensor(z, self.num_bits, per_sample=self.per_sample)
+
+
+@register_misc_transform_module
+class SimpleDequantizer(nn.Module):
+    """num_bits 16: `z.float()`; else `dequantize_tensor` (misc.py:208-231)."""
+
+    def __init__(self, num_bits):
+        super().__init__()
+        self.num_bits = num_bits
+
+    def forward(self, z):
+        return z.float() if self.num_bits == 16 else dequantize_tensor(z)
 
 
 def default_collate_w_pil(batch):
