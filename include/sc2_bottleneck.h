@@ -813,6 +813,48 @@ int sc2_maxpool_affine_relu_nhwc(const void *x, void *y, const float *a, const f
 int sc2_avgpool2d_nhwc(const void *x, void *y, int N, int H, int W, int C, int kernel, int stride, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Detection tail (csrc/detect.hip): the two operations of torchvision's Faster R-CNN inference path behind the  */
+/* feature pyramid that torch has no operator for.  tests/ref_detection.py restates both.                        */
+/* ------------------------------------------------------------------------------------------ */
+#define SC2_NMS_MAX_BOXES 16384   /* one call's boxes: a 32 MiB pair mask */
+#define SC2_ROI_MAX_LEVELS 5
+/* Greedy non-maximum suppression with groups (torchvision's `batched_nms`, the "vanilla" form: boxes of different groups never
+ * suppress each other; no coordinate offsets).  boxes: f32 [n,4] (x1, y1, x2, y2), 16-byte aligned, ALREADY in processing order
+ * (descending score, ties by ascending original index: the caller sorts); groups: i32 [n].
+ * keep[i] = 1 iff no earlier KEPT box j of the same group has IoU(j, i) > iou_threshold (strictly: equal is kept; a box that only a
+ * suppressed box overlaps is kept), else 0; *count = the number of ones.  keep: u8 [n], count: i32 [1], both DEVICE memory.
+ * IoU in f32, every operation rounded once and in this order (no fused multiply-add, IEEE division):
+ *   area = (x2 - x1) * (y2 - y1);  w = max(0, min(x2a, x2b) - max(x1a, x1b));  h likewise;  inter = w * h;
+ *   iou = inter / (area_a + area_b - inter)                     (0 / 0 = NaN compares false: kept)
+ * Two launches on `stream`: a 64 x 64-block pair mask into ws (one 64-bit word per row and column block, right of the diagonal
+ * only), then ONE workgroup that walks the rows in order against a bitmap in LDS.  Nothing is copied to the host.
+ * ws: sc2_nms_ws_bytes(n) bytes, 8-byte aligned (0 for n outside 1..SC2_NMS_MAX_BOXES).  n == 0 launches nothing (*count is cleared by
+ * a stream-ordered fill); n > SC2_NMS_MAX_BOXES returns SC2_ERR_UNSUPPORTED: split by group (groups are independent). */
+long long sc2_nms_ws_bytes(int n);
+int sc2_nms(const float *boxes, const int32_t *groups, int n, float iou_threshold, uint8_t *keep, int32_t *count, void *ws, void *stream);
+
+/* One pyramid level of sc2_roi_align: an NHWC map [N,H,W,C] (f32 or bf16, 16-byte aligned) and image pixels -> map pixels. */
+typedef struct sc2_roi_level {
+    const void *data;
+    int32_t H, W;
+    float spatial_scale;
+} sc2_roi_level;
+typedef struct sc2_roi_levels {
+    sc2_roi_level level[SC2_ROI_MAX_LEVELS];
+} sc2_roi_levels;
+/* Multi-level RoIAlign with torchvision's aligned=False semantics (what `MultiScaleRoIAlign` runs inside `FasterRCNN`).
+ * lv: the first n_levels descriptors (passed by value: no device copy of them); every level holds N images of C channels,
+ * C % 8 == 0, all f32 or all bf16 (is_bf16).  rois: f32 [K,5] (image index, x1, y1, x2, y2 in image pixels); levels: i32 [K], the level
+ * each RoI is pooled from.  out: f32 [K,C,P,P].  P in 1..14, sampling_ratio in 1..16 (the adaptive form, <= 0, is not built).
+ * Per RoI and axis, in f32: start = x1 * scale, end = x2 * scale, size = max(end - start, 1), bin = size / P; sample i of bin p at
+ * start + p * bin + (i + 0.5) * bin / sampling_ratio.  A sample with y < -1 or y > H (x likewise) contributes 0; otherwise y is
+ * clamped to [0, H - 1] (the neighbour y_low + 1 is clamped to H - 1, then with weight 0) and read bilinearly; the output is the mean
+ * of the sampling_ratio^2 samples.  A RoI whose level is outside 0..n_levels-1 or whose image index is outside 0..N-1 reads nothing:
+ * its outputs are NaN.  One workgroup per RoI, one launch on `stream`. */
+int sc2_roi_align(sc2_roi_levels lv, int n_levels, int N, int C, int is_bf16, const float *rois, const int32_t *levels, int K, int P,
+                  int sampling_ratio, float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Diagnostics (csrc/diag.hip; no product path calls these).                                    */
 /* ------------------------------------------------------------------------------------------ */
 /* The shader clock the chip holds while OTHER kernels run: `n_workgroups` probe waves (one per workgroup; launch >= 8 so that

@@ -13,6 +13,10 @@ from .layer import (LAYER_CLASS_DICT, LAYER_FUNC_DICT, BaseBottleneck, EntropyBo
                     FPBasedResNetBottleneck, MSHPBasedResNetBottleneck, SHPBasedResNetBottleneck, SimpleBottleneck, get_layer,
                     larger_resnet_bottleneck, register_layer_class, register_layer_func)
 from .loss import BppLoss  # noqa: F401
+from . import detection  # noqa: F401
+from .detection import (AnchorGenerator, FastRCNNPredictor, FasterRCNN, GeneralizedRCNNTransform, ImageList,  # noqa: F401
+                        MultiScaleRoIAlign, RegionProposalNetwork, RoIHeads, RPNHead, TwoMLPHead, batched_nms,
+                        multiscale_roi_align, nms, roi_align)
 from .compression import (COMPRESSION_MODEL_CLASS_DICT, COMPRESSION_MODEL_FUNC_DICT, FactorizedPrior,  # noqa: F401
                           JointAutoregressiveHierarchicalPriors, MeanScaleHyperprior, ScaleHyperprior,
                           bmshj2018_factorized, bmshj2018_hyperprior, get_compression_model, mbt2018, mbt2018_mean)

@@ -10,9 +10,8 @@ paths `backbone.body.bottleneck_layer` / `backbone.bottleneck_layer`, update / a
 * `BaseSegmentationModel`, `deeplabv3_model` (segmentation/base.py:42-139, deeplabv3.py:44-104) with `DeepLabHead`
   (ASPP, rates 12 / 24 / 36) and `FCNHead` restated on torch ops, torchvision parameter names.
 * `BaseRCNN`, `faster_rcnn_model` (detection/rcnn.py:26-226): the updatable shell.  RPN, RoI heads, anchor generator
-  and the image-list transform are torchvision's `FasterRCNN`; they are outside the hot path and
-  are taken from torchvision when it is importable -- without it `faster_rcnn_model` raises ImportError, while the
-  backbone + FPN (everything the bottleneck touches) is built and tested on its own.
+  and the image-list transform are torchvision's `FasterRCNN` when torchvision is importable; without it they are
+  `detection.FasterRCNN`, this package's restatement of the inference path (NMS and RoIAlign on csrc/detect.hip).
 
 These heads run on torch ops (MIOpen) in f32 or bf16; the bottleneck and the undilated ResNet stacks under them run on
 the HIP library (`FeatureExtractionBackbone.set_compute_dtype('bf16')`).
@@ -434,7 +433,8 @@ class BaseRCNN(_UpdatableDenseModel):
 def faster_rcnn_model(backbone_config, pretrained=True, pretrained_backbone_name=None, progress=True,
                       backbone_fpn_kwargs=None, num_classes=91, analysis_config=None, start_ckpt_file_path=None, **kwargs):
     """Faster R-CNN with a splittable backbone + FPN (detection/rcnn.py:183-226).  The backbone is built with
-    FrozenBatchNorm2d as the reference does; RPN / RoI heads / transform come from torchvision's FasterRCNN."""
+    FrozenBatchNorm2d as the reference does; RPN / RoI heads / transform come from torchvision's FasterRCNN where it is
+    importable, else from `detection.FasterRCNN` (inference only)."""
     from .wrapper import load_classification_model
     backbone_fpn_kwargs = dict(backbone_fpn_kwargs or {})
     backbone_config = dict(backbone_config, kwargs=dict(backbone_config.get('kwargs') or {}, norm_layer='FrozenBatchNorm2d'))
@@ -442,9 +442,8 @@ def faster_rcnn_model(backbone_config, pretrained=True, pretrained_backbone_name
     bfpn = backbone_with_fpn(backbone, **backbone_fpn_kwargs)
     try:
         from torchvision.models.detection.faster_rcnn import FasterRCNN
-    except ImportError as e:
-        raise ImportError('faster_rcnn_model: RPN / RoI heads come from torchvision.models.detection, which is not '
-                          'installed here; the updatable backbone + FPN is available as dense.backbone_with_fpn') from e
+    except ImportError:       # the package's own restatement of the inference path, NMS and RoIAlign on the library's kernels
+        from .detection import FasterRCNN
     model = BaseRCNN(FasterRCNN(bfpn, num_classes, **kwargs), analysis_config=analysis_config)
     if pretrained and pretrained_backbone_name:
         import logging

@@ -1,0 +1,619 @@
+"""The detection tail of Faster R-CNN behind the feature pyramid: a torch-only restatement of the INFERENCE path of
+torchvision's `FasterRCNN` (anchor generator, RPN, multi-scale RoIAlign, box head, RoI heads, image transform), under
+torchvision's module and parameter names so that its checkpoints load (sc2bench/models/detection/rcnn.py builds the
+reference's detector from these classes).
+
+No torchvision binary exists here to pin this file against: every semantic below is **[recalled: torchvision 0.15+]** in
+the sense of SURVEY.md section 8(c) -- written down from the published source as remembered, not compared against a run.
+
+Two operations have no torch operator and run on the library's kernels (csrc/detect.hip) for device tensors:
+non-maximum suppression (`nms`, `batched_nms` -> `hip.batched_nms`) and RoIAlign (`roi_align`, `multiscale_roi_align` ->
+`hip.roi_align`).  CPU tensors, and device tensors while `hip.host_policy.nms_hip` / `roi_align_hip` are off (A/B), take a
+torch-op implementation of the same definitions (include/sc2_bottleneck.h states them; tests/ref_detection.py restates
+them independently).  Everything else is small tensor algebra and two small GEMM stacks on torch ops.
+
+Training of the RPN / RoI heads (matcher, samplers, losses) is not built: both modules raise NotImplementedError in
+training mode.
+"""
+import math
+from collections import OrderedDict
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from . import hip
+
+BBOX_XFORM_CLIP = math.log(1000.0 / 16)
+
+
+# ------------------------------------------------------------------------------------------------ box algebra
+def clip_boxes_to_image(boxes, size):
+    height, width = size
+    x = boxes[..., 0::2].clamp(min=0, max=width)
+    y = boxes[..., 1::2].clamp(min=0, max=height)
+    return torch.stack((x, y), dim=boxes.dim()).reshape(boxes.shape)
+
+
+def remove_small_boxes(boxes, min_size):
+    ws, hs = boxes[:, 2] - boxes[:, 0], boxes[:, 3] - boxes[:, 1]
+    return torch.where((ws >= min_size) & (hs >= min_size))[0]
+
+
+class BoxCoder(object):
+    """Box regression deltas <-> boxes (torchvision.models.detection._utils.BoxCoder); only `decode` is needed at inference."""
+
+    def __init__(self, weights, bbox_xform_clip=BBOX_XFORM_CLIP):
+        self.weights = weights
+        self.bbox_xform_clip = bbox_xform_clip
+
+    def decode(self, rel_codes, boxes):
+        concat = torch.cat(list(boxes), dim=0)
+        box_sum = concat.shape[0]
+        pred = self.decode_single(rel_codes, concat)
+        if box_sum > 0:
+            pred = pred.reshape(box_sum, -1, 4)
+        return pred
+
+    def decode_single(self, rel_codes, boxes):
+        boxes = boxes.to(rel_codes.dtype)
+        widths, heights = boxes[:, 2] - boxes[:, 0], boxes[:, 3] - boxes[:, 1]
+        ctr_x, ctr_y = boxes[:, 0] + 0.5 * widths, boxes[:, 1] + 0.5 * heights
+        wx, wy, ww, wh = self.weights
+        dx, dy = rel_codes[:, 0::4] / wx, rel_codes[:, 1::4] / wy
+        dw = torch.clamp(rel_codes[:, 2::4] / ww, max=self.bbox_xform_clip)
+        dh = torch.clamp(rel_codes[:, 3::4] / wh, max=self.bbox_xform_clip)
+        pred_ctr_x, pred_ctr_y = dx * widths[:, None] + ctr_x[:, None], dy * heights[:, None] + ctr_y[:, None]
+        half_w, half_h = 0.5 * (torch.exp(dw) * widths[:, None]), 0.5 * (torch.exp(dh) * heights[:, None])
+        return torch.stack((pred_ctr_x - half_w, pred_ctr_y - half_h, pred_ctr_x + half_w, pred_ctr_y + half_h), dim=2).flatten(1)
+
+
+# ------------------------------------------------------------------------------------------------ NMS
+def _nms_sorted_torch(b, g, iou_threshold, rows=1024):
+    """The definition of sc2_nms on torch ops: b f32 [n,4] in processing order, g [n] -> bool keep mask [n] on b's device.
+    The pair tests are evaluated `rows` rows at a time in f32 (every operation its own op: rounded once, as the kernel does),
+    the greedy walk runs on the host over each chunk's bits."""
+    import numpy as np
+    n = b.shape[0]
+    x1, y1, x2, y2 = b.unbind(1)
+    area = (x2 - x1) * (y2 - y1)
+    thr = torch.tensor(float(iou_threshold), dtype=torch.float32, device=b.device)
+    removed, keep = np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
+    for r0 in range(0, n, rows):
+        r1 = min(n, r0 + rows)
+        w = (torch.min(x2[r0:r1, None], x2[None, r0:]) - torch.max(x1[r0:r1, None], x1[None, r0:])).clamp(min=0)
+        h = (torch.min(y2[r0:r1, None], y2[None, r0:]) - torch.max(y1[r0:r1, None], y1[None, r0:])).clamp(min=0)
+        inter = w * h
+        iou = inter / (area[r0:r1, None] + area[None, r0:] - inter)
+        m = ((iou > thr) & (g[r0:r1, None] == g[None, r0:])).cpu().numpy()
+        for i in range(r0, r1):
+            if not removed[i]:
+                keep[i] = True
+                removed[i + 1:] |= m[i - r0, i + 1 - r0:]
+    return torch.from_numpy(keep).to(b.device)
+
+
+def batched_nms(boxes, scores, idxs, iou_threshold):
+    """Greedy NMS within each value of `idxs` -> int64 indices of the kept boxes by descending score (ties: lower index first).
+    torchvision's "vanilla" batched NMS, not its coordinate-offset trick (see `hip.batched_nms`)."""
+    if boxes.is_cuda and hip.host_policy.nms_hip:
+        return hip.batched_nms(boxes, scores, idxs, iou_threshold)
+    if boxes.shape[0] == 0:
+        return torch.empty(0, dtype=torch.int64, device=boxes.device)
+    order = torch.sort(scores, descending=True, stable=True)[1]
+    b, g = boxes.detach().to(torch.float32)[order], idxs[order]
+    if b.shape[0] <= 1024:
+        return order[_nms_sorted_torch(b, g, iou_threshold)]
+    keep = torch.zeros(b.shape[0], dtype=torch.bool, device=b.device)
+    for v in torch.unique(g).tolist():        # groups are independent: far fewer pair tests group by group
+        sel = torch.where(g == v)[0]
+        keep[sel] = _nms_sorted_torch(b[sel], g[sel], iou_threshold)
+    return order[keep]
+
+
+def nms(boxes, scores, iou_threshold):
+    return batched_nms(boxes, scores, torch.zeros(boxes.shape[0], dtype=torch.int32, device=boxes.device), iou_threshold)
+
+
+# ------------------------------------------------------------------------------------------------ RoIAlign
+def _roi_axis(c, size):
+    """one axis of the bilinear sample positions c (f32): -> (valid, low, high, l, h)"""
+    valid = ~((c < -1.0) | (c > float(size)))
+    c = c.clamp(min=0.0)
+    low = c.to(torch.int64).clamp(min=0, max=size - 1)
+    edge = low >= size - 1
+    high = torch.where(edge, low, low + 1)
+    c = torch.where(edge, low.to(c.dtype), c)
+    l = c - low.to(c.dtype)
+    return valid, low, high, l, 1.0 - l
+
+
+def _roi_align_level_torch(feat, rois, scale, P, S, chunk=128):
+    """feat [N,C,H,W], rois f32 [k,5] -> f32 [k,C,P,P], aligned=False"""
+    feat = feat.to(torch.float32)
+    H, W = feat.shape[-2:]
+    p = torch.arange(P, dtype=torch.float32, device=feat.device)[None, :, None]
+    i = torch.arange(S, dtype=torch.float32, device=feat.device)[None, None, :]
+    outs = []
+    for k0 in range(0, rois.shape[0], chunk):
+        r = rois[k0:k0 + chunk].to(torch.float32)
+        k = r.shape[0]
+        img = r[:, 0].to(torch.int64)[:, None, None]
+        coords = []
+        for lo, hi in ((r[:, 2], r[:, 4]), (r[:, 1], r[:, 3])):     # y, then x
+            start, end = lo * scale, hi * scale
+            bin_ = ((end - start).clamp(min=1.0) / P)[:, None, None]
+            coords.append((start[:, None, None] + p * bin_ + (i + 0.5) * bin_ / S).reshape(k, P * S))
+        vy, yl, yh, ly, hy = _roi_axis(coords[0], H)
+        vx, xl, xh, lx, hx = _roi_axis(coords[1], W)
+
+        def at(yy, xx):      # [k, PS, PS, C]
+            return feat[img, :, yy[:, :, None], xx[:, None, :]]
+
+        def wt(a, b):
+            return (a[:, :, None] * b[:, None, :])[..., None]
+        val = wt(hy, hx) * at(yl, xl) + wt(hy, lx) * at(yl, xh) + wt(ly, hx) * at(yh, xl) + wt(ly, lx) * at(yh, xh)
+        val = val * (vy[:, :, None] & vx[:, None, :])[..., None]
+        val = val.reshape(k, P, S, P, S, -1).sum(dim=(2, 4)) / float(S * S)
+        outs.append(val.permute(0, 3, 1, 2))
+    return torch.cat(outs, dim=0)
+
+
+def multiscale_roi_align(feats, scales, rois, levels, output_size, sampling_ratio):
+    """RoIAlign (aligned=False) of rois f32 [K,5] (image index, x1, y1, x2, y2), each from the map `levels[k]` of `feats`
+    (NCHW maps of one batch, any memory format; `scales[l]`: image pixels -> pixels of map l) -> f32 [K,C,P,P]."""
+    feats = list(feats)
+    P, S = int(output_size), int(sampling_ratio)
+    if S <= 0:
+        raise NotImplementedError('roi_align: the adaptive sampling grid (sampling_ratio <= 0) is not built')
+    rois = rois.to(torch.float32)
+    if feats[0].is_cuda and hip.host_policy.roi_align_hip:
+        if feats[0].shape[1] % 8:
+            raise ValueError('roi_align: {} channels (the kernel takes multiples of 8)'.format(feats[0].shape[1]))
+        dtype = torch.bfloat16 if feats[0].dtype == torch.bfloat16 else torch.float32
+        nhwc = [f.to(dtype).permute(0, 2, 3, 1).contiguous() for f in feats]     # a view for channels_last maps
+        return hip.roi_align(nhwc, [float(s) for s in scales], rois.contiguous(), levels.to(torch.int32).contiguous(), P, S)
+    out = torch.zeros((rois.shape[0], feats[0].shape[1], P, P), dtype=torch.float32, device=rois.device)
+    for l, (f, s) in enumerate(zip(feats, scales)):
+        idx = torch.where(levels == l)[0]
+        if idx.numel():
+            out[idx] = _roi_align_level_torch(f, rois[idx], float(s), P, S)
+    return out
+
+
+def roi_align(input, boxes, output_size, spatial_scale=1.0, sampling_ratio=-1, aligned=False):
+    """torchvision.ops.roi_align for a square output and aligned=False.  boxes: Tensor [K,5] or a list of [k_i,4] per image."""
+    if aligned:
+        raise NotImplementedError('roi_align: aligned=True is not built (MultiScaleRoIAlign inside FasterRCNN uses aligned=False)')
+    if isinstance(output_size, (tuple, list)):
+        if output_size[0] != output_size[1]:
+            raise NotImplementedError('roi_align: output_size must be square')
+        output_size = output_size[0]
+    if not isinstance(boxes, torch.Tensor):
+        boxes = convert_to_roi_format(boxes)
+    levels = torch.zeros(boxes.shape[0], dtype=torch.int32, device=boxes.device)
+    return multiscale_roi_align([input], [spatial_scale], boxes, levels, output_size, sampling_ratio).to(input.dtype)
+
+
+def convert_to_roi_format(boxes):
+    concat = torch.cat(list(boxes), dim=0)
+    ids = torch.cat([torch.full_like(b[:, :1], i) for i, b in enumerate(boxes)], dim=0)
+    return torch.cat([ids, concat], dim=1)
+
+
+class LevelMapper(object):
+    """FPN paper eq. 1: the pyramid level of a box from its area (torchvision.ops.poolers.LevelMapper)."""
+
+    def __init__(self, k_min, k_max, canonical_scale=224, canonical_level=4, eps=1e-6):
+        self.k_min, self.k_max, self.s0, self.lvl0, self.eps = k_min, k_max, canonical_scale, canonical_level, eps
+
+    def __call__(self, boxlists):
+        s = torch.sqrt(torch.cat([(b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1]) for b in boxlists]))
+        target = torch.floor(self.lvl0 + torch.log2(s / self.s0) + torch.tensor(self.eps, dtype=s.dtype))
+        return (torch.clamp(target, min=self.k_min, max=self.k_max).to(torch.int64) - self.k_min).to(torch.int64)
+
+
+class MultiScaleRoIAlign(nn.Module):
+    """torchvision.ops.MultiScaleRoIAlign.  The feature maps are FILTERED BY NAME: the reference's configs name the pyramid
+    '1', '2', '3', '4', 'pool' while FasterRCNN's default pooler asks for '0', '1', '2', '3', so only three maps (strides 4, 8, 16)
+    reach it and large RoIs clamp to stride 16 -- the reference's behaviour, kept as it is."""
+
+    def __init__(self, featmap_names, output_size, sampling_ratio, canonical_scale=224, canonical_level=4):
+        super().__init__()
+        if isinstance(output_size, int):
+            output_size = (output_size, output_size)
+        self.featmap_names = list(featmap_names)
+        self.output_size = tuple(output_size)
+        self.sampling_ratio = sampling_ratio
+        self.canonical_scale, self.canonical_level = canonical_scale, canonical_level
+        self.scales = None
+        self.map_levels = None
+
+    def setup_scales(self, features, image_shapes):
+        max_h, max_w = max(s[0] for s in image_shapes), max(s[1] for s in image_shapes)
+        self.scales = [2.0 ** float(round(math.log2(float(f.shape[-2]) / float(max_h)))) for f in features]
+        assert all(2.0 ** float(round(math.log2(float(f.shape[-1]) / float(max_w)))) == s for f, s in zip(features, self.scales))
+        k_min, k_max = -math.log2(self.scales[0]), -math.log2(self.scales[-1])
+        self.map_levels = LevelMapper(int(k_min), int(k_max), self.canonical_scale, self.canonical_level)
+
+    def filtered(self, x):
+        feats = [v for k, v in x.items() if k in self.featmap_names]
+        if not feats:
+            raise ValueError('MultiScaleRoIAlign: none of the feature maps {} is named in {}'.format(list(x.keys()), self.featmap_names))
+        return feats
+
+    def forward(self, x, boxes, image_shapes):
+        feats = self.filtered(x)
+        self.setup_scales(feats, image_shapes)
+        rois = convert_to_roi_format([b.to(torch.float32) for b in boxes])
+        if len(feats) == 1:
+            levels = torch.zeros(rois.shape[0], dtype=torch.int64, device=rois.device)
+        else:
+            levels = self.map_levels([b.to(torch.float32) for b in boxes])      # torch ops on every path
+        if self.output_size[0] != self.output_size[1]:
+            raise NotImplementedError('MultiScaleRoIAlign: output_size must be square')
+        return multiscale_roi_align(feats, self.scales, rois, levels, self.output_size[0], self.sampling_ratio)
+
+
+# ------------------------------------------------------------------------------------------------ anchors, RPN
+class ImageList(object):
+    def __init__(self, tensors, image_sizes):
+        self.tensors = tensors
+        self.image_sizes = image_sizes
+
+    def to(self, device):
+        return ImageList(self.tensors.to(device), self.image_sizes)
+
+
+class AnchorGenerator(nn.Module):
+    def __init__(self, sizes=((128, 256, 512),), aspect_ratios=((0.5, 1.0, 2.0),)):
+        super().__init__()
+        if not isinstance(sizes[0], (list, tuple)):
+            sizes = tuple((s,) for s in sizes)
+        if not isinstance(aspect_ratios[0], (list, tuple)):
+            aspect_ratios = (aspect_ratios,) * len(sizes)
+        self.sizes, self.aspect_ratios = sizes, aspect_ratios
+        self.cell_anchors = [self.generate_anchors(s, a) for s, a in zip(sizes, aspect_ratios)]
+
+    @staticmethod
+    def generate_anchors(scales, aspect_ratios, dtype=torch.float32, device='cpu'):
+        scales = torch.as_tensor(scales, dtype=dtype, device=device)
+        h_ratios = torch.sqrt(torch.as_tensor(aspect_ratios, dtype=dtype, device=device))
+        w_ratios = 1 / h_ratios
+        ws, hs = (w_ratios[:, None] * scales[None, :]).view(-1), (h_ratios[:, None] * scales[None, :]).view(-1)
+        return (torch.stack([-ws, -hs, ws, hs], dim=1) / 2).round()
+
+    def num_anchors_per_location(self):
+        return [len(s) * len(a) for s, a in zip(self.sizes, self.aspect_ratios)]
+
+    def grid_anchors(self, grid_sizes, strides, dtype, device):
+        if len(grid_sizes) != len(self.cell_anchors):
+            raise ValueError('AnchorGenerator: {} feature maps for {} anchor sizes'.format(len(grid_sizes), len(self.cell_anchors)))
+        anchors = []
+        for (gh, gw), (sh, sw), base in zip(grid_sizes, strides, self.cell_anchors):
+            shifts_x = torch.arange(0, gw, dtype=torch.int32, device=device) * sw
+            shifts_y = torch.arange(0, gh, dtype=torch.int32, device=device) * sh
+            shift_y, shift_x = torch.meshgrid(shifts_y, shifts_x, indexing='ij')
+            shift_x, shift_y = shift_x.reshape(-1), shift_y.reshape(-1)
+            shifts = torch.stack((shift_x, shift_y, shift_x, shift_y), dim=1)
+            anchors.append((shifts.view(-1, 1, 4) + base.to(dtype=dtype, device=device).view(1, -1, 4)).reshape(-1, 4))   # (y, x, anchor)
+        return anchors
+
+    def forward(self, image_list, feature_maps):
+        grid_sizes = [tuple(f.shape[-2:]) for f in feature_maps]
+        image_size = image_list.tensors.shape[-2:]
+        strides = [(image_size[0] // g[0], image_size[1] // g[1]) for g in grid_sizes]
+        per_level = self.grid_anchors(grid_sizes, strides, torch.float32, feature_maps[0].device)
+        return [torch.cat(per_level) for _ in image_list.image_sizes]
+
+
+class RPNHead(nn.Module):
+    """3x3 conv + ReLU, then 1x1 objectness (A channels) and 1x1 box deltas (4A).  Keys `conv.0.0.*` (torchvision 0.13+: the conv
+    sits in a Conv2dNormActivation inside a Sequential); the earlier `conv.*` is accepted on load."""
+
+    def __init__(self, in_channels, num_anchors, conv_depth=1):
+        super().__init__()
+        self.conv = nn.Sequential(*[nn.Sequential(nn.Conv2d(in_channels, in_channels, 3, padding=1), nn.ReLU(inplace=True))
+                                    for _ in range(conv_depth)])
+        self.cls_logits = nn.Conv2d(in_channels, num_anchors, 1)
+        self.bbox_pred = nn.Conv2d(in_channels, num_anchors * 4, 1)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.normal_(m.weight, std=0.01)
+                nn.init.constant_(m.bias, 0)
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        for t in ('weight', 'bias'):
+            old, new = '{}conv.{}'.format(prefix, t), '{}conv.0.0.{}'.format(prefix, t)
+            if old in state_dict:
+                state_dict[new] = state_dict.pop(old)
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    def forward(self, x):
+        dtype = self.cls_logits.weight.dtype
+        logits, bbox_reg = [], []
+        for feature in x:
+            t = self.conv(feature.to(dtype))
+            logits.append(self.cls_logits(t))
+            bbox_reg.append(self.bbox_pred(t))
+        return logits, bbox_reg
+
+
+def permute_and_flatten(layer, N, A, C, H, W):
+    return layer.view(N, -1, C, H, W).permute(0, 3, 4, 1, 2).reshape(N, -1, C)      # (N,A,C,H,W) -> (N,H,W,A,C)
+
+
+def concat_box_prediction_layers(box_cls, box_regression):
+    cls_flat, reg_flat = [], []
+    for cls_l, reg_l in zip(box_cls, box_regression):
+        N, AxC, H, W = cls_l.shape
+        A = reg_l.shape[1] // 4
+        cls_flat.append(permute_and_flatten(cls_l, N, A, AxC // A, H, W))
+        reg_flat.append(permute_and_flatten(reg_l, N, A, 4, H, W))
+    return torch.cat(cls_flat, dim=1).flatten(0, -2), torch.cat(reg_flat, dim=1).reshape(-1, 4)
+
+
+_NO_TRAINING = ('{}: training is not built in this package -- the proposal matcher, the balanced positive / negative samplers '
+                'and the classification / box-regression losses are missing; only the eval forward exists')
+
+
+class RegionProposalNetwork(nn.Module):
+    def __init__(self, anchor_generator, head, fg_iou_thresh=0.7, bg_iou_thresh=0.3, batch_size_per_image=256, positive_fraction=0.5,
+                 pre_nms_top_n=None, post_nms_top_n=None, nms_thresh=0.7, score_thresh=0.0):
+        super().__init__()
+        self.anchor_generator = anchor_generator
+        self.head = head
+        self.box_coder = BoxCoder(weights=(1.0, 1.0, 1.0, 1.0))
+        self.fg_iou_thresh, self.bg_iou_thresh = fg_iou_thresh, bg_iou_thresh
+        self.batch_size_per_image, self.positive_fraction = batch_size_per_image, positive_fraction
+        self._pre_nms_top_n = pre_nms_top_n or dict(training=2000, testing=1000)
+        self._post_nms_top_n = post_nms_top_n or dict(training=2000, testing=1000)
+        self.nms_thresh = nms_thresh
+        self.score_thresh = score_thresh
+        self.min_size = 1e-3
+
+    def pre_nms_top_n(self):
+        return self._pre_nms_top_n['training' if self.training else 'testing']
+
+    def post_nms_top_n(self):
+        return self._post_nms_top_n['training' if self.training else 'testing']
+
+    def _get_top_n_idx(self, objectness, num_anchors_per_level):
+        r, offset = [], 0
+        for ob in objectness.split(num_anchors_per_level, 1):
+            n = ob.shape[1]
+            r.append(ob.topk(min(self.pre_nms_top_n(), n), dim=1)[1] + offset)
+            offset += n
+        return torch.cat(r, dim=1)
+
+    def filter_proposals(self, proposals, objectness, image_shapes, num_anchors_per_level):
+        num_images = proposals.shape[0]
+        device = proposals.device
+        objectness = objectness.detach().reshape(num_images, -1)
+        levels = torch.cat([torch.full((n,), idx, dtype=torch.int64, device=device) for idx, n in enumerate(num_anchors_per_level)], 0)
+        levels = levels.reshape(1, -1).expand_as(objectness)
+        top_n_idx = self._get_top_n_idx(objectness, num_anchors_per_level)       # chosen on the logits
+        batch_idx = torch.arange(num_images, device=device)[:, None]
+        objectness, levels, proposals = objectness[batch_idx, top_n_idx], levels[batch_idx, top_n_idx], proposals[batch_idx, top_n_idx]
+        objectness_prob = torch.sigmoid(objectness)
+        final_boxes, final_scores = [], []
+        for boxes, scores, lvl, img_shape in zip(proposals, objectness_prob, levels, image_shapes):
+            boxes = clip_boxes_to_image(boxes, img_shape)
+            keep = remove_small_boxes(boxes, self.min_size)
+            boxes, scores, lvl = boxes[keep], scores[keep], lvl[keep]
+            keep = torch.where(scores >= self.score_thresh)[0]
+            boxes, scores, lvl = boxes[keep], scores[keep], lvl[keep]
+            keep = batched_nms(boxes, scores, lvl, self.nms_thresh)[:self.post_nms_top_n()]
+            final_boxes.append(boxes[keep])
+            final_scores.append(scores[keep])
+        return final_boxes, final_scores
+
+    def forward(self, images, features, targets=None):
+        if self.training:
+            if targets is None:
+                raise ValueError('targets should not be None in training mode')
+            raise NotImplementedError(_NO_TRAINING.format('RegionProposalNetwork'))
+        features = list(features.values())
+        objectness, pred_bbox_deltas = self.head(features)
+        anchors = self.anchor_generator(images, features)
+        num_images = len(anchors)
+        num_anchors_per_level = [o[0].numel() for o in objectness]
+        objectness, pred_bbox_deltas = concat_box_prediction_layers(objectness, pred_bbox_deltas)
+        proposals = self.box_coder.decode(pred_bbox_deltas.detach().float(), anchors).view(num_images, -1, 4)
+        boxes, _ = self.filter_proposals(proposals, objectness.float(), images.image_sizes, num_anchors_per_level)
+        return boxes, {}
+
+
+# ------------------------------------------------------------------------------------------------ box head, RoI heads
+class TwoMLPHead(nn.Module):
+    def __init__(self, in_channels, representation_size):
+        super().__init__()
+        self.fc6 = nn.Linear(in_channels, representation_size)
+        self.fc7 = nn.Linear(representation_size, representation_size)
+
+    def forward(self, x):
+        x = x.flatten(start_dim=1).to(self.fc6.weight.dtype)
+        return F.relu(self.fc7(F.relu(self.fc6(x))))
+
+
+class FastRCNNPredictor(nn.Module):
+    def __init__(self, in_channels, num_classes):
+        super().__init__()
+        self.cls_score = nn.Linear(in_channels, num_classes)
+        self.bbox_pred = nn.Linear(in_channels, num_classes * 4)
+
+    def forward(self, x):
+        if x.dim() == 4 and list(x.shape[2:]) != [1, 1]:
+            raise ValueError('FastRCNNPredictor: expected the last two dimensions to be [1,1], got {}'.format(list(x.shape[2:])))
+        x = x.flatten(start_dim=1)
+        return self.cls_score(x), self.bbox_pred(x)
+
+
+class RoIHeads(nn.Module):
+    def __init__(self, box_roi_pool, box_head, box_predictor, fg_iou_thresh=0.5, bg_iou_thresh=0.5, batch_size_per_image=512,
+                 positive_fraction=0.25, bbox_reg_weights=None, score_thresh=0.05, nms_thresh=0.5, detections_per_img=100):
+        super().__init__()
+        self.box_roi_pool, self.box_head, self.box_predictor = box_roi_pool, box_head, box_predictor
+        self.fg_iou_thresh, self.bg_iou_thresh = fg_iou_thresh, bg_iou_thresh
+        self.batch_size_per_image, self.positive_fraction = batch_size_per_image, positive_fraction
+        self.box_coder = BoxCoder((10.0, 10.0, 5.0, 5.0) if bbox_reg_weights is None else bbox_reg_weights)
+        self.score_thresh, self.nms_thresh, self.detections_per_img = score_thresh, nms_thresh, detections_per_img
+
+    def postprocess_detections(self, class_logits, box_regression, proposals, image_shapes):
+        device = class_logits.device
+        num_classes = class_logits.shape[-1]
+        boxes_per_image = [b.shape[0] for b in proposals]
+        pred_boxes = self.box_coder.decode(box_regression, proposals)
+        pred_scores = F.softmax(class_logits, -1)
+        all_boxes, all_scores, all_labels = [], [], []
+        for boxes, scores, image_shape in zip(pred_boxes.split(boxes_per_image, 0), pred_scores.split(boxes_per_image, 0), image_shapes):
+            boxes = clip_boxes_to_image(boxes, image_shape)
+            labels = torch.arange(num_classes, device=device).view(1, -1).expand_as(scores)
+            boxes, scores, labels = boxes[:, 1:].reshape(-1, 4), scores[:, 1:].reshape(-1), labels[:, 1:].reshape(-1)   # no background
+            inds = torch.where(scores > self.score_thresh)[0]
+            boxes, scores, labels = boxes[inds], scores[inds], labels[inds]
+            keep = remove_small_boxes(boxes, min_size=1e-2)
+            boxes, scores, labels = boxes[keep], scores[keep], labels[keep]
+            keep = batched_nms(boxes, scores, labels, self.nms_thresh)[:self.detections_per_img]
+            all_boxes.append(boxes[keep])
+            all_scores.append(scores[keep])
+            all_labels.append(labels[keep])
+        return all_boxes, all_scores, all_labels
+
+    def forward(self, features, proposals, image_shapes, targets=None):
+        if self.training:
+            if targets is None:
+                raise ValueError('targets should not be None in training mode')
+            raise NotImplementedError(_NO_TRAINING.format('RoIHeads'))
+        box_features = self.box_head(self.box_roi_pool(features, proposals, image_shapes))
+        class_logits, box_regression = self.box_predictor(box_features)
+        boxes, scores, labels = self.postprocess_detections(class_logits.float(), box_regression.float(), proposals, image_shapes)
+        return [{'boxes': b, 'labels': l, 'scores': s} for b, l, s in zip(boxes, labels, scores)], {}
+
+
+# ------------------------------------------------------------------------------------------------ transform, model
+def resize_boxes(boxes, original_size, new_size):
+    ratio_h, ratio_w = [torch.tensor(s, dtype=torch.float32, device=boxes.device) / torch.tensor(o, dtype=torch.float32, device=boxes.device)
+                        for s, o in zip(new_size, original_size)]
+    xmin, ymin, xmax, ymax = boxes.unbind(1)
+    return torch.stack((xmin * ratio_w, ymin * ratio_h, xmax * ratio_w, ymax * ratio_h), dim=1)
+
+
+class GeneralizedRCNNTransform(nn.Module):
+    """Normalise, resize so that the shorter side is min_size unless the longer would pass max_size, zero-pad the batch to a
+    multiple of `size_divisible`; `postprocess` maps the detections back to each image's own size."""
+
+    def __init__(self, min_size, max_size, image_mean, image_std, size_divisible=32, fixed_size=None, **kwargs):
+        super().__init__()
+        self.min_size = tuple(min_size) if isinstance(min_size, (list, tuple)) else (min_size,)
+        self.max_size = max_size
+        self.image_mean, self.image_std = image_mean, image_std
+        self.size_divisible = size_divisible
+        self.fixed_size = fixed_size
+        self._skip_resize = kwargs.pop('_skip_resize', False)
+
+    def normalize(self, image):
+        if not image.is_floating_point():
+            raise TypeError('Expected input images to be of floating type (in range [0, 1]), but found type {}'.format(image.dtype))
+        mean = torch.as_tensor(self.image_mean, dtype=image.dtype, device=image.device)
+        std = torch.as_tensor(self.image_std, dtype=image.dtype, device=image.device)
+        return (image - mean[:, None, None]) / std[:, None, None]
+
+    def resized_size(self, h, w):
+        """the size `resize` produces from an h x w image in eval mode: floor(side * scale), as F.interpolate recomputes it"""
+        if self.fixed_size is not None:
+            return self.fixed_size[1], self.fixed_size[0]
+        scale = min(float(self.min_size[-1]) / min(h, w), float(self.max_size) / max(h, w))
+        return int(math.floor(h * scale)), int(math.floor(w * scale))
+
+    def resize(self, image, target=None):
+        h, w = image.shape[-2:]
+        if self.training and self._skip_resize:
+            return image, target
+        if self.fixed_size is not None:
+            image = F.interpolate(image[None], size=[self.fixed_size[1], self.fixed_size[0]], mode='bilinear', align_corners=False)[0]
+        else:
+            scale = min(float(self.min_size[-1]) / min(h, w), float(self.max_size) / max(h, w))
+            image = F.interpolate(image[None], scale_factor=scale, mode='bilinear', recompute_scale_factor=True, align_corners=False)[0]
+        if target is not None and 'boxes' in target:
+            target = dict(target, boxes=resize_boxes(target['boxes'], (h, w), image.shape[-2:]))
+        return image, target
+
+    def batch_images(self, images):
+        stride = float(self.size_divisible)
+        max_h, max_w = max(i.shape[-2] for i in images), max(i.shape[-1] for i in images)
+        max_h, max_w = int(math.ceil(max_h / stride) * stride), int(math.ceil(max_w / stride) * stride)
+        batched = images[0].new_full((len(images), images[0].shape[0], max_h, max_w), 0)
+        for i, img in enumerate(images):
+            batched[i, :, :img.shape[1], :img.shape[2]].copy_(img)
+        return batched
+
+    def forward(self, images, targets=None):
+        images = [img for img in images]
+        targets = [dict(t) for t in targets] if targets is not None else None
+        for i, image in enumerate(images):
+            if image.dim() != 3:
+                raise ValueError('images is expected to be a list of 3d tensors of shape [C, H, W], got {}'.format(tuple(image.shape)))
+            image, t = self.resize(self.normalize(image), targets[i] if targets is not None else None)
+            images[i] = image
+            if targets is not None:
+                targets[i] = t
+        image_sizes = [(int(img.shape[-2]), int(img.shape[-1])) for img in images]
+        return ImageList(self.batch_images(images), image_sizes), targets
+
+    def postprocess(self, result, image_shapes, original_image_sizes):
+        if self.training:
+            return result
+        for i, (pred, im_s, o_im_s) in enumerate(zip(result, image_shapes, original_image_sizes)):
+            result[i]['boxes'] = resize_boxes(pred['boxes'], im_s, o_im_s)
+        return result
+
+
+class FasterRCNN(nn.Module):
+    """torchvision.models.detection.FasterRCNN under its keyword names; `transform`, `backbone`, `rpn`, `roi_heads` are the
+    attributes `dense.BaseRCNN` takes over."""
+
+    def __init__(self, backbone, num_classes=None, min_size=800, max_size=1333, image_mean=None, image_std=None,
+                 rpn_anchor_generator=None, rpn_head=None, rpn_pre_nms_top_n_train=2000, rpn_pre_nms_top_n_test=1000,
+                 rpn_post_nms_top_n_train=2000, rpn_post_nms_top_n_test=1000, rpn_nms_thresh=0.7, rpn_fg_iou_thresh=0.7,
+                 rpn_bg_iou_thresh=0.3, rpn_batch_size_per_image=256, rpn_positive_fraction=0.5, rpn_score_thresh=0.0,
+                 box_roi_pool=None, box_head=None, box_predictor=None, box_score_thresh=0.05, box_nms_thresh=0.5,
+                 box_detections_per_img=100, box_fg_iou_thresh=0.5, box_bg_iou_thresh=0.5, box_batch_size_per_image=512,
+                 box_positive_fraction=0.25, bbox_reg_weights=None, **kwargs):
+        super().__init__()
+        if not hasattr(backbone, 'out_channels'):
+            raise ValueError('backbone should contain an attribute out_channels specifying the number of output channels')
+        if (num_classes is None) == (box_predictor is None):
+            raise ValueError('exactly one of num_classes and box_predictor should be given')
+        out_channels = backbone.out_channels
+        if rpn_anchor_generator is None:
+            rpn_anchor_generator = AnchorGenerator(((32,), (64,), (128,), (256,), (512,)), ((0.5, 1.0, 2.0),) * 5)
+        if rpn_head is None:
+            rpn_head = RPNHead(out_channels, rpn_anchor_generator.num_anchors_per_location()[0])
+        self.rpn = RegionProposalNetwork(rpn_anchor_generator, rpn_head, rpn_fg_iou_thresh, rpn_bg_iou_thresh, rpn_batch_size_per_image,
+                                         rpn_positive_fraction, dict(training=rpn_pre_nms_top_n_train, testing=rpn_pre_nms_top_n_test),
+                                         dict(training=rpn_post_nms_top_n_train, testing=rpn_post_nms_top_n_test), rpn_nms_thresh,
+                                         score_thresh=rpn_score_thresh)
+        if box_roi_pool is None:
+            box_roi_pool = MultiScaleRoIAlign(featmap_names=['0', '1', '2', '3'], output_size=7, sampling_ratio=2)
+        if box_head is None:
+            box_head = TwoMLPHead(out_channels * box_roi_pool.output_size[0] ** 2, 1024)
+        if box_predictor is None:
+            box_predictor = FastRCNNPredictor(1024, num_classes)
+        self.roi_heads = RoIHeads(box_roi_pool, box_head, box_predictor, box_fg_iou_thresh, box_bg_iou_thresh, box_batch_size_per_image,
+                                  box_positive_fraction, bbox_reg_weights, box_score_thresh, box_nms_thresh, box_detections_per_img)
+        self.backbone = backbone
+        self.transform = GeneralizedRCNNTransform(min_size, max_size, image_mean or [0.485, 0.456, 0.406],
+                                                  image_std or [0.229, 0.224, 0.225], **kwargs)
+
+    def forward(self, images, targets=None):
+        if self.training and targets is None:
+            raise ValueError('targets should not be None in training mode')
+        original_image_sizes = [tuple(img.shape[-2:]) for img in images]
+        images, targets = self.transform(images, targets)
+        features = self.backbone(images.tensors)
+        if isinstance(features, torch.Tensor):
+            features = OrderedDict([('0', features)])
+        proposals, _ = self.rpn(images, features, targets)
+        detections, _ = self.roi_heads(features, proposals, images.image_sizes, targets)
+        return self.transform.postprocess(detections, images.image_sizes, original_image_sizes)

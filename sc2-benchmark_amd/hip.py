@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     'sc2_mse_partial_len', 'sc2_mse_sum_bf16', 'sc2_mse_grad_bf16', 'sc2_relu_bwd_bf16', 'sc2_relu_bwd_mse_bf16',
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
+    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
 ]
 
@@ -58,6 +59,20 @@ class ArScanArgs(ctypes.Structure):
                                                 'y_hat_nhwc', 'y', 'symbols', 'indexes', 'buf', 'io_offset', 'io_nbytes',
                                                 'cdfs', 'cdf_sizes', 'offsets', 'st_x', 'st_pos', 'status',
                                                 'gaussian_params')])
+
+
+NMS_MAX_BOXES = 16384      # SC2_NMS_MAX_BOXES
+ROI_MAX_LEVELS = 5         # SC2_ROI_MAX_LEVELS
+
+
+class RoiLevel(ctypes.Structure):
+    """sc2_roi_level of include/sc2_bottleneck.h."""
+    _fields_ = [('data', ctypes.c_void_p), ('H', ctypes.c_int32), ('W', ctypes.c_int32), ('spatial_scale', ctypes.c_float)]
+
+
+class RoiLevels(ctypes.Structure):
+    """sc2_roi_levels (passed by value)."""
+    _fields_ = [('level', RoiLevel * ROI_MAX_LEVELS)]
 
 
 class Sc2Error(RuntimeError):
@@ -119,6 +134,8 @@ class HostPolicy(object):
     pipeline_host_steps = True   # StagePipeline(host_steps=None): the first batches of a run (up to 4, by the host's core count) are coded by the host thread pool while the device coder's first group is under way, their back stages gated behind the opening burst of front stages: + 1.5 - 2.5 % at K = 20 and K = 100 (profiles/r06o_host_steps_ab.txt); False: device coder only
     eval_graphs = True         # the updated eval forward of SplittableResNet at small batch replays HIP graphs of its device halves (graphs.py)
     eval_graph_max_batch = 1   # ... for batches up to this size (the reference evaluates at batch size 1)
+    nms_hip = True             # detection.nms / batched_nms of device tensors on sc2_nms (False: the torch-op restatement, A/B)
+    roi_align_hip = True       # detection.roi_align / multiscale_roi_align of device tensors on sc2_roi_align (False: torch ops, A/B)
 
 
 host_policy = HostPolicy()
@@ -285,6 +302,10 @@ def lib():
     L.sc2_bq_dequantize_nhwc.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, vp]
     L.sc2_maxpool_affine_relu_nhwc.argtypes = [vp, vp, vp, vp] + [i32] * 10 + [vp]
     L.sc2_avgpool2d_nhwc.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp]
+    L.sc2_nms_ws_bytes.argtypes = [i32]
+    L.sc2_nms_ws_bytes.restype = i64
+    L.sc2_nms.argtypes = [vp, vp, i32, f32, vp, vp, vp, vp]
+    L.sc2_roi_align.argtypes = [RoiLevels, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]
     L.sc2_rans_host_tables_create.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp)]
     L.sc2_rans_host_tables_destroy.argtypes = [vp]
     L.sc2_rans_host_tables_destroy.restype = None
@@ -1058,6 +1079,104 @@ def bq_dequantize(q, scale, zero_point, out_format=OUT_F32_NCHW, affine=None, re
         _check(lib().sc2_bq_dequantize_nhwc(_ptr(q), _ptr(scale), _ptr(zp), 1 if n_seg > 1 else 0, _ptr(a), _ptr(b),
                                             1 if relu else 0, _ptr(y), N, C, H, W, cpad, _stream()), 'bq_dequantize_nhwc')
     return y
+
+
+# --------------------------------------------------------------------------------------------- #
+# detection tail: non-maximum suppression and multi-level RoIAlign (csrc/detect.hip)
+# --------------------------------------------------------------------------------------------- #
+def nms_sorted(boxes, groups, iou_threshold, keep=None, tag=None):
+    """Greedy NMS of boxes that are ALREADY in processing order.  boxes: f32 [n,4] (x1, y1, x2, y2), groups: i32 [n] (boxes of
+    different groups never suppress each other), n <= NMS_MAX_BOXES -> (keep u8 [n] in the same order, count i32 [1]), both on the
+    device; nothing synchronises.  `keep`: a caller's u8 [n] buffer to write into.  n == 0 launches nothing."""
+    _dev(boxes, 'boxes')
+    _dev(groups, 'groups')
+    assert boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.shape[1] == 4 and boxes.is_contiguous()
+    n = int(boxes.shape[0])
+    assert groups.dtype == torch.int32 and groups.shape == (n,) and groups.is_contiguous()
+    if keep is None:
+        keep = torch.empty(n, dtype=torch.uint8, device=boxes.device)
+    assert keep.dtype == torch.uint8 and keep.shape == (n,) and keep.is_contiguous() and keep.device == boxes.device
+    count = torch.empty(1, dtype=torch.int32, device=boxes.device)
+    if n == 0:
+        return keep, count.zero_()
+    if n > NMS_MAX_BOXES:
+        raise ValueError('nms_sorted: {} boxes in one call (at most {}); batched_nms splits by group'.format(n, NMS_MAX_BOXES))
+    ws = torch.empty(int(lib().sc2_nms_ws_bytes(n)), dtype=torch.uint8, device=boxes.device)
+    with _timed(tag or 'nms'):
+        _check(lib().sc2_nms(_ptr(boxes), _ptr(groups), n, float(iou_threshold), _ptr(keep), _ptr(count), _ptr(ws), _stream()), 'nms')
+    return keep, count
+
+
+def batched_nms(boxes, scores, idxs, iou_threshold, tag=None):
+    """torchvision's `batched_nms` in its "vanilla" form: greedy NMS within each value of `idxs`, -> int64 indices of the kept boxes
+    in descending score order (ties: the lower index first -- a STABLE descending sort decides the processing order).
+    torchvision's other form adds `idx * (max coordinate + 1)` to every box and runs one plain NMS; that perturbs the f32
+    coordinates (the offsets are rounded into them), so its decisions near the threshold are not those of the definition: not
+    built here.
+    More than NMS_MAX_BOXES boxes are split by group into several calls (groups are independent: the result is unchanged); a
+    single group above the cap raises ValueError.  The returned index list has a data-dependent length: one synchronising
+    `nonzero`, as in torchvision (plus one `unique` where the input has to be split)."""
+    _dev(boxes, 'boxes')
+    n = int(boxes.shape[0])
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=boxes.device)
+    order = torch.sort(scores, descending=True, stable=True)[1]
+    b = boxes.detach().to(torch.float32)[order].contiguous()
+    g = idxs[order].to(torch.int32).contiguous()
+    if n <= NMS_MAX_BOXES:
+        keep, _ = nms_sorted(b, g, iou_threshold, tag=tag)
+        return order[keep.bool()]
+    values, counts = torch.unique(g, return_counts=True)
+    values, counts = values.tolist(), counts.tolist()
+    if max(counts) > NMS_MAX_BOXES:
+        raise ValueError('batched_nms: a single group holds {} boxes (at most {} per group)'.format(max(counts), NMS_MAX_BOXES))
+    keep = torch.zeros(n, dtype=torch.bool, device=boxes.device)
+    i = 0
+    while i < len(values):       # consecutive groups up to the cap per call
+        j, total = i, 0
+        while j < len(values) and total + counts[j] <= NMS_MAX_BOXES:
+            total += counts[j]
+            j += 1
+        sel = ((g >= values[i]) & (g <= values[j - 1])).nonzero().squeeze(1)       # ascending: the processing order is kept
+        part, _ = nms_sorted(b[sel].contiguous(), g[sel].contiguous(), iou_threshold, tag=tag)
+        keep[sel] = part.bool()
+        i = j
+    return order[keep]
+
+
+def nms(boxes, scores, iou_threshold, tag=None):
+    """torchvision's `nms`: `batched_nms` with every box in one group (at most NMS_MAX_BOXES boxes)."""
+    return batched_nms(boxes, scores, torch.zeros(boxes.shape[0], dtype=torch.int32, device=boxes.device), iou_threshold, tag=tag)
+
+
+def roi_align(feats_nhwc, scales, rois, levels, output_size, sampling_ratio, out=None, tag=None):
+    """Multi-level RoIAlign, torchvision's aligned=False semantics (include/sc2_bottleneck.h: sc2_roi_align).
+    feats_nhwc: up to ROI_MAX_LEVELS maps [N,H_l,W_l,C], contiguous, all f32 or all bf16, C % 8 == 0; scales: one float per map
+    (image pixels -> map pixels); rois: f32 [K,5] (image index, x1, y1, x2, y2); levels: i32 [K], the map each RoI is pooled from
+    -> f32 [K,C,P,P].  A RoI whose level or image index does not exist comes back as NaN."""
+    feats_nhwc = list(feats_nhwc)
+    if not 1 <= len(feats_nhwc) <= ROI_MAX_LEVELS or len(scales) != len(feats_nhwc):
+        raise ValueError('roi_align: {} maps, {} scales (1..{} of each)'.format(len(feats_nhwc), len(scales), ROI_MAX_LEVELS))
+    f0 = _dev(feats_nhwc[0], 'feats')
+    N, C = int(f0.shape[0]), int(f0.shape[3])
+    lv = RoiLevels()
+    for l, (f, sc) in enumerate(zip(feats_nhwc, scales)):
+        _dev(f, 'feats')
+        assert f.dim() == 4 and f.is_contiguous() and f.dtype == f0.dtype and f.shape[0] == N and f.shape[3] == C and f.device == f0.device
+        lv.level[l].data, lv.level[l].H, lv.level[l].W, lv.level[l].spatial_scale = f.data_ptr(), int(f.shape[1]), int(f.shape[2]), float(sc)
+    assert f0.dtype in (torch.float32, torch.bfloat16)
+    _dev(rois, 'rois')
+    _dev(levels, 'levels')
+    K, P = int(rois.shape[0]), int(output_size)
+    assert rois.dtype == torch.float32 and rois.shape == (K, 5) and rois.is_contiguous()
+    assert levels.dtype == torch.int32 and levels.shape == (K,) and levels.is_contiguous()
+    if out is None:
+        out = torch.empty((K, C, P, P), dtype=torch.float32, device=f0.device)
+    assert out.dtype == torch.float32 and out.shape == (K, C, P, P) and out.is_contiguous() and out.device == f0.device
+    with _timed(tag or 'roi_align'):
+        _check(lib().sc2_roi_align(lv, len(feats_nhwc), N, C, 1 if f0.dtype == torch.bfloat16 else 0, _ptr(rois), _ptr(levels), K, P,
+                                   int(sampling_ratio), _ptr(out), _stream()), 'roi_align')
+    return out
 
 
 def bn_train_fwd(x_nhwc, gamma, beta, running_mean, running_var, momentum, eps, relu, residual=None, tag=None):
