@@ -106,7 +106,7 @@ class FeatureExtractionBackbone(UpdatableBackbone):
 
     def _hip_layer(self, name, module):
         """HipHead of one child, or None if the child is not a stack of Bottleneck blocks (dilated 3x3 layers -- DeepLab's
-        layer3 / layer4 -- run as d * d undilated launches on the phase grids, `head._Conv._dilated`)."""
+        layer3 / layer4 -- run as d * d undilated launches on the phase grids, `head._Conv._phase_grids`)."""
         from .head import HipHead
         from .resnet import Bottleneck
         if not (isinstance(module, nn.Sequential) and len(module) > 0 and all(isinstance(b, Bottleneck) for b in module)):

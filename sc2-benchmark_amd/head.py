@@ -90,52 +90,41 @@ class ConvSpec(object):
 
 
 class _Conv(object):
+    """One folded conv + norm layer launch: `route` says which kernel a call takes, `__call__` makes that launch."""
+
     def __init__(self, conv, bn, tag):
         assert conv.bias is None and conv.groups == 1
-        self.w, self.b, self.k_order, w_folded = _fold(conv, bn)
+        w_tile, self.b, self.k_order, w_folded = _fold(conv, bn)
         self.w_folded = w_folded       # f32 OIHW with the norm layer's scale folded in (frozen.py builds the data gradient from it)
-        self.cout = conv.out_channels
+        self.cin, self.cout = conv.in_channels, conv.out_channels
         self.k = conv.kernel_size
         self.stride = conv.stride
         self.pad = conv.padding
         self.dilation = conv.dilation
         self.tag = tag
-        # HBM-bound 1x1 layers with a short K and a wide N run on the persistent streaming kernel
-        self.stream = hip.conv1x1_stream_supported(conv.in_channels, conv.out_channels, self.k[0], self.k[1],
-                                                   self.stride, self.pad) and (conv.dilation == (1, 1) or self.k == (1, 1))
-        # K = 1024 / 2048 1x1 layers (conv1 of layer3 / layer4, layer4's downsample): weights resident in registers, one
-        # channel chunk per workgroup
-        self.kres = (not self.stream) and (conv.dilation == (1, 1) or self.k == (1, 1)) and hip.conv1x1_kres_supported(
-            conv.in_channels, conv.out_channels, self.k[0], self.k[1], self.stride, self.pad)
-        if self.stream or self.kres:
-            self.w_frag = hip.pack_weight_fragments(w_folded.reshape(w_folded.shape[0], w_folded.shape[1]))
-        # long-K 1x1 layers that are not HBM-bound: the window-plane 1x1 kernel (which layers: _win1_policy, by measurement)
-        self.w_win1 = None
-        if self.k == (1, 1) and _win1_policy(conv.in_channels, conv.out_channels, self.stride[0]) and \
-                hip.conv1x1_win_supported(conv.in_channels, conv.out_channels, 1, 1, self.stride, self.pad):
-            self.w_win1 = hip.pack_conv_win(w_folded)
-        # long-K 1x1 layers that are plain compute-heavy GEMMs: the eight-wave 256-channel kernel, on conv1x1_win's weight stream (not the
-        # bare data-gradient convolutions of frozen.py: the gradient paths stay where they are).  Which layers it runs is asked per call
-        # (_w8_policy), so hip.configure(conv1x1_w8=...) works on a built head; the stream is packed here only for the layers the policy
-        # in force selects, a layer switched in later packs its own at its first call (_w8_weights)
-        self.cin = conv.in_channels
-        self.w8_ok = bn is not None and self.k == (1, 1) and hip.conv1x1_w8_supported(conv.in_channels, conv.out_channels, 1, 1,
-                                                                                      self.stride, self.pad)
-        self.w_w8 = None
-        if self.w8_ok and _w8_policy(self.cin, self.cout, self.stride[0]):
-            self._w8_weights()
-        # 3x3 stride-1 layers on 28 / 14 / 7 pixel maps (conv2 of every block at the 224 x 224 operating point): the
-        # window-plane kernel; other map sizes stay on the implicit-GEMM tile kernel (decided per call, by the map size)
         self.w2d = w_folded.reshape(w_folded.shape[0], w_folded.shape[1]).to(torch.bfloat16) if self.k == (1, 1) else None
-        self.w_win = None
-        if hip.conv3x3_win_supported(14, 14, conv.in_channels, conv.out_channels, self.k[0], self.k[1], self.stride, self.pad,
-                                     conv.dilation):   # (14 x 14 is a supported map of both the stride-1 and the stride-2 form)
-            self.w_win = hip.pack_conv3x3_win(w_folded)
-        # Dilated 3x3 layers (DeepLab's layer3 / layer4, torchvision `replace_stride_with_dilation`): a stride-1 conv with
-        # dilation d and padding d is d*d independent UNDILATED pad-1 convs on the phase grids x[a::d, b::d] -- the same
-        # weights, the same kernels, outputs scattered back to y[a::d, b::d]
-        # (round 5: sc2_conv2d_fwd takes the dilation itself -- one launch on the generic tile with runtime dilation -- whenever the
-        #  layer has more than 96 output channels; narrower layers keep the phase-grid form below)
+        self._packed = {'tile': w_tile}      # the packed weight by layout: see `packed`
+        geom = (self.cin, self.cout, self.k[0], self.k[1], self.stride, self.pad)
+        undilated = self.dilation == (1, 1) or self.k == (1, 1)
+        # The routes this layer is OPEN to, by its shape and the policy in force now (`route` lists which switch is read when).
+        # HBM-bound 1x1 layers with a short K and a wide N: the persistent streaming kernel
+        self.stream = hip.conv1x1_stream_supported(*geom) and undilated
+        # K = 1024 / 2048 1x1 layers (conv1 of layer3 / layer4, layer4's downsample): weights resident in registers, one channel
+        # chunk per workgroup
+        self.kres = (not self.stream) and undilated and hip.conv1x1_kres_supported(*geom)
+        # long-K 1x1 layers that are not HBM-bound: the window-plane 1x1 kernel (which layers: _win1_policy, by measurement)
+        self.win1 = self.k == (1, 1) and _win1_policy(self.cin, self.cout, self.stride[0]) and hip.conv1x1_win_supported(*geom)
+        # long-K 1x1 layers that are plain compute-heavy GEMMs: the eight-wave 256-channel kernel, on conv1x1_win's weight stream (not
+        # the bare data-gradient convolutions of frozen.py: the gradient paths stay where they are).  WHICH of these layers it runs is
+        # asked per call (_w8_policy), so hip.configure(conv1x1_w8=...) works on a built head
+        self.w8_ok = bn is not None and self.k == (1, 1) and hip.conv1x1_w8_supported(*geom)
+        # 3x3 stride-1 layers on 28 / 14 / 7 pixel maps and stride-2 layers on 56 / 28 / 14 pixel maps (conv2 of every block at the
+        # 224 x 224 operating point): the window-plane kernel; other map sizes stay on the implicit-GEMM tile kernel (decided per call,
+        # by the map size; 14 x 14 is a supported map of both the stride-1 and the stride-2 form)
+        self.win3 = hip.conv3x3_win_supported(14, 14, *geom, self.dilation)
+        # Dilated 3x3 layers (DeepLab's layer3 / layer4, torchvision `replace_stride_with_dilation`): sc2_conv2d_fwd takes the dilation
+        # itself -- one launch on the generic tile with runtime dilation -- whenever the layer has more than 96 output channels;
+        # narrower layers run as phase grids (`_phase_grids`)
         self.native_dilation = self.dilation != (1, 1) and self.k != (1, 1) and hip.weight_rows(self.cout) % 128 == 0
         if self.dilation != (1, 1) and not self.native_dilation:
             d = self.dilation[0]
@@ -144,13 +133,107 @@ class _Conv(object):
                 raise hip.Sc2Error('the HIP head supports dilation on layers of <= 96 output channels only as 3x3 stride-1 with '
                                    'padding == dilation (got kernel {}, stride {}, padding {}, dilation {})'.format(
                                        self.k, self.stride, self.pad, self.dilation))
+        # Packed here: the layouts of the routes open now, so that no first call -- which may be inside a graph capture -- packs.  A
+        # layer that hip.configure(conv1x1_w8=...) switches in later packs at its first call, as does conv1 of a pair launch (HipHead)
+        if self.stream or self.kres:
+            self.packed('frag')
+        if self.win1 or self.win3 or (self.w8_ok and _w8_policy(self.cin, self.cout, self.stride[0])):
+            self.packed('win')
 
-    def _w8_weights(self):
-        if self.w_w8 is None:
-            self.w_w8 = self.w_win1 if self.w_win1 is not None else hip.pack_conv_win(self.w_folded)
-        return self.w_w8
+    _PACKERS = {'tile': lambda c: hip.pack_conv_weight(c.w_folded, c.k_order),       # the implicit-GEMM tile kernel (sc2_conv2d_fwd)
+                'frag': lambda c: hip.pack_weight_fragments(c.w_folded.reshape(c.cout, c.cin)),   # 1x1: stream, kres, the pair launch
+                'win': lambda c: hip.pack_conv_win(c.w_folded)}                       # the window-plane kernels (win1, w8, win3)
 
-    def _dilated(self, x, epilogue):
+    def packed(self, layout):
+        """The folded weight in `layout` ('tile' / 'frag' / 'win'), packed once and kept: one device copy per layout and layer."""
+        w = self._packed.get(layout)
+        if w is None:
+            w = self._packed[layout] = self._PACKERS[layout](self)
+        return w
+
+    w = property(lambda self: self._packed['tile'])
+
+    def route(self, x_shape, epilogue, has_ep_x=False, has_mask=False):
+        """The launch a call with these operands takes: the first name in the order below whose condition holds.  No tensor, no launch.
+
+        plain calls    w8 > win1 > stream > kres > win3 > tile
+        dilated 3x3    tile_dilated > phase_grids
+        masked calls   win1_mask > stream_mask > win3_mask > mask_unfused      (ep_mask: the ReLU gradient behind a data gradient)
+
+        Switches read when the layer is BUILT, through the flags they set (`stream`, `kres`, `win1`, `win3`): conv_stream, conv_kres,
+        conv1x1_win, and conv_win / conv_win_s2 for whether the layer is open to win3 at all.  hip.configure() of these reaches only
+        layers built afterwards.
+        Switches read at EVERY call: conv1x1_w8 (_w8_policy), conv_win / conv_win_s2 (hip.conv3x3_win_supported, with the map size),
+        relu_mask_fused, conv_dilation; and, in HipHead.forward, conv1x1_pair.
+
+        Kept as they were, oddities included: the 32-bit operand bound covers input and output for w8 / win1 (the output counted at
+        the INPUT's map size) but only the input for win3; kres takes no residual, hence no EPI_BIAS_ADD_RELU; w8 is closed to bare
+        convolutions (`w8_ok`: bn is None); the masked win3 form needs stride 1 and no ep_x, and a layer open to stream or kres is not
+        asked for it."""
+        N, H, W, C = x_shape
+        n_in, n_out, s = N * H * W * C, N * H * W * self.cout, self.stride[0]
+        if has_mask:
+            if hip.host_policy.relu_mask_fused and self.dilation == (1, 1) and hip._fits32(n_in, n_out):
+                if self.win1:
+                    return 'win1_mask'
+                if self.stream and hip.conv1x1_stream_mask_supported(C, self.cout, s):
+                    return 'stream_mask'
+                if not has_ep_x and not (self.stream or self.kres) and self.win3 and self.stride == (1, 1) and \
+                        hip.conv3x3_win_supported(H, W, C, self.cout, self.k[0], self.k[1], self.stride, self.pad):
+                    return 'win3_mask'
+            return 'mask_unfused'
+        if self.dilation != (1, 1) and self.k != (1, 1):
+            return 'tile_dilated' if self.native_dilation and hip.host_policy.conv_dilation else 'phase_grids'   # ('0': A/B)
+        no_add = epilogue == hip.EPI_BIAS or epilogue == hip.EPI_BIAS_RELU
+        fusable = no_add or epilogue == hip.EPI_BIAS_ADD_RELU
+        if self.w8_ok and fusable and _w8_policy(self.cin, self.cout, s) and hip._fits32(n_in, n_out):
+            return 'w8'
+        if self.win1 and fusable and hip._fits32(n_in, n_out):
+            return 'win1'
+        if self.stream and fusable:
+            return 'stream'
+        if self.kres and no_add:
+            return 'kres'
+        if self.win3 and no_add and hip._fits32(n_in) and \
+                hip.conv3x3_win_supported(H, W, C, self.cout, self.k[0], self.k[1], self.stride, self.pad):
+            return 'win3'
+        return 'tile'
+
+    # the fused kernels by route name: (hip's launcher -- looked up at the call: tests and tools replace it --, weight layout, takes a
+    # residual, takes a mask)
+    _FUSED = {'w8': ('conv1x1_w8_fwd', 'win', True, False), 'kres': ('conv1x1_kres_fwd', 'frag', False, False),
+              'win1': ('conv1x1_win_fwd', 'win', True, True), 'win1_mask': ('conv1x1_win_fwd', 'win', True, True),
+              'stream': ('conv1x1_stream_fwd', 'frag', True, True), 'stream_mask': ('conv1x1_stream_fwd', 'frag', True, True),
+              'win3': ('conv3x3_win_fwd', 'win', False, True), 'win3_mask': ('conv3x3_win_fwd', 'win', False, True)}
+
+    def __call__(self, x, epilogue, ep_x=None, ep_mask=None):
+        """ep_mask (bf16 like the output, epilogue EPI_BIAS): y = ep_mask > 0 ? conv + bias [+ ep_x] : 0 -- the ReLU gradient behind a
+        data gradient (frozen.py; ep_x: a second gradient that reaches the same tensor, the skip path's, added in front of the mask);
+        in the launch's epilogue on the window-plane and streaming kernels, else as a `relu_bwd` pass behind the unmasked launch."""
+        assert ep_mask is None or epilogue == hip.EPI_BIAS
+        name = self.route(x.shape, epilogue, ep_x is not None, ep_mask is not None)
+        if name == 'mask_unfused':
+            return hip.relu_bwd(self(x, epilogue), ep_mask, add=ep_x)
+        if name == 'phase_grids':
+            assert ep_x is None
+            return self._phase_grids(x, epilogue)
+        if name == 'tile' or name == 'tile_dilated':      # (a dilated 1x1 layer is an undilated one: 'tile' passes no dilation)
+            return hip.conv2d_fwd(x, self.w, self.cout, self.k[0], self.k[1], self.stride, self.pad, epilogue=epilogue, ep_x=ep_x,
+                                  ep_beta=self.b, tag=self.tag, k_order=self.k_order,
+                                  dilation=self.dilation if name == 'tile_dilated' else 1)
+        # (epilogue, ep_x, ep_mask) in the fused kernels' terms; a route that takes no residual or no mask is chosen only without one
+        launcher, layout, takes_residual, takes_mask = self._FUSED[name]
+        kw = {}
+        if takes_residual:
+            kw['residual'] = ep_x if ep_mask is not None or epilogue == hip.EPI_BIAS_ADD_RELU else None
+        if takes_mask:
+            kw['mask'] = ep_mask
+        return getattr(hip, launcher)(x, self.packed(layout), self.b, stride=self.stride[0], relu=epilogue != hip.EPI_BIAS, tag=self.tag,
+                                      **kw)
+
+    def _phase_grids(self, x, epilogue):
+        """a stride-1 conv with dilation d and padding d is d*d independent UNDILATED pad-1 convs on the phase grids x[a::d, b::d] --
+        the same weights, the same kernel, outputs scattered back to y[a::d, b::d]"""
         d = self.dilation[0]
         N, H, W, _ = x.shape
         y = torch.empty((N, H, W, self.cout), dtype=torch.bfloat16, device=x.device)
@@ -160,52 +243,6 @@ class _Conv(object):
                                     ep_beta=self.b, tag=self.tag, k_order=self.k_order)
                 y[:, a::d, b::d, :] = ys
         return y
-
-    def __call__(self, x, epilogue, ep_x=None, ep_mask=None):
-        """ep_mask (bf16 like the output, epilogue EPI_BIAS): y = ep_mask > 0 ? conv + bias : 0 -- the ReLU gradient behind a data
-        gradient (frozen.py); in the launch's epilogue on the window-plane kernels, else as a `relu_bwd` pass behind it."""
-        if ep_mask is not None:
-            # (ep_x with ep_mask: a second gradient that reaches the same tensor, added in front of the mask -- the skip path's)
-            assert epilogue == hip.EPI_BIAS
-            fits = max(x.numel(), x.shape[0] * x.shape[1] * x.shape[2] * self.cout) * 2 < 0x7FF00000
-            if hip.host_policy.relu_mask_fused and self.dilation == (1, 1) and fits:
-                if self.w_win1 is not None:
-                    return hip.conv1x1_win_fwd(x, self.w_win1, self.b, stride=self.stride[0], residual=ep_x, mask=ep_mask, tag=self.tag)
-                if self.stream and hip.conv1x1_stream_mask_supported(x.shape[3], self.cout, self.stride[0]):
-                    return hip.conv1x1_stream_fwd(x, self.w_frag, self.b, stride=self.stride[0], residual=ep_x, mask=ep_mask, tag=self.tag)
-                if ep_x is None and not (self.stream or self.kres) and self.w_win is not None and self.stride == (1, 1) and \
-                        hip.conv3x3_win_supported(x.shape[1], x.shape[2], x.shape[3], self.cout, self.k[0], self.k[1], self.stride, self.pad):
-                    return hip.conv3x3_win_fwd(x, self.w_win, self.b, tag=self.tag, stride=1, mask=ep_mask)
-            return hip.relu_bwd(self(x, epilogue), ep_mask, add=ep_x)
-        if self.dilation != (1, 1) and self.k != (1, 1):
-            if self.native_dilation and hip.host_policy.conv_dilation:      # ('0': A/B, the phase grids)
-                return hip.conv2d_fwd(x, self.w, self.cout, self.k[0], self.k[1], self.stride, self.pad, epilogue=epilogue,
-                                      ep_x=ep_x, ep_beta=self.b, tag=self.tag, k_order=self.k_order, dilation=self.dilation)
-            assert ep_x is None
-            return self._dilated(x, epilogue)
-        if self.w8_ok and epilogue in (hip.EPI_BIAS, hip.EPI_BIAS_RELU, hip.EPI_BIAS_ADD_RELU) and \
-                _w8_policy(self.cin, self.cout, self.stride[0]) and \
-                max(x.numel(), x.shape[0] * x.shape[1] * x.shape[2] * self.cout) * 2 < 0x7FF00000:
-            return hip.conv1x1_w8_fwd(x, self._w8_weights(), self.b, stride=self.stride[0],
-                                      residual=ep_x if epilogue == hip.EPI_BIAS_ADD_RELU else None,
-                                      relu=epilogue != hip.EPI_BIAS, tag=self.tag)
-        if self.w_win1 is not None and epilogue in (hip.EPI_BIAS, hip.EPI_BIAS_RELU, hip.EPI_BIAS_ADD_RELU) and \
-                max(x.numel(), x.shape[0] * x.shape[1] * x.shape[2] * self.cout) * 2 < 0x7FF00000:
-            return hip.conv1x1_win_fwd(x, self.w_win1, self.b, stride=self.stride[0],
-                                       residual=ep_x if epilogue == hip.EPI_BIAS_ADD_RELU else None,
-                                       relu=epilogue != hip.EPI_BIAS, tag=self.tag)
-        if self.stream and epilogue in (hip.EPI_BIAS, hip.EPI_BIAS_RELU, hip.EPI_BIAS_ADD_RELU):
-            return hip.conv1x1_stream_fwd(x, self.w_frag, self.b, stride=self.stride[0],
-                                          residual=ep_x if epilogue == hip.EPI_BIAS_ADD_RELU else None,
-                                          relu=epilogue != hip.EPI_BIAS, tag=self.tag)
-        if self.kres and epilogue in (hip.EPI_BIAS, hip.EPI_BIAS_RELU):
-            return hip.conv1x1_kres_fwd(x, self.w_frag, self.b, stride=self.stride[0], relu=epilogue == hip.EPI_BIAS_RELU,
-                                        tag=self.tag)
-        if self.w_win is not None and epilogue in (hip.EPI_BIAS, hip.EPI_BIAS_RELU) and x.numel() * 2 < 0x7FF00000 and \
-                hip.conv3x3_win_supported(x.shape[1], x.shape[2], x.shape[3], self.cout, self.k[0], self.k[1], self.stride, self.pad):
-            return hip.conv3x3_win_fwd(x, self.w_win, self.b, relu=epilogue == hip.EPI_BIAS_RELU, tag=self.tag, stride=self.stride[0])
-        return hip.conv2d_fwd(x, self.w, self.cout, self.k[0], self.k[1], self.stride, self.pad, epilogue=epilogue,
-                              ep_x=ep_x, ep_beta=self.b, tag=self.tag, k_order=self.k_order)
 
 
 class HipHead(object):
@@ -249,12 +286,6 @@ class HipHead(object):
         return (c3.k == (1, 1) and c1n.k == (1, 1) and c3.stride == (1, 1) and c1n.stride == (1, 1) and c3.stream and
                 c3.w2d is not None and c1n.w2d is not None and c3.w2d.shape[0] == c1n.w2d.shape[1] and
                 hip.conv1x1_pair_supported(c3.w2d.shape[1], c3.cout, c1n.cout))
-
-    @staticmethod
-    def _pair_w1(c1n):
-        if getattr(c1n, 'w_frag_pair', None) is None:
-            c1n.w_frag_pair = hip.pack_weight_fragments(c1n.w_folded.reshape(c1n.w_folded.shape[0], c1n.w_folded.shape[1]))
-        return c1n.w_frag_pair
 
     def tail_spec(self):
         """(W1 [128, 256], bias1, Wds [512, 256], bias_ds) of the first block when it is layer2.0 of a ResNet-50 tail (conv1 1x1
@@ -313,11 +344,11 @@ class HipHead(object):
             if join is not None:
                 torch.cuda.current_stream(h.device).wait_event(join)
             nxt = self.blocks[bi + 1] if bi + 1 < len(self.blocks) else None
-            if nxt is not None and self._pair_ok(c3, nxt[0]) and o.numel() // o.shape[-1] * c3.cout * 2 < 0x7FF00000:
+            if nxt is not None and self._pair_ok(c3, nxt[0]) and hip._fits32(o.numel() // o.shape[-1] * c3.cout):
                 # conv3 + residual + ReLU of this block and conv1 + ReLU of the next in one launch (conv1x1_pair.hip): the
                 # block output is written once and feeds the second GEMM from LDS (layer2's block boundaries, and layer2.3 ->
                 # layer3.0, whose downsample then reads the block output as any other identity path does)
-                h, o_next = hip.conv1x1_pair_fwd(o, c3.w_frag, c3.b, identity.contiguous(), self._pair_w1(nxt[0]), nxt[0].b,
+                h, o_next = hip.conv1x1_pair_fwd(o, c3.packed('frag'), c3.b, identity.contiguous(), nxt[0].packed('frag'), nxt[0].b,
                                                  tag=c3.tag + '+' + nxt[0].tag)
             else:
                 h = c3(o, hip.EPI_BIAS_ADD_RELU, ep_x=identity)

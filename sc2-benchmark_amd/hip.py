@@ -401,6 +401,16 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
+def _pair2(v):
+    """a stride / padding / dilation given as an int or as (h, w) -> (h, w)"""
+    return (v, v) if isinstance(v, int) else v
+
+
+def _fits32(*element_counts):
+    """True if bf16 tensors of these element counts stay within the 32-bit byte offsets the buffer-addressed kernels use."""
+    return max(element_counts) * 2 < 0x7FF00000
+
+
 # --------------------------------------------------------------------------------------------- #
 # layout
 # --------------------------------------------------------------------------------------------- #
@@ -519,8 +529,7 @@ def conv_patch_supported(x_shape, cout, kh, kw, stride, pad, out_format=OUT_BF16
     """True if this conv runs on the LDS-resident-patch kernel (weights then packed K_SLAB_MAJOR | K_B_FRAG_MAJOR)."""
     if not host_policy.conv_patch:      # A/B switch (tools/)
         return False
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(pad)
     N, H, W, Cin = x_shape
     OH = (H + 2 * ph - kh) // sh + 1
     OW = (W + 2 * pw - kw) // sw + 1
@@ -591,7 +600,7 @@ def gdn1_bwd_gemm(x_nhwc, w_packed, epilogue, ep_x, ep_x2, beta=None, tag=None):
 def gdn1_rows_supported(x_nhwc, C):
     """True if GDN1 over C channels of this bf16 [..., C] tensor runs on the resident-row kernel (C = 96, 256 or 512, < 2 GB)."""
     return bool(host_policy.gdn_rows) and x_nhwc.dtype == torch.bfloat16 and x_nhwc.is_cuda and x_nhwc.is_contiguous() and \
-        x_nhwc.shape[-1] == C and x_nhwc.numel() * 2 < 0x7FF00000 and bool(lib().sc2_gdn1_rows_supported(C))
+        x_nhwc.shape[-1] == C and _fits32(x_nhwc.numel()) and bool(lib().sc2_gdn1_rows_supported(C))
 
 
 def gdn1_rows_fwd(x_nhwc, gamma_frag, beta, inverse, tag=None):
@@ -684,8 +693,7 @@ def conv2d_wgrad(x_nhwc, gy_nhwc, kh, kw, stride, pad, x_abs=False):
     _dev(gy_nhwc, 'gy')
     assert x_nhwc.dtype == torch.bfloat16 and gy_nhwc.dtype == torch.bfloat16
     assert x_nhwc.is_contiguous() and gy_nhwc.is_contiguous()
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(pad)
     N, H, W, Cin = x_nhwc.shape
     OH = (H + 2 * ph - kh) // sh + 1
     OW = (W + 2 * pw - kw) // sw + 1
@@ -710,8 +718,7 @@ def conv2d_dgrad(gy_nhwc, weight, stride, pad, in_hw, out_dtype=torch.bfloat16, 
     `cache`: a dict owned by the caller of a FROZEN weight -- the packed sub-filters are then built once, not per step.
     """
     cout, cin, KH, KW = weight.shape
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(pad)
     H, W = in_hw
     N = gy_nhwc.shape[0]
     fmt = OUT_BF16_NHWC if out_dtype == torch.bfloat16 else OUT_F32_NHWC
@@ -739,7 +746,7 @@ def conv2d_dgrad(gy_nhwc, weight, stride, pad, in_hw, out_dtype=torch.bfloat16, 
                    conv2x2_win_supported(tuple(gy_nhwc.shape), cin, len(khs), len(kws), 1, pad_h))
             # ... and a 512-channel gradient (dec.conv2: 512 -> 256, k2, p0) as two 256-channel halves of that kernel (pad 1)
             win2 = (not win and cin == 512 and pad_h == 1 and sh == 1 and sw == 1 and out_dtype == torch.bfloat16 and pad_w == 1 and
-                    gy_nhwc.is_contiguous() and host_policy.dgrad_win_halves and gx.numel() * 2 < 0x7FF00000 and
+                    gy_nhwc.is_contiguous() and host_policy.dgrad_win_halves and _fits32(gx.numel()) and
                     conv2x2_win_supported(tuple(gy_nhwc.shape), 256, len(khs), len(kws), 1, 1))
             # (the packed sub-filters belong to THIS weight tensor at this version, stride and padding: a cache dict shared
             #  between layers, or kept across an optimizer step, must miss -- ADVICE r4)
@@ -808,8 +815,7 @@ def deconv_parity_classes(weight, stride, padding):
 def conv_fused_gdn_supported(x_shape, cout, kh, kw, stride, pad, out_format=OUT_BF16_NHWC):
     """Non-zero if conv + GDN1 runs as ONE launch (EPI_FUSED_GDN / EPI_FUSED_IGDN) for this geometry (x_shape =
     [N,H,W,Cin]): 1 = ep_x takes GDN1.effective()'s packed-row gamma, 2 = GDN1.effective_fragments()'s."""
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(pad)
     N, H, W, Cin = x_shape
     OH = (H + 2 * ph - kh) // sh + 1
     OW = (W + 2 * pw - kw) // sw + 1
@@ -830,9 +836,7 @@ def conv2d_fwd(x_nhwc, w_packed, cout, kh, kw, stride, pad, a_op=AOP_NONE, epilo
     _dev(w_packed, 'w_packed')
     assert x_nhwc.dtype == torch.bfloat16 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
     assert w_packed.dtype == torch.bfloat16 and w_packed.is_contiguous()
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
-    dh, dw = (dilation, dilation) if isinstance(dilation, int) else dilation
+    (sh, sw), (ph, pw), (dh, dw) = _pair2(stride), _pair2(pad), _pair2(dilation)
     N, H, W, Cin = x_nhwc.shape
     OH = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
     OW = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
@@ -871,8 +875,7 @@ def conv2d_fwd(x_nhwc, w_packed, cout, kh, kw, stride, pad, a_op=AOP_NONE, epilo
 
 def conv2x2_gdn512_supported(cin, cout, kh, kw, stride, pad):
     """True if Conv2d(cin -> 512, k2, s1, p1) followed by a 512-channel GDN1 runs as the single fused launch."""
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(pad)
     return sh == sw and ph == pw and bool(lib().sc2_conv2x2_gdn512_supported(cin, cout, kh, kw, sh, ph))
 
 
@@ -924,8 +927,7 @@ def conv2_gdn48_supported(x_shape, cout, kh, kw, stride, pad):
     """True if this conv + GDN1(48) runs as the persistent weights-in-registers launch (96 -> 48, k5 s2 p2, W = 112)."""
     if not host_policy.conv2_fused:      # A/B switch (tools/)
         return False
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(pad)
     return (len(x_shape) == 4 and (kh, kw, sh, sw, ph, pw) == (5, 5, 2, 2, 2, 2) and
             bool(lib().sc2_conv2_gdn48_supported(x_shape[3], cout, x_shape[2])))
 
@@ -966,7 +968,7 @@ def maxpool_nhwc(x_nhwc, kernel, stride, pad, tag=None):
     _dev(x_nhwc, 'x')
     assert x_nhwc.dtype == torch.bfloat16 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
     N, H, W, C = x_nhwc.shape
-    (kh, kw), (sh, sw), (ph, pw) = [(v, v) if isinstance(v, int) else tuple(v) for v in (kernel, stride, pad)]
+    (kh, kw), (sh, sw), (ph, pw) = [_pair2(v) for v in (kernel, stride, pad)]
     out = torch.empty((N, (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1, C), dtype=torch.bfloat16, device=x_nhwc.device)
     with _timed(tag or 'maxpool'):
         _check(lib().sc2_maxpool_nhwc(_ptr(x_nhwc), _ptr(out), N, H, W, C, kh, kw, sh, sw, ph, pw, _stream()), 'maxpool_nhwc')
@@ -981,7 +983,7 @@ def maxpool_affine_relu_nhwc(x_nhwc, a, b, kernel, stride, pad, tag=None):
     N, H, W, C = x_nhwc.shape
     for t in (_dev(a, 'a'), _dev(b, 'b')):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C
-    (kh, kw), (sh, sw), (ph, pw) = [(v, v) if isinstance(v, int) else tuple(v) for v in (kernel, stride, pad)]
+    (kh, kw), (sh, sw), (ph, pw) = [_pair2(v) for v in (kernel, stride, pad)]
     out = torch.empty((N, (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1, C), dtype=torch.bfloat16, device=x_nhwc.device)
     with _timed(tag or 'maxpool_affine_relu'):
         _check(lib().sc2_maxpool_affine_relu_nhwc(_ptr(x_nhwc), _ptr(out), _ptr(a), _ptr(b), N, H, W, C, kh, kw, sh, sw, ph, pw, _stream()),
@@ -1245,8 +1247,7 @@ def pack_weight_fragments(w2d):
 
 def conv1x1_kres_supported(cin, cout, kh, kw, stride, pad):
     """True if this 1x1 conv runs on the weights-in-registers kernel (K = 1024 or 2048, stride 1 or 2)."""
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(pad)
     mode = str(host_policy.conv_kres)          # A/B switch (tools/): 0 off, 2 = also the K = 2048 layers
     if mode == '0':
         return False
@@ -1255,28 +1256,52 @@ def conv1x1_kres_supported(cin, cout, kh, kw, stride, pad):
     return (kh, kw, ph, pw) == (1, 1, 0, 0) and sh == sw and bool(lib().sc2_conv1x1_kres_supported(cin, cout, sh))
 
 
-def conv1x1_kres_fwd(x_nhwc, w_frag, bias, stride=1, relu=False, tag=None):
-    """x bf16 [N,H,W,Cin] -> bf16 [N,OH,OW,Cout]; w_frag = pack_weight_fragments(w[Cout, Cin]); Cin 1024 or 2048."""
+# the two weight streams of these kernels: (the dimension that counts 16-channel tiles of Cout, the shape as a function of (Cin, Cout))
+_ROWS_FRAG = (0, lambda cin, cout: (cout // 16, cin // 32, 64, 8))                      # pack_weight_fragments(w[Cout, Cin])
+_WIN_FRAG = {taps: (1, lambda cin, cout, taps=taps: (cin // 32 * taps, cout // 16, 64, 8)) for taps in (1, 9)}   # pack_conv_win, by KH * KW
+
+
+def _frag_conv_fwd(what, x_nhwc, w_frag, bias, frag_shape, stride, relu, tag, *extra, stride_arg=True, out=None):
+    """The frame of the (x, w_frag, bias) -> bf16 NHWC wrappers around `sc2_<what>(x, w_frag, bias, *extra, out, N, H, W, Cin, Cout,
+    [stride,] relu, stream)`.  Checks x, the fragment stream (`frag_shape`: one of the two rules above) and the bias; makes the output
+    [N, (H - 1) // stride + 1, (W - 1) // stride + 1, Cout] -- a 1x1 conv without padding or a 3x3 conv with padding 1 -- or views `out`,
+    a contiguous bf16 tensor of that size, as it; checks each of `extra`, (name, tensor or None) operands laid out like the output
+    ('mask' excludes relu); launches under the kernel timer (default tag: `what` without '_fwd')."""
     for t, name in ((x_nhwc, 'x'), (w_frag, 'w_frag'), (bias, 'bias')):
         _dev(t, name)
     assert x_nhwc.dtype == torch.bfloat16 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
     N, H, W, Cin = x_nhwc.shape
-    cout = w_frag.shape[0] * 16
-    assert w_frag.dtype == torch.bfloat16 and w_frag.is_contiguous() and tuple(w_frag.shape) == (cout // 16, Cin // 32, 64, 8)
+    cout = w_frag.shape[frag_shape[0]] * 16
+    assert w_frag.dtype == torch.bfloat16 and w_frag.is_contiguous() and tuple(w_frag.shape) == frag_shape[1](Cin, cout)
     assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == cout
-    stride = int(stride)
-    out = torch.empty((N, (H - 1) // stride + 1, (W - 1) // stride + 1, cout), dtype=torch.bfloat16, device=x_nhwc.device)
-    with _timed(tag or 'conv1x1_kres'):
-        _check(lib().sc2_conv1x1_kres_fwd(_ptr(x_nhwc), _ptr(w_frag), _ptr(bias), _ptr(out), N, H, W, Cin, cout, stride,
-                                          1 if relu else 0, _stream()), 'conv1x1_kres_fwd')
+    shape = (N, (H - 1) // stride + 1, (W - 1) // stride + 1, cout)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.bfloat16, device=x_nhwc.device)
+    else:
+        _dev(out, 'out')
+        assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.numel() == N * shape[1] * shape[2] * cout
+        out = out.view(shape)
+    ptrs = [_ptr(x_nhwc), _ptr(w_frag), _ptr(bias)]
+    for name, t in extra:
+        if t is not None:
+            _dev(t, name)
+            assert t.dtype == torch.bfloat16 and t.is_contiguous() and tuple(t.shape) == shape and not (relu and name == 'mask'), name
+        ptrs.append(_ptr(t))
+    dims = (N, H, W, Cin, cout, stride) if stride_arg else (N, H, W, Cin, cout)
+    with _timed(tag or what[:-4]):
+        _check(getattr(lib(), 'sc2_' + what)(*ptrs, _ptr(out), *dims, 1 if relu else 0, _stream()), what)
     return out
+
+
+def conv1x1_kres_fwd(x_nhwc, w_frag, bias, stride=1, relu=False, tag=None):
+    """x bf16 [N,H,W,Cin] -> bf16 [N,OH,OW,Cout]; w_frag = pack_weight_fragments(w[Cout, Cin]); Cin 1024 or 2048."""
+    return _frag_conv_fwd('conv1x1_kres_fwd', x_nhwc, w_frag, bias, _ROWS_FRAG, int(stride), relu, tag)
 
 
 def conv3x3_win_supported(h, w, cin, cout, kh, kw, stride, pad, dilation=(1, 1)):
     """True if this conv runs on the window-plane 3x3 kernel: stride 1, pad 1 on 28 / 14 / 7 pixel maps, or stride 2, pad 1 on
     56 / 28 / 14 pixel maps (h, w = the INPUT map)."""
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(pad)
     if not host_policy.conv_win:      # A/B switch (tools/)
         return False
     if (kh, kw, ph, pw) != (3, 3, 1, 1) or tuple(dilation) != (1, 1):
@@ -1284,7 +1309,7 @@ def conv3x3_win_supported(h, w, cin, cout, kh, kw, stride, pad, dilation=(1, 1))
     if (sh, sw) == (2, 2):
         return host_policy.conv_win_s2 and bool(lib().sc2_conv3x3s2_win_supported(h, w, cin, cout))
     return (sh, sw) == (1, 1) and \
-        bool(lib().sc2_conv3x3_win_supported(h, w, cin, cout))   # (the caller checks the 2 GB operand bound: head._Conv)
+        bool(lib().sc2_conv3x3_win_supported(h, w, cin, cout))   # (the caller checks the 2 GB operand bound: head._Conv.route)
 
 
 def pack_conv_win(w):
@@ -1308,12 +1333,11 @@ def pack_conv3x3_win(w):
 
 def conv2x2_win_supported(x_shape, cout, kh, kw, stride, pad):
     """True if this conv runs on the window-plane decoder kernel (k2, s1, Cout 256, width 56 / pad 0 or 55 / pad 1)."""
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(pad)
     if not host_policy.conv2x2_win:      # A/B switch (tools/)
         return False
     N, H, W, Cin = x_shape
-    if max(N * H * W * Cin, N * (H + 2 * ph - 1) * (W + 2 * pw - 1) * cout) * 2 >= 0x7FF00000:   # 32-bit buffer offsets
+    if not _fits32(N * H * W * Cin, N * (H + 2 * ph - 1) * (W + 2 * pw - 1) * cout):
         return False
     return (kh, kw, sh, sw) == (2, 2, 1, 1) and ph == pw and bool(lib().sc2_conv2x2_win_supported(H, W, Cin, cout, ph))
 
@@ -1333,7 +1357,7 @@ def conv2x2_win_tail_supported(x_shape):
     if not host_policy.conv2x2_win or not host_policy.w2_tail:      # A/B switches (tools/)
         return False
     N, H, W, Cin = x_shape
-    if N * 56 * 56 * 256 * 2 >= 0x7FF00000 or N * H * W * Cin * 2 >= 0x7FF00000:
+    if not _fits32(N * 56 * 56 * 256, N * H * W * Cin):
         return False
     return bool(lib().sc2_conv2x2_win_tail_supported(H, W, Cin))
 
@@ -1398,34 +1422,14 @@ def conv2x2_win_fwd(x_nhwc, w_frag, pad, beta=None, inverse=True, tag=None, out=
 def conv3x3_win_fwd(x_nhwc, w_frag, bias, relu=False, tag=None, stride=1, mask=None):
     """y = act(conv3x3(x, stride 1 or 2, pad 1) + bias); bf16 NHWC in / out; w_frag = pack_conv3x3_win(w).
     mask (stride 1, bf16 like y, no relu): y = mask > 0 ? conv + bias : 0 -- the gradient through a ReLU whose output is `mask`."""
-    for t, name in ((x_nhwc, 'x'), (w_frag, 'w_frag'), (bias, 'bias')):
-        _dev(t, name)
-    assert x_nhwc.dtype == torch.bfloat16 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
-    N, H, W, Cin = x_nhwc.shape
-    cout = w_frag.shape[1] * 16
-    assert w_frag.dtype == torch.bfloat16 and w_frag.is_contiguous() and tuple(w_frag.shape) == (Cin // 32 * 9, cout // 16, 64, 8)
-    assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == cout
-    stride = int(stride)
-    if stride == 2:
-        out = torch.empty((N, H // 2, W // 2, cout), dtype=torch.bfloat16, device=x_nhwc.device)
-        with _timed(tag or 'conv3x3s2_win'):
-            _check(lib().sc2_conv3x3s2_win_fwd(_ptr(x_nhwc), _ptr(w_frag), _ptr(bias), _ptr(out), N, H, W, Cin, cout,
-                                               1 if relu else 0, _stream()), 'conv3x3s2_win_fwd')
-        return out
-    assert stride == 1
-    out = torch.empty((N, H, W, cout), dtype=torch.bfloat16, device=x_nhwc.device)
-    if mask is not None:
-        _dev(mask, 'mask')
-        assert not relu and mask.dtype == torch.bfloat16 and mask.is_contiguous() and tuple(mask.shape) == tuple(out.shape)
-    with _timed(tag or 'conv3x3_win'):
-        _check(lib().sc2_conv3x3_win_fwd(_ptr(x_nhwc), _ptr(w_frag), _ptr(bias), _ptr(mask), _ptr(out), N, H, W, Cin, cout,
-                                         1 if relu else 0, _stream()), 'conv3x3_win_fwd')
-    return out
+    if int(stride) == 2:      # (an entry of its own, without a mask, for even maps: (H - 1) // 2 + 1 = H // 2)
+        return _frag_conv_fwd('conv3x3s2_win_fwd', x_nhwc, w_frag, bias, _WIN_FRAG[9], 2, relu, tag, stride_arg=False)
+    assert int(stride) == 1
+    return _frag_conv_fwd('conv3x3_win_fwd', x_nhwc, w_frag, bias, _WIN_FRAG[9], 1, relu, tag, ('mask', mask), stride_arg=False)
 
 
 def conv1x1_stream_supported(cin, cout, kh, kw, stride, pad):
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(pad)
     if not host_policy.conv_stream:      # A/B switch (tools/)
         return False
     return kh == 1 and kw == 1 and sh == sw and ph == 0 and pw == 0 and \
@@ -1438,25 +1442,7 @@ def conv1x1_stream_mask_supported(cin, cout, stride):
 
 def conv1x1_stream_fwd(x_nhwc, w_frag, bias, stride=1, residual=None, relu=False, tag=None, mask=None):
     """y = act(conv1x1(x) + bias [+ residual]) on the persistent streaming kernel; bf16 NHWC in / out."""
-    for t, name in ((x_nhwc, 'x'), (w_frag, 'w_frag'), (bias, 'bias')):
-        _dev(t, name)
-    assert x_nhwc.dtype == torch.bfloat16 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
-    N, H, W, Cin = x_nhwc.shape
-    cout = w_frag.shape[0] * 16
-    assert w_frag.dtype == torch.bfloat16 and w_frag.is_contiguous() and tuple(w_frag.shape) == (cout // 16, Cin // 32, 64, 8)
-    assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == cout
-    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
-    out = torch.empty((N, OH, OW, cout), dtype=torch.bfloat16, device=x_nhwc.device)
-    if residual is not None:
-        _dev(residual, 'residual')
-        assert residual.dtype == torch.bfloat16 and residual.is_contiguous() and tuple(residual.shape) == tuple(out.shape)
-    if mask is not None:
-        _dev(mask, 'mask')
-        assert not relu and mask.dtype == torch.bfloat16 and mask.is_contiguous() and tuple(mask.shape) == tuple(out.shape)
-    with _timed(tag or 'conv1x1_stream'):
-        _check(lib().sc2_conv1x1_stream_fwd(_ptr(x_nhwc), _ptr(w_frag), _ptr(bias), _ptr(residual), _ptr(mask), _ptr(out), N, H, W,
-                                            Cin, cout, int(stride), 1 if relu else 0, _stream()), 'conv1x1_stream_fwd')
-    return out
+    return _frag_conv_fwd('conv1x1_stream_fwd', x_nhwc, w_frag, bias, _ROWS_FRAG, int(stride), relu, tag, ('residual', residual), ('mask', mask))
 
 
 def conv1x1_pair_supported(k1, c, n2):
@@ -1485,12 +1471,11 @@ def conv1x1_pair_fwd(o_nhwc, w3_frag, b3, identity, w1_frag, b1, tag=None):
 
 def conv2x2_c48_supported(x_shape, cout, kh, kw, stride, pad):
     """True if this conv runs on the streaming kernel of the FP encoder's last layer (Cin 48, k2, s1, p0, Cout <= 32)."""
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(pad)
     if not host_policy.conv_c48:      # A/B switch (tools/)
         return False
     N, H, W, Cin = x_shape
-    if N * H * W * Cin * 2 >= 0x7FF00000:
+    if not _fits32(N * H * W * Cin):
         return False
     return (kh, kw, sh, sw, ph, pw) == (2, 2, 1, 1, 0, 0) and bool(lib().sc2_conv2x2_c48_supported(H, W, Cin, cout))
 
@@ -1532,39 +1517,19 @@ def conv2x2_c48_fwd(x_nhwc, w_frag, cout, medians=None, tag=None, out=None):
 
 def conv1x1_win_supported(cin, cout, kh, kw, stride, pad):
     """True if this 1x1 conv can run on the window-plane 1x1 kernel (Cin, Cout multiples of 128, stride 1 or 2)."""
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(pad)
     return (kh, kw, ph, pw) == (1, 1, 0, 0) and sh == sw and bool(lib().sc2_conv1x1_win_supported(cin, cout, sh))
 
 
 def conv1x1_win_fwd(x_nhwc, w_frag, bias, stride=1, residual=None, relu=False, tag=None, mask=None):
     """y = act(conv1x1(x) + bias [+ residual]) on the window-plane 1x1 kernel; bf16 NHWC in / out;
     w_frag = pack_conv_win(w.reshape(Cout, Cin, 1, 1)).  mask (bf16 like y, no relu): y = mask > 0 ? value : 0."""
-    for t, name in ((x_nhwc, 'x'), (w_frag, 'w_frag'), (bias, 'bias')):
-        _dev(t, name)
-    assert x_nhwc.dtype == torch.bfloat16 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
-    N, H, W, Cin = x_nhwc.shape
-    cout = w_frag.shape[1] * 16
-    assert w_frag.dtype == torch.bfloat16 and w_frag.is_contiguous() and tuple(w_frag.shape) == (Cin // 32, cout // 16, 64, 8)
-    assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == cout
-    stride = int(stride)
-    out = torch.empty((N, (H - 1) // stride + 1, (W - 1) // stride + 1, cout), dtype=torch.bfloat16, device=x_nhwc.device)
-    if residual is not None:
-        _dev(residual, 'residual')
-        assert residual.dtype == torch.bfloat16 and residual.is_contiguous() and tuple(residual.shape) == tuple(out.shape)
-    if mask is not None:
-        _dev(mask, 'mask')
-        assert not relu and mask.dtype == torch.bfloat16 and mask.is_contiguous() and tuple(mask.shape) == tuple(out.shape)
-    with _timed(tag or 'conv1x1_win'):
-        _check(lib().sc2_conv1x1_win_fwd(_ptr(x_nhwc), _ptr(w_frag), _ptr(bias), _ptr(residual), _ptr(mask), _ptr(out), N, H, W, Cin,
-                                         cout, stride, 1 if relu else 0, _stream()), 'conv1x1_win_fwd')
-    return out
+    return _frag_conv_fwd('conv1x1_win_fwd', x_nhwc, w_frag, bias, _WIN_FRAG[1], int(stride), relu, tag, ('residual', residual), ('mask', mask))
 
 
 def conv1x1_w8_supported(cin, cout, kh, kw, stride, pad):
     """True if this 1x1 conv can run on the eight-wave 256-channel 1x1 kernel (Cin % 128 == 0, Cout % 256 == 0, stride 1 or 2)."""
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (pad, pad) if isinstance(pad, int) else pad
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(pad)
     return (kh, kw, ph, pw) == (1, 1, 0, 0) and sh == sw and bool(lib().sc2_conv1x1_w8_supported(cin, cout, sh))
 
 
@@ -1572,28 +1537,7 @@ def conv1x1_w8_fwd(x_nhwc, w_frag, bias, stride=1, residual=None, relu=False, ta
     """y = act(conv1x1(x) + bias [+ residual]) on the eight-wave 256-channel 1x1 kernel (conv1x1_w8.hip); bf16 NHWC in / out;
     w_frag = pack_conv_win(w.reshape(Cout, Cin, 1, 1)), the stream of conv1x1_win_fwd, whose results it reproduces bit for bit.
     out: a contiguous bf16 tensor of the output's size to write into (default: a new one)."""
-    for t, name in ((x_nhwc, 'x'), (w_frag, 'w_frag'), (bias, 'bias')):
-        _dev(t, name)
-    assert x_nhwc.dtype == torch.bfloat16 and x_nhwc.dim() == 4 and x_nhwc.is_contiguous()
-    N, H, W, Cin = x_nhwc.shape
-    cout = w_frag.shape[1] * 16
-    assert w_frag.dtype == torch.bfloat16 and w_frag.is_contiguous() and tuple(w_frag.shape) == (Cin // 32, cout // 16, 64, 8)
-    assert bias.dtype == torch.float32 and bias.is_contiguous() and bias.numel() == cout
-    stride = int(stride)
-    shape = (N, (H - 1) // stride + 1, (W - 1) // stride + 1, cout)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.bfloat16, device=x_nhwc.device)
-    else:
-        _dev(out, 'out')
-        assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.numel() == N * shape[1] * shape[2] * cout
-        out = out.view(shape)
-    if residual is not None:
-        _dev(residual, 'residual')
-        assert residual.dtype == torch.bfloat16 and residual.is_contiguous() and tuple(residual.shape) == tuple(out.shape)
-    with _timed(tag or 'conv1x1_w8'):
-        _check(lib().sc2_conv1x1_w8_fwd(_ptr(x_nhwc), _ptr(w_frag), _ptr(bias), _ptr(residual), _ptr(out), N, H, W, Cin, cout, stride,
-                                        1 if relu else 0, _stream()), 'conv1x1_w8_fwd')
-    return out
+    return _frag_conv_fwd('conv1x1_w8_fwd', x_nhwc, w_frag, bias, _WIN_FRAG[1], int(stride), relu, tag, ('residual', residual), out=out)
 
 
 def pack_gamma_fragments(gamma):
@@ -1910,8 +1854,7 @@ def _precise_conv_setup(x_shape, device, cout, kh, kw, stride, padding, a_op, ep
     scatter: (rows, cols, out f32 [N,out_H,out_W,cout], stride_h, stride_w, off_h, off_w) as for conv2d_fwd -- the launch computes
     rows x cols pixels per image and writes pixel (r, c) to (r*stride_h + off_h, c*stride_w + off_w) of `out`, which it returns."""
     N, H, W, Cin = x_shape
-    sh, sw = (stride, stride) if isinstance(stride, int) else stride
-    ph, pw = (padding, padding) if isinstance(padding, int) else padding
+    (sh, sw), (ph, pw) = _pair2(stride), _pair2(padding)
     OH, OW = (H + 2 * ph - kh) // sh + 1, (W + 2 * pw - kw) // sw + 1
     sc = (0, 0, 0, 0, 0, 0)
     if scatter is not None:
