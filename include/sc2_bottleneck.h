@@ -568,6 +568,10 @@ int sc2_eb_bits_partial_len(int N, int C, int HW);
 int sc2_eb_backward(const float *y, const float *noise, const float *params, int N, int C, int HW, int mode,
                     float lik_bound, const float *g_yhat, const float *g_lik, float *g_y, float *g_params_partial,
                     int n_partial, void *stream);
+/* planes (images) of one channel that a workgroup of sc2_eb_backward walks for this problem size: the largest of 8, 4, 2, 1
+ * that divides N and leaves (N / it) * C >= 512 workgroups.  The workgroup's sums go to the first partial row of its first plane,
+ * zeros to the other rows of its planes (rows per plane = sc2_eb_bits_partial_len(N, C, HW) / (N * C)). */
+int sc2_eb_backward_planes_per_wg(int N, int C, int HW);
 
 /* symbols = int32(round_half_even(y - median[c])) in NCHW order, one row of C*HW per image.
  * Replaces EntropyModel.quantize(x, "symbols", means) reached from layer.py:506. */

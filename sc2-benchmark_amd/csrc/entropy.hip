@@ -299,6 +299,13 @@ extern "C" int sc2_eb_bits_partial_len(int N, int C, int HW) {
     return N * C * plane_grid_x(HW, EB_TILE);
 }
 
+extern "C" int sc2_eb_backward_planes_per_wg(int N, int C, int HW) {
+    if (N <= 0 || C <= 0 || HW <= 0) return 0;
+    int ppw = 8;                             // planes (images) per workgroup: a divisor of N that leaves >= 512 workgroups
+    while (ppw > 1 && (N % ppw != 0 || (long long)(N / ppw) * C < 512)) ppw >>= 1;
+    return ppw;
+}
+
 extern "C" int sc2_eb_forward(const float *y, const float *noise, const float *params, int N, int C, int HW, int mode,
                               float lik_bound, float *y_hat, void *y_hat_bf16_nhwc, float *lik, float *bits_partial,
                               int bits_partial_len, void *stream) {
@@ -328,8 +335,7 @@ extern "C" int sc2_eb_backward(const float *y, const float *noise, const float *
     if (mode == SC2_EB_NOISE) SC2_REQUIRE(noise, SC2_ERR_INVALID_ARG, "eb_backward: noise mode needs the noise tensor");
     SC2_REQUIRE(n_partial == sc2_eb_bits_partial_len(N, C, HW), SC2_ERR_INVALID_ARG,
                 "eb_backward: n_partial %d != %d", n_partial, sc2_eb_bits_partial_len(N, C, HW));
-    int ppw = 8;                             // planes (images) per workgroup: a divisor of N that leaves >= 512 workgroups
-    while (ppw > 1 && (N % ppw != 0 || (long long)(N / ppw) * C < 512)) ppw >>= 1;
+    const int ppw = sc2_eb_backward_planes_per_wg(N, C, HW);
     dim3 grid((N / ppw) * C, 1);
     hipLaunchKernelGGL(eb_backward_kernel, grid, dim3(EB_THREADS), 0, static_cast<hipStream_t>(stream), y, noise,
                        params, C, HW, mode, lik_bound, g_yhat, g_lik, g_y, g_params_partial, ppw, plane_grid_x(HW, EB_TILE));

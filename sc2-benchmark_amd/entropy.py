@@ -705,8 +705,9 @@ class EntropyBottleneck(_HostTablesMixin, nn.Module):
             raise hip.Sc2Error('the HIP entropy-bottleneck kernels are built for filters=(3,3,3,3) '
                                '(the only configuration sc2bench uses); got {}'.format(self.filters))
 
-    def effective_params(self):
-        """f32 [C, 64] block the kernels read (layout: include/sc2_bottleneck.h); differentiable."""
+    def effective_params(self, dtype=torch.float32):
+        """f32 [C, 64] block the kernels read (layout: include/sc2_bottleneck.h); differentiable.  ``dtype``: torch.float64 on a
+        module cast with .double() gives the same block without the rounding to f32 (the tests' float64 reference)."""
         self._check_filters()
         C = self.channels
         parts = []
@@ -717,7 +718,7 @@ class EntropyBottleneck(_HostTablesMixin, nn.Module):
                 parts.append(torch.tanh(self.factors[i]).reshape(C, -1))
         parts.append(self._get_medians().reshape(C, 1))
         p = torch.cat(parts, dim=1)
-        return F.pad(p, (0, hip.EB_PARAM_STRIDE - p.shape[1])).float().contiguous()
+        return F.pad(p, (0, hip.EB_PARAM_STRIDE - p.shape[1])).to(dtype).contiguous()
 
     def _cached_params(self):
         ps = list(self.matrices) + list(self.biases) + list(self.factors) + [self.quantiles]

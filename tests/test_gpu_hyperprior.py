@@ -211,6 +211,63 @@ def test_gaussian_conditional_backward_kernel(S, R, dev):
         assert bool(closed.any()) and bool((sd.grad.cpu()[closed] == 0).all())      # ... is shut on the device too
 
 
+def test_gaussian_conditional_kernels_past_the_grid_cap(S, R, dev):
+    """gaussian.hip launches at most 8192 blocks of 256 threads: above 2 097 152 elements every thread takes a second trip of its
+    grid-stride loop.  gc_forward (both modes), gc_backward and gc_symbols_indexes at 3 x 192 x 64 x 64 = 2 359 296 elements, `scales`
+    and `means` the two chunk(2, 1) halves of one tensor (each with its own image stride), against the oracle module with the
+    tolerances of the tests above; symbols and indexes bit for bit."""
+    hip = S.hip
+    shape = (3, 192, 64, 64)
+    assert shape[0] * shape[1] * shape[2] * shape[3] > 8192 * 256
+    g = torch.Generator().manual_seed(9)
+    y = torch.randn(shape, generator=g) * 3
+    params = torch.randn(shape[0], 2 * shape[1], shape[2], shape[3], generator=g)
+    params[:, :shape[1]] = params[:, :shape[1]].abs() * 1.5 - 0.2                    # scales: some below the 0.11 bound
+    noise = torch.rand(shape, generator=g) - 0.5
+    w1, w2 = torch.randn(shape, generator=g), torch.randn(shape, generator=g)
+    pr = params.clone().requires_grad_(True)
+    yr = y.clone().requires_grad_(True)
+    ref = R.GaussianConditional(None)
+    ref.update_scale_table(R.get_scale_table())
+    scales_r, means_r = pr.chunk(2, 1)
+    y_hat, lik = ref(yr, scales_r, means=means_r, training=True, noise=noise)
+    ((y_hat * w1).sum() + (lik * w2).sum()).backward()
+    with torch.no_grad():
+        y_hat_q, lik_q = ref(y, scales_r, means=means_r, training=False)
+        sym_ref = ref.quantize(y, 'symbols', means_r.detach())
+        idx_ref = ref.build_indexes(scales_r.detach())
+    yd, pd, nd = y.to(dev), params.to(dev), noise.to(dev)
+    sd, md = pd.chunk(2, 1)
+    assert not sd.is_contiguous() and not md.is_contiguous() and sd.stride(0) == 2 * sd[0].numel()
+    got_y_hat, got_lik = hip.gc_forward(yd, sd, md, nd, mode=hip.EB_NOISE)
+    assert torch.equal(got_y_hat.cpu(), y_hat.detach())
+    torch.testing.assert_close(got_lik.cpu(), lik.detach(), rtol=2e-5, atol=1e-9)
+    got_y_hat, got_lik = hip.gc_forward(yd, sd, md, None, mode=hip.EB_DEQUANTIZE)
+    assert torch.equal(got_y_hat.cpu(), y_hat_q)
+    torch.testing.assert_close(got_lik.cpu(), lik_q, rtol=2e-5, atol=1e-9)
+    g_y, g_s, g_m = hip.gc_backward(yd, sd, md, nd, w1.to(dev), w2.to(dev))
+    g_scales, g_means = pr.grad.chunk(2, 1)
+    for got, want, nm in ((g_y, yr.grad, 'y'), (g_s, g_scales, 'scales'), (g_m, g_means, 'means')):
+        err = (got.cpu() - want).abs()
+        tol = 2e-3 * want.abs() + 1e-4 * want.abs().max()
+        assert bool((err <= tol).all()), '{}: max err {} (max |g| {})'.format(nm, err.max().item(), want.abs().max().item())
+    # LowerBound gate of the scales: shut in the oracle -> shut on the device, wherever f32 can tell which way the gradient points.
+    # (Among 385 738 scales under the bound, f32 and f64 autograd of the oracle disagree on the sign of 73 075 un-gated gradients, all
+    #  below 1e-43: exp(-l^2 / 2) underflows.  The gate is checked where the un-gated gradient reaches the absolute term of the
+    #  tolerance above, 1e-4 of the largest gradient; below it that comparison accepts any value of that size.)
+    clamped = scales_r.detach().clamp_min(0.11).clone().requires_grad_(True)
+    (ref(y, clamped, means=means_r.detach(), training=True, noise=noise)[1] * w2).sum().backward()
+    decidable = clamped.grad.abs() >= 1e-4 * g_scales.abs().max()
+    closed = (scales_r.detach() < 0.11) & (g_scales == 0) & decidable
+    assert int(closed.sum()) > 10000 and bool((g_s.cpu()[closed] == 0).all())
+    table = R.get_scale_table().to(dev).contiguous()
+    sym, idx = hip.gc_symbols_indexes(yd, sd, md, table)
+    assert sym.dtype == torch.int32 and torch.equal(sym.cpu(), sym_ref)
+    assert idx.dtype == torch.int32 and torch.equal(idx.cpu(), idx_ref)
+    # the second trip is really there: the last elements differ from an all-zero / unwritten buffer
+    assert bool((got_lik.reshape(-1)[8192 * 256:] > 0).all()) and int(idx.reshape(-1)[8192 * 256:].max()) > 0
+
+
 @pytest.mark.parametrize('kind,act', [('convT', 'leaky'), ('convT', None), ('conv', 'relu'), ('conv', 'leaky')])
 def test_hyper_transform_backward(S, dev, kind, act):
     """Data and weight gradients of the h_a / h_s layers (conv k5 s2 p1 and ConvTranspose2d k5 s2 p1, with the fused

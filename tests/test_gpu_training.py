@@ -1,8 +1,14 @@
 """-m gpu: training path (HIP forward AND backward kernels under autograd: conv data / weight gradients on the
-implicit-GEMM and wgrad kernels, GDN1 and entropy-bottleneck backward kernels) against the f32 CPU oracle's autograd.
+implicit-GEMM and wgrad kernels, the GDN1 backward kernels, with the entropy bottleneck's backward kernel in the same
+graph) against the f32 CPU oracle's autograd.
 
 Tolerance: activations, weights and gradients pass through bf16 operands with f32 accumulation on the device, so
-parameter gradients are compared by relative L2 error per tensor (<= 6e-2) and the loss by 2e-2 relative."""
+parameter gradients are compared by relative L2 error per tensor (<= 6e-2) and the loss by 2e-2 relative.
+
+This is NOT a test of the entropy-bottleneck backward kernel: it is f32 end to end, a wrong slot among its 59 sums or a
+dropped factor passes at 6e-2, and every shape here (N * C < 1024, latents of at most 1024 pixels) launches it with one
+plane per workgroup and one partial row per plane.  The kernel-level check -- float64 reference, f32-grade bound, every
+launch shape -- is tests/test_gpu_eb_backward.py."""
 import os
 import sys
 
