@@ -859,6 +859,33 @@ int sc2_roi_align(sc2_roi_levels lv, int n_levels, int N, int C, int is_bf16, co
                   int sampling_ratio, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Segmentation tail (csrc/seg.hip): low-resolution class logits -> labels of the resized map and confusion counts, */
+/* one launch.  tests/ref_seg.py restates it in float64.                                                            */
+/* ------------------------------------------------------------------------------------------ */
+#define SC2_SEG_MAX_CLASSES 64    /* a workgroup's [C,C] int32 histogram: 16 KB of LDS at most */
+/* What `interpolate(logits, (H, W), mode='bilinear', align_corners=False).argmax(1)` followed by the confusion-matrix update of
+ * the reference's SegEvaluator computes, without forming the resized logits, in f32 on the unrounded input.
+ * logits : [N,C,h,w], f32 or bf16 (is_bf16), addressed by four ELEMENT strides (>= 0): NCHW memory, a slice of it, or the permuted
+ *          view of an NHWC map whose channel pitch is padded.  Only classes 0..C-1 decide a label.  c_readable: how many
+ *          consecutive elements behind class 0 of EVERY pixel lie inside the caller's allocation (>= C; their values beyond C are
+ *          never used).  With stride_c == 1, c_readable >= C rounded up to 8 (bf16) / 4 (f32), a 16-byte aligned base and the other
+ *          strides multiples of 8 / 4, classes are read with 16-byte loads; any other layout takes the strided path.
+ * H, W   : the output size; any size, H < h included.  All four sides at most 32768; C in 1..SC2_SEG_MAX_CLASSES
+ *          (SC2_ERR_UNSUPPORTED otherwise: the caller keeps its torch-op path).
+ * Per axis, for output index d, in integers: t = (2d+1)*in - out;  t <= 0: i0 = 0, lambda = 0;  otherwise i0 = t / (2 out),
+ * lambda = float(t % (2 out)) / float(2 out);  i1 = min(i0 + 1, in - 1).  Per class, every operation rounded once (no fused
+ * multiply-add):  (1-ly)*((1-lx)*x[y0,x0] + lx*x[y0,x1]) + ly*((1-lx)*x[y1,x0] + lx*x[y1,x1]).
+ * label  = the first class holding the maximum; a NaN counts as larger than any number and the first NaN wins (torch.argmax).
+ * labels : int64 [N,H,W] contiguous, or NULL (no store is issued).
+ * targets: int64 [N,H,W] contiguous, mat: int64 [C,C]; given together, every pixel with 0 <= target < C ADDS 1 to
+ *          mat[target][label] (any other target value -- 255, negatives, >= C -- is skipped).  mat is not cleared: it carries over
+ *          from call to call.  Integer sums: the matrix does not depend on the order of arrival.  Either NULL: nothing is counted.
+ * At least one of labels and the (targets, mat) pair must be given.  One launch on `stream`. */
+int sc2_seg_predict(const void *logits, int is_bf16, int N, int C, int h, int w, long long stride_n, long long stride_c,
+                    long long stride_h, long long stride_w, int c_readable, int H, int W, const long long *targets, long long *labels,
+                    long long *mat, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Diagnostics (csrc/diag.hip; no product path calls these).                                    */
 /* ------------------------------------------------------------------------------------------ */
 /* The shader clock the chip holds while OTHER kernels run: `n_workgroups` probe waves (one per workgroup; launch >= 8 so that

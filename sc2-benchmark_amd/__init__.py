@@ -22,12 +22,13 @@ from .compression import (COMPRESSION_MODEL_CLASS_DICT, COMPRESSION_MODEL_FUNC_D
                           bmshj2018_factorized, bmshj2018_hyperprior, get_compression_model, mbt2018, mbt2018_mean)
 from .entropy import GDN  # noqa: F401
 from .transforms import (AdaptivePad, PILImageModule, PILTensorModule, QuantizedTensor, SimpleDequantizer,  # noqa: F401
-                         SimpleQuantizer, dequantize_tensor, quantize_tensor)
+                         SimpleQuantizer, cat_list, dequantize_tensor, pascal_seg_collate_fn, pascal_seg_eval_collate_fn,
+                         quantize_tensor)
 from .wrapper import (WRAPPER_CLASS_DICT, CodecFeatureCompressionClassifier, CodecInputCompressionClassifier,  # noqa: F401
                       EntropicClassifier, NeuralInputCompressionClassifier, SplitClassifier, wrap_model)
 
 from .dense import (DETECTION_MODEL_FUNC_DICT, SEGMENTATION_MODEL_FUNC_DICT, BaseRCNN, BaseSegmentationModel,  # noqa: F401
-                    SegEvaluator, UpdatableBackboneWithFPN, backbone_with_fpn, deeplabv3_model, faster_rcnn_model)
+                    SegEvaluator, UpdatableBackboneWithFPN, backbone_with_fpn, deeplabv3_model, faster_rcnn_model, seg_labels)
 
 from .pipeline import StagePipeline, supports_stages  # noqa: F401
 from . import graphs  # noqa: F401

@@ -469,12 +469,15 @@ class BaseSegmentationModel(_UpdatableDenseModel):
     def _body(self):
         return self.backbone
 
-    def _head(self, head, feat, size):
+    def _logits(self, head, feat):
+        """the head's low-resolution logits [N,classes,h,w]: a permuted view of NHWC memory from the library's kernels, NCHW from torch's"""
         w = next(head.parameters())
         feat = feat.to(w.dtype)
         hd = _hip_dense_head(self, head, feat)
-        logits = hd(feat) if hd is not None else head(feat)
-        return F.interpolate(logits, size=size, mode='bilinear', align_corners=False)
+        return hd(feat) if hd is not None else head(feat)
+
+    def _head(self, head, feat, size):
+        return F.interpolate(self._logits(head, feat), size=size, mode='bilinear', align_corners=False)
 
     def _finish(self, features, input_shape):
         result = OrderedDict()
@@ -485,6 +488,14 @@ class BaseSegmentationModel(_UpdatableDenseModel):
 
     def forward(self, x):
         return self._finish(self.backbone(x), x.shape[-2:])
+
+    def predict(self, x, targets=None, mat=None):
+        """The evaluation tail of the reference (`model(x)['out'].argmax(1)` into `SegEvaluator.update`) without the resized
+        logits: backbone -> classifier -> `seg_labels` on the low-resolution map.  -> int64 labels [N,H,W] of the input's size;
+        with `targets` (int64 [N,H,W]) and `mat` (int64 [classes,classes]) the confusion counts are ADDED to `mat`.  The aux head
+        does not run.  `forward` is what it was: it still returns the resized logits."""
+        features = self.backbone(x)
+        return seg_labels(self._logits(self.classifier, features['out']), x.shape[-2:], targets, mat)
 
 
 def create_deeplabv3(backbone, num_input_channels=2048, uses_aux=False, num_aux_channels=1024, num_classes=21):
@@ -520,6 +531,33 @@ def deeplabv3_model(backbone_config, pretrained=True, pretrained_backbone_name=N
 
 
 # ------------------------------------------------------------------------------------------------ evaluation state
+def _count_pairs(mat, target, prediction):
+    """SegEvaluator.update's arithmetic on flat tensors: mat[t, p] += 1 where 0 <= t < classes."""
+    n = mat.shape[0]
+    keep = (target >= 0) & (target < n)
+    inds = n * target[keep].to(torch.int64) + prediction[keep]
+    mat += torch.bincount(inds, minlength=n ** 2).reshape(n, n)
+
+
+def seg_labels(logits, size, targets=None, mat=None, want_labels=True):
+    """Labels of low-resolution logits [N,C,h,w] at `size` = (H, W), and (with `targets` int64 [N,H,W] and `mat` int64 [C,C]) their
+    confusion counts added to `mat`.  Device tensors of up to 64 classes go to ONE launch of `sc2_seg_predict`: bilinear
+    weights from integers, f32 arithmetic on the unrounded logits, no resized tensor.  CPU tensors, more classes and
+    `host_policy.seg_predict_hip = False` take the torch-op restatement: interpolate in f32, argmax, bincount.
+    -> int64 labels [N,H,W] (None with want_labels=False on the kernel path: nothing is stored)."""
+    from . import hip
+    size = (int(size[0]), int(size[1]))
+    if (logits.is_cuda and hip.host_policy.seg_predict_hip and logits.shape[1] <= hip.SEG_MAX_CLASSES and
+            logits.dtype in (torch.float32, torch.bfloat16)):
+        if targets is not None and mat is not None:
+            return hip.seg_predict(logits, size, targets.to(torch.int64).contiguous(), mat, want_labels=want_labels)
+        return hip.seg_predict(logits, size)
+    labels = F.interpolate(logits.float(), size=size, mode='bilinear', align_corners=False).argmax(1)
+    if targets is not None and mat is not None:
+        _count_pairs(mat, targets.flatten(), labels.flatten())
+    return labels
+
+
 class SegEvaluator(object):
     """Confusion matrix of a segmentation run and its cross-rank reduction (script/task/utils/eval.py:4-46: one int64
     [classes, classes] all-reduce -- the C4 collective of SURVEY.md 2.3)."""
@@ -536,6 +574,17 @@ class SegEvaluator(object):
             keep = (target >= 0) & (target < n)
             inds = n * target[keep].to(torch.int64) + prediction[keep]
             self.mat += torch.bincount(inds, minlength=n ** 2).reshape(n, n)
+
+    def update_logits(self, targets, logits):
+        """`update(targets.flatten(), interpolate(logits, targets' size).argmax(1).flatten())` from the LOW-resolution logits
+        [N,classes,h,w]: on a HIP device one launch that adds into the matrix (`seg_labels`), no resized tensor, no labels."""
+        n = self.num_classes
+        if logits.shape[1] != n:
+            raise ValueError('update_logits: {} logit planes for {} classes'.format(logits.shape[1], n))
+        if self.mat is None:
+            self.mat = torch.zeros((n, n), dtype=torch.int64, device=targets.device)
+        with torch.no_grad():
+            seg_labels(logits, targets.shape[-2:], targets, self.mat, want_labels=False)
 
     def reset(self):
         if self.mat is not None:
@@ -554,3 +603,8 @@ class SegEvaluator(object):
             return
         dist.barrier()
         dist.all_reduce(self.mat)
+
+    def __str__(self):
+        acc_global, acc, iu = self.compute()
+        return 'mean IoU: {:.1f}, IoU: {}, Global pixelwise acc: {:.1f}, Average row correct: {}'.format(
+            iu.mean().item(), ['{:.1f}'.format(i) for i in iu.tolist()], acc_global.item(), ['{:.1f}'.format(i) for i in acc.tolist()])

@@ -154,9 +154,64 @@ def evaluate(model, data_loader, device, max_samples=None, log_freq=1000, title=
             'pipeline': 'stage pipeline (sc2bench_amd/pipeline.py)' if pipelined else 'none: module forward per batch'}
 
 
+def evaluate_segmentation(model, data_loader, device, num_classes, max_samples=None, log_freq=1000, title=None):
+    """The evaluation loop of the semantic-segmentation task (script/task/semantic_segmentation.py:95-134): eval mode, analysis
+    on, every batch's labels counted into a `SegEvaluator`, the matrix summed over ranks, the analyzers summarised.
+    A model with `predict` (dense.BaseSegmentationModel) labels and counts from its LOW-resolution logits -- on a HIP device
+    one `sc2_seg_predict` launch per batch, no resized logits; any other model runs `model(images)['out'].argmax(1)` into
+    `SegEvaluator.update` as the reference does.
+    -> {'miou', 'acc_global', 'iou', 'acc', 'samples', 'seconds', 'analysis', 'evaluator'}."""
+    from .dense import SegEvaluator
+    # moved BEFORE inference mode is entered: tensors created under it (a model built on the host and copied here) do not track the
+    # version counter that the coder's table caches key on
+    model = model.to(device) if device.type == 'cuda' else model
+    with torch.inference_mode():
+        return _evaluate_segmentation(model, data_loader, device, num_classes, SegEvaluator(num_classes), max_samples, log_freq, title)
+
+
+def _evaluate_segmentation(model, data_loader, device, num_classes, evaluator, max_samples, log_freq, title):
+    if hasattr(model, 'use_cpu4compression') and device.type != 'cuda':
+        model.use_cpu4compression()
+    if title is not None:
+        logger.info(title)
+    model.eval()
+    analyzable = isinstance(model, AnalyzableModule)
+    if analyzable:
+        model.activate_analysis()
+    fused = callable(getattr(model, 'predict', None))
+    t0 = time.perf_counter()
+    seen = 0
+    for i, batch in enumerate(data_loader):
+        images, targets = batch[0], batch[1]
+        if isinstance(images, torch.Tensor):
+            images = images.to(device, non_blocking=True)
+        if isinstance(targets, torch.Tensor):
+            targets = targets.to(device, non_blocking=True)
+        if fused:
+            if evaluator.mat is None:
+                evaluator.mat = torch.zeros((num_classes, num_classes), dtype=torch.int64, device=targets.device)
+            model.predict(images, targets, evaluator.mat)
+        else:
+            evaluator.update(targets.flatten(), model(images)['out'].argmax(1).flatten())
+        seen += len(images)
+        if log_freq and (i + 1) % log_freq == 0:
+            logger.info('Test: [{}] {} samples'.format(i + 1, seen))
+        if max_samples is not None and seen >= max_samples:
+            break
+    evaluator.reduce_from_all_processes()
+    logger.info(str(evaluator))
+    acc_global, acc, iou = evaluator.compute()
+    analysis = []
+    if analyzable and model.activated_analysis:
+        model.summarize()
+        analysis = [a.summary() for a in model.analyzers if hasattr(a, 'summary') and getattr(a, 'file_size_list', None)]
+    return {'miou': iou.mean().item(), 'acc_global': acc_global.item(), 'iou': iou.tolist(), 'acc': acc.tolist(), 'samples': seen,
+            'seconds': time.perf_counter() - t0, 'analysis': analysis, 'evaluator': evaluator}
+
+
 def build_data_loader(dataset_dict, loader_config):
     """`test.test_data_loader` block -> DataLoader (dataset by id, sampler class, kwargs, `collate_fn` by name)."""
-    from .transforms import default_collate_w_pil
+    from .transforms import COLLATE_FUNC_DICT
     dataset = dataset_dict[loader_config['dataset_id']]
     kwargs = dict(loader_config.get('kwargs') or {})
     sampler_cfg = loader_config.get('sampler') or {}
@@ -164,9 +219,17 @@ def build_data_loader(dataset_dict, loader_config):
     sampler = None
     if sampler_cls is not None and not isinstance(sampler_cls, C.Placeholder):
         sampler = sampler_cls(dataset, **(sampler_cfg.get('kwargs') or {}))
-    collate = {'default_collate_w_pil': default_collate_w_pil}.get(loader_config.get('collate_fn'))
+    collate = COLLATE_FUNC_DICT.get(loader_config.get('collate_fn'))      # default_collate_w_pil, pascal_seg_collate_fn, pascal_seg_eval_collate_fn
     kwargs.setdefault('batch_size', 1)
     return torch.utils.data.DataLoader(dataset, sampler=sampler, collate_fn=collate, **kwargs)
+
+
+def _classifier_classes(model):
+    """output channels of a segmentation model's classifier: its last convolution"""
+    convs = [m for m in model.classifier.modules() if isinstance(m, torch.nn.Conv2d)]
+    if not convs:
+        raise ValueError('cannot tell the number of classes of {}: set test.num_classes'.format(type(model.classifier).__name__))
+    return convs[-1].out_channels
 
 
 def test_only(config, device, max_samples=None, num_workers=None):
@@ -186,6 +249,15 @@ def test_only(config, device, max_samples=None, num_workers=None):
     if num_workers is not None:
         loader_config['kwargs'] = dict(loader_config.get('kwargs') or {}, num_workers=num_workers)
     loader = build_data_loader(config['datasets'], loader_config)
+    from .dense import BaseSegmentationModel
+    if isinstance(model, BaseSegmentationModel):
+        # the reference's segmentation main() updates an updatable model before its test-only evaluation (semantic_segmentation.py:239)
+        body = model._body()
+        if not model.bottleneck_updated and hasattr(body, 'check_if_updatable') and body.check_if_updatable():
+            model.update()
+        num_classes = ((model_config.get('kwargs') or {}).get('num_classes') or config['test'].get('num_classes') or
+                       _classifier_classes(model))
+        return evaluate_segmentation(model, loader, device, num_classes, max_samples=max_samples, title='[Student/model]')
     return evaluate(model, loader, device, max_samples=max_samples, title='[Student/model]')
 
 
@@ -202,7 +274,7 @@ def main(argv=None):
     if args.json:
         C.overwrite_config(config, json.loads(args.json))
     result = test_only(config, torch.device(args.device), args.max_samples, args.num_workers)
-    print(json.dumps(result))
+    print(json.dumps({k: v for k, v in result.items() if k != 'evaluator'}))      # (the SegEvaluator object of a segmentation run stays in the returned dict)
     return result
 
 

@@ -38,7 +38,7 @@ ABI_SYMBOLS = [
     'sc2_mse_partial_len', 'sc2_mse_sum_bf16', 'sc2_mse_grad_bf16', 'sc2_relu_bwd_bf16', 'sc2_relu_bwd_mse_bf16',
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
-    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align',
+    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_seg_predict',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
 ]
 
@@ -63,6 +63,7 @@ class ArScanArgs(ctypes.Structure):
 
 NMS_MAX_BOXES = 16384      # SC2_NMS_MAX_BOXES
 ROI_MAX_LEVELS = 5         # SC2_ROI_MAX_LEVELS
+SEG_MAX_CLASSES = 64       # SC2_SEG_MAX_CLASSES
 
 
 class RoiLevel(ctypes.Structure):
@@ -136,6 +137,7 @@ class HostPolicy(object):
     eval_graph_max_batch = 1   # ... for batches up to this size (the reference evaluates at batch size 1)
     nms_hip = True             # detection.nms / batched_nms of device tensors on sc2_nms (False: the torch-op restatement, A/B)
     roi_align_hip = True       # detection.roi_align / multiscale_roi_align of device tensors on sc2_roi_align (False: torch ops, A/B)
+    seg_predict_hip = True     # dense.seg_labels (BaseSegmentationModel.predict, SegEvaluator.update_logits) of device tensors on sc2_seg_predict (False: interpolate + argmax + bincount, A/B)
 
 
 host_policy = HostPolicy()
@@ -307,6 +309,7 @@ def lib():
     L.sc2_nms_ws_bytes.restype = i64
     L.sc2_nms.argtypes = [vp, vp, i32, f32, vp, vp, vp, vp]
     L.sc2_roi_align.argtypes = [RoiLevels, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]
+    L.sc2_seg_predict.argtypes = [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, i32, vp, vp, vp, vp]
     L.sc2_rans_host_tables_create.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp)]
     L.sc2_rans_host_tables_destroy.argtypes = [vp]
     L.sc2_rans_host_tables_destroy.restype = None
@@ -1180,6 +1183,43 @@ def roi_align(feats_nhwc, scales, rois, levels, output_size, sampling_ratio, out
         _check(lib().sc2_roi_align(lv, len(feats_nhwc), N, C, 1 if f0.dtype == torch.bfloat16 else 0, _ptr(rois), _ptr(levels), K, P,
                                    int(sampling_ratio), _ptr(out), _stream()), 'roi_align')
     return out
+
+
+# --------------------------------------------------------------------------------------------- #
+# segmentation tail: labels of the resized logits and confusion counts in one launch (csrc/seg.hip)
+# --------------------------------------------------------------------------------------------- #
+def seg_predict(logits, size, targets=None, mat=None, want_labels=True, tag=None):
+    """`F.interpolate(logits, size, mode='bilinear', align_corners=False).argmax(1)` and the confusion-matrix update of
+    `SegEvaluator`, in f32 on the unrounded logits, without the resized tensor (include/sc2_bottleneck.h: sc2_seg_predict).
+    logits: [N,C,h,w] f32 or bf16 with any non-negative strides (NCHW, a slice, the permuted view of a padded NHWC map), C <= 64
+    (more raises Sc2Error); size: (H, W); targets: int64 [N,H,W]; mat: int64 [C,C] contiguous, ADDED to where 0 <= target < C.
+    -> int64 labels [N,H,W], or None with want_labels=False (then targets and mat are required)."""
+    _dev(logits, 'logits')
+    assert logits.dim() == 4 and logits.dtype in (torch.float32, torch.bfloat16)
+    N, C, h, w = (int(v) for v in logits.shape)
+    H, W = int(size[0]), int(size[1])
+    if (targets is None) != (mat is None):
+        raise ValueError('seg_predict: targets and mat are given together or not at all')
+    if targets is None and not want_labels:
+        raise ValueError('seg_predict: nothing to compute (no labels wanted, no targets and mat)')
+    if targets is not None:
+        _dev(targets, 'targets')
+        _dev(mat, 'mat')
+        assert targets.dtype == torch.int64 and targets.shape == (N, H, W) and targets.is_contiguous() and targets.device == logits.device
+        assert mat.dtype == torch.int64 and mat.shape == (C, C) and mat.is_contiguous() and mat.device == logits.device
+    labels = torch.empty((N, H, W), dtype=torch.int64, device=logits.device) if want_labels else None
+    sn, sc, sh, sw = (int(v) for v in logits.stride())
+    # elements readable behind every pixel's class 0: the kernel's 16-byte class loads run up to C rounded up to 8 (bf16) / 4 (f32)
+    readable = C
+    if sc == 1:
+        vec = 8 if logits.dtype == torch.bfloat16 else 4
+        last = logits.storage_offset() + (N - 1) * sn + (h - 1) * sh + (w - 1) * sw
+        if last + (C + vec - 1) // vec * vec <= logits.untyped_storage().nbytes() // logits.element_size():
+            readable = (C + vec - 1) // vec * vec
+    with _timed(tag or 'seg_predict'):
+        _check(lib().sc2_seg_predict(_ptr(logits), 1 if logits.dtype == torch.bfloat16 else 0, N, C, h, w, sn, sc, sh, sw, readable, H, W,
+                                     _ptr(targets), _ptr(labels), _ptr(mat), _stream()), 'seg_predict')
+    return labels
 
 
 def bn_train_fwd(x_nhwc, gamma, beta, running_mean, running_var, momentum, eps, relu, residual=None, tag=None):

@@ -365,6 +365,46 @@ def default_collate_w_pil(batch):
     return default_collate(batch)
 
 
+# ------------------------------------------------------------------------------------- sc2bench.transforms.collator
+def cat_list(images, fill_value=0):
+    """Tensors of different sizes -> one batch tensor of the largest size along every dimension, each sample in its top-left
+    corner, the rest `fill_value` (dtype and device of the first sample).  A single sample that is not a tensor (a PIL image
+    at batch size 1) is handed back as it came."""
+    if len(images) == 1 and not isinstance(images[0], torch.Tensor):
+        return images
+    shape = tuple(max(dims) for dims in zip(*(img.shape for img in images)))
+    batch = images[0].new_full((len(images),) + shape, fill_value)
+    for i, img in enumerate(images):
+        batch[i][..., :img.shape[-2], :img.shape[-1]].copy_(img)
+    return batch
+
+
+COLLATE_FUNC_DICT = dict()
+
+
+def register_collate_func(func):
+    COLLATE_FUNC_DICT[func.__name__] = func
+    return func
+
+
+register_collate_func(default_collate_w_pil)
+
+
+@register_collate_func
+def pascal_seg_collate_fn(batch):
+    """(image, target, supplementary dict) triplets of PASCAL VOC 2012 -> (images padded with 0, targets padded with the ignore
+    label 255, the dicts as a tuple)."""
+    images, targets, supp_dicts = zip(*batch)
+    return cat_list(images, fill_value=0), cat_list(targets, fill_value=255), supp_dicts
+
+
+@register_collate_func
+def pascal_seg_eval_collate_fn(batch):
+    """(image, target) pairs -> (images padded with 0, targets padded with 255)."""
+    images, targets = zip(*batch)
+    return cat_list(images, fill_value=0), cat_list(targets, fill_value=255)
+
+
 # --------------------------------------------------------------------------------------------------------- sc2bench.codec
 def _pil_codec_round_trip(pil_img, save_kwargs, open_kwargs):
     """image -> codec bytes in memory -> reopened image: (image, byte count of the coded file)."""
