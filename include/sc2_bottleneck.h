@@ -886,6 +886,68 @@ int sc2_seg_predict(const void *logits, int is_bf16, int N, int C, int h, int w,
                     long long *mat, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* COCO box AP (csrc/coco.hip): COCOeval's `bbox` protocol with its default parameters, written from the published     */
+/* protocol.  tests/ref_coco.py restates it as a sequential float64 loop; both kernels reproduce that bit for bit.    */
+/* ------------------------------------------------------------------------------------------ */
+#define SC2_COCO_THRS 10          /* iouThrs = linspace(.5, .95, 10) */
+#define SC2_COCO_RECS 101         /* recThrs = linspace(0, 1, 101) */
+#define SC2_COCO_AREAS 4          /* [0,1e10], [0,32^2], [32^2,96^2], [96^2,1e10] */
+#define SC2_COCO_MAXDETS 3        /* maxDets = (1, 10, 100) */
+#define SC2_COCO_TILE_DETS 100    /* the on-chip IoU tile of one (image, category) segment: 100 x 64 f64 = 50 KB of LDS */
+#define SC2_COCO_TILE_GTS 64
+#define SC2_COCO_SCAN_CHUNK 1024  /* detections per step of the accumulate kernel's scan (256 lanes x 4) */
+/* The definition (useCats = 1; categories are the ground truth's in ascending id order, detections of any other label are dropped;
+ * images are those the evaluator was given, in ascending id order, one with no prediction included):
+ * Boxes: a detection (x1,y1,x2,y2) in f32 becomes (x1, y1, f32(x2-x1), f32(y2-y1)), then f64; ground truth is xywh in f64.  Detection
+ *   area = w*h in f64; ground-truth area = the annotation's `area` field.
+ * IoU, in f64, every operation rounded once: w = min(dx+dw, gx+gw) - max(dx, gx), h likewise; w <= 0 or h <= 0: 0; else i = w*h,
+ *   u = dw*dh for a crowd ground truth, else dw*dh + gw*gh - i; iou = i / u.
+ * Per (image, category) SEGMENT: detections in descending score order (ties: ascending original position), the first 100 kept.  Per
+ *   area range [lo, hi]: a ground truth is IGNORED if it is a crowd or its area is < lo or > hi; ground truths are walked non-ignored
+ *   first (stable).  Per threshold t and detection in order: best = min(t, 1 - 1e-10), m = none; walk the ground truths: skip one
+ *   already matched at t unless it is a crowd; stop if m is non-ignored and this one is ignored; skip if iou < best; else best = iou,
+ *   m = this (equal IoU moves the match to the LATER ground truth).  A match marks both; the detection inherits the ground truth's
+ *   ignore flag.  An unmatched detection whose own area is < lo or > hi is ignored.  npig = the number of non-ignored ground truths.
+ * Per (category, area range, maxDet): the first maxDet detections of every image, images in ascending id order, stable-sorted by
+ *   descending score.  Per threshold: tp = matched and not ignored, fp = unmatched and not ignored, integer running sums;
+ *   rc = tp / npig, pr = tp / (fp + tp + 2^-52); pr made non-increasing from the right; precision[t, r] = pr[first i with
+ *   rc[i] >= recThrs[r]] or 0; recall[t] = rc[last], 0 with no detections.  A total npig of 0 leaves -1 everywhere.
+ * Summary: the twelve statistics (AP, AP50, AP75, APs, APm, APl, AR1, AR10, AR100, ARs, ARm, ARl), each the mean of the entries
+ *   > -1, or -1 with none.
+ *
+ * sc2_coco_match: ONE launch, one workgroup per segment.  dets: f64 [n_det,4] xywh ALREADY in processing order within each segment;
+ * gts: f64 [n_gt,4] xywh, gt_area: f64 [n_gt], gt_crowd: u8 [n_gt]; det_off / gt_off: i32 [n_seg+1] ascending offsets (segment s holds
+ * det_off[s] .. det_off[s+1]-1; a segment whose offsets leave 0..n_det / 0..n_gt is treated as empty); iou_thrs: f64 [10], area_rng: f64
+ * [4,2] (lo, hi), both computed by the host so that both sides compare against the same bits.  Every pointer is DEVICE memory.
+ * flags: i32 [n_det,4]: per detection and area range, bit t = matched at threshold t, bit 10+t = ignored at t.
+ * npig : i32 [n_seg,4].
+ * The IoU of the first SC2_COCO_TILE_DETS x SC2_COCO_TILE_GTS pairs of a segment is computed once, by the whole workgroup, into LDS;
+ * the forty (area range, threshold) walks run on forty lanes of one wave, serial over the detections.  Neither count is bounded:
+ * pairs outside the tile are recomputed where they are read (the same operations: the same bits), and a segment of more than
+ * SC2_COCO_TILE_GTS ground truths keeps its matched marks (one byte per ground truth and lane) in `ws` instead of LDS.
+ * ws: sc2_coco_match_ws_bytes(n_gt) bytes.  Empty segments are legal; n_seg == 0 launches nothing.  Nothing is copied to the host.
+ * A detection past the hundredth of its segment is matched like any other, behind the first hundred (it cannot change them): the
+ * cut is sc2_coco_accumulate's `rank < maxDet`. */
+long long sc2_coco_match_ws_bytes(long long n_gt);
+int sc2_coco_match(const double *dets, const double *gts, const double *gt_area, const uint8_t *gt_crowd, const int32_t *det_off,
+                   const int32_t *gt_off, int n_seg, int n_det, int n_gt, const double *iou_thrs, const double *area_rng, int32_t *flags,
+                   int32_t *npig, void *ws, void *stream);
+/* sc2_coco_accumulate: ONE launch, one workgroup per (category, area range, maxDet), looping over the ten thresholds.
+ * order: i32 [n_order], indices into flags / rank: category k's detections are order[cat_off[k] .. cat_off[k+1]-1] in that category's
+ * score-sorted order (the caller's stable sorts); cat_off: i32 [K+1]; flags: i32 [n_det,4] of sc2_coco_match; rank: i32 [n_det], the
+ * detection's position inside its (image, category) segment (kept where rank < maxDet); npig: i32 [K,4] category totals; rec_thrs: f64
+ * [101] ascending; max_dets: i32 [3].  An index outside 0..n_det-1 is skipped, a category whose offsets leave 0..n_order is empty.
+ * precision: f64 [10,101,K,4,3], recall: f64 [10,K,4,3]; every element is written.
+ * A category's detections are scanned in chunks of SC2_COCO_SCAN_CHUNK with carried totals (block-wide integer scan of the packed
+ * tp / fp counts).  The reverse running maximum and the 101 look-ups are one maximum per recall bin: precision[t, r] is the largest
+ * pr among the entries whose rc reaches recThrs[r], which only a true positive can raise -- each true positive takes its pr to the
+ * bin counting the thresholds its rc reaches (an integer maximum on the f64 bits, pr >= 0), and a suffix maximum over the 102 bins
+ * ends the threshold.  K == 0 launches nothing. */
+int sc2_coco_accumulate(const int32_t *order, const int32_t *cat_off, const int32_t *flags, const int32_t *rank, const int32_t *npig,
+                        const double *rec_thrs, const int32_t *max_dets, int K, int n_order, int n_det, double *precision, double *recall,
+                        void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Diagnostics (csrc/diag.hip; no product path calls these).                                    */
 /* ------------------------------------------------------------------------------------------ */
 /* The shader clock the chip holds while OTHER kernels run: `n_workgroups` probe waves (one per workgroup; launch >= 8 so that

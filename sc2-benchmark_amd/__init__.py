@@ -22,7 +22,7 @@ from .compression import (COMPRESSION_MODEL_CLASS_DICT, COMPRESSION_MODEL_FUNC_D
                           bmshj2018_factorized, bmshj2018_hyperprior, get_compression_model, mbt2018, mbt2018_mean)
 from .entropy import GDN  # noqa: F401
 from .transforms import (AdaptivePad, PILImageModule, PILTensorModule, QuantizedTensor, SimpleDequantizer,  # noqa: F401
-                         SimpleQuantizer, cat_list, dequantize_tensor, pascal_seg_collate_fn, pascal_seg_eval_collate_fn,
+                         SimpleQuantizer, cat_list, coco_collate_fn, dequantize_tensor, pascal_seg_collate_fn, pascal_seg_eval_collate_fn,
                          quantize_tensor)
 from .wrapper import (WRAPPER_CLASS_DICT, CodecFeatureCompressionClassifier, CodecInputCompressionClassifier,  # noqa: F401
                       EntropicClassifier, NeuralInputCompressionClassifier, SplitClassifier, wrap_model)
@@ -30,6 +30,7 @@ from .wrapper import (WRAPPER_CLASS_DICT, CodecFeatureCompressionClassifier, Cod
 from .dense import (DETECTION_MODEL_FUNC_DICT, SEGMENTATION_MODEL_FUNC_DICT, BaseRCNN, BaseSegmentationModel,  # noqa: F401
                     SegEvaluator, UpdatableBackboneWithFPN, backbone_with_fpn, deeplabv3_model, faster_rcnn_model, seg_labels)
 
+from .coco_eval import CocoBoxEvaluator, CocoDictDetection, coco_gt_from_dataset  # noqa: F401
 from .pipeline import StagePipeline, supports_stages  # noqa: F401
 from . import graphs  # noqa: F401
 

@@ -5,7 +5,7 @@
 
 It builds `models.model` (or `models.student_model`) from the reference's YAML file unchanged, loads `test.test_data_loader`
 (dataset, sampler, batch size, `collate_fn`), runs the model in eval mode under `torch.inference_mode()`, reports top-1 /
-top-5 accuracy and lets every analyzer summarise (data size in KB, as the reference logs it).  Metric totals and counts are
+top-5 accuracy (mIoU for a segmentation model, COCO box AP for a Faster R-CNN) and lets every analyzer summarise (data size in KB, as the reference logs it).  Metric totals and counts are
 summed over ranks when a process group is up (`MetricLogger.synchronize_between_processes`: SURVEY.md C5).
 """
 import argparse
@@ -209,10 +209,65 @@ def _evaluate_segmentation(model, data_loader, device, num_classes, evaluator, m
             'seconds': time.perf_counter() - t0, 'analysis': analysis, 'evaluator': evaluator}
 
 
+def evaluate_detection(model, data_loader, device, gt=None, max_samples=None, log_freq=1000, title=None, iou_types=('bbox',)):
+    """The evaluation loop of the object-detection task (script/task/object_detection.py:117-175): eval mode, analysis on, images as a
+    list on the device, the model's outputs LEFT on the device and buffered by a `CocoBoxEvaluator` under the image ids read from the
+    host-side targets; detections of all ranks are gathered, box AP is accumulated (coco_eval.py: two launches on a HIP device), the
+    twelve lines are logged and the analyzers summarised.  `gt`: anything `CocoBoxEvaluator` takes; None = `coco_gt_from_dataset` of the
+    loader's dataset.  -> {'map', 'stats', 'summary' (the printed lines), 'samples', 'seconds', 'analysis', 'evaluator'}."""
+    from .coco_eval import CocoBoxEvaluator, coco_gt_from_dataset
+    evaluator = CocoBoxEvaluator(coco_gt_from_dataset(data_loader.dataset) if gt is None else gt, iou_types)
+    model = model.to(device) if device.type == 'cuda' else model
+    with torch.inference_mode():
+        return _evaluate_detection(model, data_loader, device, evaluator, max_samples, log_freq, title)
+
+
+def _evaluate_detection(model, data_loader, device, evaluator, max_samples, log_freq, title):
+    import contextlib
+    import io
+    if hasattr(model, 'use_cpu4compression') and device.type != 'cuda':
+        model.use_cpu4compression()
+    if title is not None:
+        logger.info(title)
+    model.eval()
+    analyzable = isinstance(model, AnalyzableModule)
+    if analyzable:
+        model.activate_analysis()
+    t0 = time.perf_counter()
+    seen = 0
+    for i, (images, targets) in enumerate(data_loader):
+        if max_samples is not None and seen + len(images) > max_samples:
+            images, targets = images[:max_samples - seen], targets[:max_samples - seen]
+        image_ids = [int(t['image_id']) for t in targets]      # host-side targets: read before anything is moved
+        images = [image.to(device, non_blocking=True) for image in images]
+        outputs = model(images)
+        evaluator.update({image_id: output for image_id, output in zip(image_ids, outputs)})
+        seen += len(images)
+        if log_freq and (i + 1) % log_freq == 0:
+            logger.info('Test: [{}] {} samples'.format(i + 1, seen))
+        if max_samples is not None and seen >= max_samples:
+            break
+    evaluator.synchronize_between_processes()
+    evaluator.accumulate()
+    with contextlib.redirect_stdout(io.StringIO()) as printed:
+        evaluator.summarize()
+    logger.info(printed.getvalue())
+    analysis = []
+    if analyzable and model.activated_analysis:
+        model.summarize()
+        analysis = [a.summary() for a in model.analyzers if hasattr(a, 'summary') and getattr(a, 'file_size_list', None)]
+    stats = evaluator.coco_eval[evaluator.iou_types[0]].stats
+    return {'map': float(stats[0]), 'stats': stats.tolist(), 'summary': printed.getvalue(), 'samples': seen, 'seconds': time.perf_counter() - t0,
+            'analysis': analysis, 'evaluator': evaluator}
+
+
 def build_data_loader(dataset_dict, loader_config):
     """`test.test_data_loader` block -> DataLoader (dataset by id, sampler class, kwargs, `collate_fn` by name)."""
     from .transforms import COLLATE_FUNC_DICT
     dataset = dataset_dict[loader_config['dataset_id']]
+    if isinstance(dataset, dict) and 'coco_gt' in dataset:      # `--json`: a COCO dictionary (or its path) in place of the dataset
+        from .coco_eval import CocoDictDetection
+        dataset = CocoDictDetection(dataset['coco_gt'], seed=dataset.get('seed', 0))
     kwargs = dict(loader_config.get('kwargs') or {})
     sampler_cfg = loader_config.get('sampler') or {}
     sampler_cls = sampler_cfg.get('class_or_func')
@@ -258,6 +313,13 @@ def test_only(config, device, max_samples=None, num_workers=None):
         num_classes = ((model_config.get('kwargs') or {}).get('num_classes') or config['test'].get('num_classes') or
                        _classifier_classes(model))
         return evaluate_segmentation(model, loader, device, num_classes, max_samples=max_samples, title='[Student/model]')
+    from .dense import BaseRCNN
+    from .detection import FasterRCNN
+    if isinstance(model, (FasterRCNN, BaseRCNN)):
+        body = model._body() if isinstance(model, BaseRCNN) else None
+        if body is not None and not model.bottleneck_updated and hasattr(body, 'check_if_updatable') and body.check_if_updatable():
+            model.update()
+        return evaluate_detection(model, loader, device, max_samples=max_samples, title='[Student/model]')
     return evaluate(model, loader, device, max_samples=max_samples, title='[Student/model]')
 
 
@@ -274,7 +336,9 @@ def main(argv=None):
     if args.json:
         C.overwrite_config(config, json.loads(args.json))
     result = test_only(config, torch.device(args.device), args.max_samples, args.num_workers)
-    print(json.dumps({k: v for k, v in result.items() if k != 'evaluator'}))      # (the SegEvaluator object of a segmentation run stays in the returned dict)
+    if 'summary' in result:
+        print(result['summary'], end='')      # a detection run: the twelve lines of COCOeval's summary
+    print(json.dumps({k: v for k, v in result.items() if k not in ('evaluator', 'summary')}))      # (the evaluator object of a segmentation / detection run stays in the returned dict)
     return result
 
 

@@ -38,7 +38,7 @@ ABI_SYMBOLS = [
     'sc2_mse_partial_len', 'sc2_mse_sum_bf16', 'sc2_mse_grad_bf16', 'sc2_relu_bwd_bf16', 'sc2_relu_bwd_mse_bf16',
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
-    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_seg_predict',
+    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_seg_predict', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
 ]
 
@@ -64,6 +64,8 @@ class ArScanArgs(ctypes.Structure):
 NMS_MAX_BOXES = 16384      # SC2_NMS_MAX_BOXES
 ROI_MAX_LEVELS = 5         # SC2_ROI_MAX_LEVELS
 SEG_MAX_CLASSES = 64       # SC2_SEG_MAX_CLASSES
+COCO_THRS, COCO_RECS, COCO_AREAS, COCO_MAXDETS = 10, 101, 4, 3     # SC2_COCO_*
+COCO_TILE_DETS, COCO_TILE_GTS, COCO_SCAN_CHUNK = 100, 64, 1024
 
 
 class RoiLevel(ctypes.Structure):
@@ -137,6 +139,7 @@ class HostPolicy(object):
     eval_graph_max_batch = 1   # ... for batches up to this size (the reference evaluates at batch size 1)
     nms_hip = True             # detection.nms / batched_nms of device tensors on sc2_nms (False: the torch-op restatement, A/B)
     roi_align_hip = True       # detection.roi_align / multiscale_roi_align of device tensors on sc2_roi_align (False: torch ops, A/B)
+    coco_eval_hip = True       # coco_eval.CocoBoxEvaluator.accumulate of device tensors on sc2_coco_match + sc2_coco_accumulate (False: the torch / numpy host path of the same module; tools/coco_eval_times.py)
     seg_predict_hip = True     # dense.seg_labels (BaseSegmentationModel.predict, SegEvaluator.update_logits) of device tensors on sc2_seg_predict (False: interpolate + argmax + bincount, A/B)
 
 
@@ -310,6 +313,10 @@ def lib():
     L.sc2_nms.argtypes = [vp, vp, i32, f32, vp, vp, vp, vp]
     L.sc2_roi_align.argtypes = [RoiLevels, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]
     L.sc2_seg_predict.argtypes = [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, i32, vp, vp, vp, vp]
+    L.sc2_coco_match_ws_bytes.argtypes = [i64]
+    L.sc2_coco_match_ws_bytes.restype = i64
+    L.sc2_coco_match.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.sc2_coco_accumulate.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.sc2_rans_host_tables_create.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp)]
     L.sc2_rans_host_tables_destroy.argtypes = [vp]
     L.sc2_rans_host_tables_destroy.restype = None
@@ -1220,6 +1227,78 @@ def seg_predict(logits, size, targets=None, mat=None, want_labels=True, tag=None
         _check(lib().sc2_seg_predict(_ptr(logits), 1 if logits.dtype == torch.bfloat16 else 0, N, C, h, w, sn, sc, sh, sw, readable, H, W,
                                      _ptr(targets), _ptr(labels), _ptr(mat), _stream()), 'seg_predict')
     return labels
+
+
+# --------------------------------------------------------------------------------------------- #
+# COCO box AP: matching of every (image, category) segment and the precision / recall curves (csrc/coco.hip)
+# --------------------------------------------------------------------------------------------- #
+def _coco_arg(t, name, dtype, shape):
+    _dev(t, name)
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError('{}: expected a contiguous {} tensor of shape {}, got {} {}{}'.format(
+            name, dtype, tuple(shape), t.dtype, tuple(t.shape), '' if t.is_contiguous() else ' (not contiguous)'))
+    return t
+
+
+def coco_match(dets, gts, gt_area, gt_crowd, det_off, gt_off, iou_thrs, area_rng, flags=None, npig=None, tag=None):
+    """COCOeval's matching of every (image, category) segment in ONE launch (include/sc2_bottleneck.h: sc2_coco_match).
+    dets: f64 [n_det,4] xywh in processing order within each segment; gts: f64 [n_gt,4] xywh, gt_area: f64 [n_gt], gt_crowd: u8 [n_gt];
+    det_off / gt_off: i32 [n_seg+1]; iou_thrs: f64 [10]; area_rng: f64 [4,2] -> (flags i32 [n_det,4]: bit t matched, bit 10+t ignored;
+    npig i32 [n_seg,4]), on the device; nothing synchronises.  `flags` / `npig`: a caller's buffers to write into."""
+    n_det, n_gt = int(dets.shape[0]), int(gts.shape[0])
+    n_seg = int(det_off.shape[0]) - 1
+    if n_seg < 0 or gt_off.shape[0] != n_seg + 1:
+        raise ValueError('coco_match: {} detection offsets and {} ground-truth offsets (n_seg + 1 of each)'.format(det_off.shape[0], gt_off.shape[0]))
+    dev = _coco_arg(dets, 'dets', torch.float64, (n_det, 4)).device
+    _coco_arg(gts, 'gts', torch.float64, (n_gt, 4))
+    _coco_arg(gt_area, 'gt_area', torch.float64, (n_gt,))
+    _coco_arg(gt_crowd, 'gt_crowd', torch.uint8, (n_gt,))
+    _coco_arg(det_off, 'det_off', torch.int32, (n_seg + 1,))
+    _coco_arg(gt_off, 'gt_off', torch.int32, (n_seg + 1,))
+    _coco_arg(iou_thrs, 'iou_thrs', torch.float64, (COCO_THRS,))
+    _coco_arg(area_rng, 'area_rng', torch.float64, (COCO_AREAS, 2))
+    if flags is None:
+        flags = torch.empty((n_det, COCO_AREAS), dtype=torch.int32, device=dev)
+    if npig is None:
+        npig = torch.empty((n_seg, COCO_AREAS), dtype=torch.int32, device=dev)
+    _coco_arg(flags, 'flags', torch.int32, (n_det, COCO_AREAS))
+    _coco_arg(npig, 'npig', torch.int32, (n_seg, COCO_AREAS))
+    for t in (gts, gt_area, gt_crowd, det_off, gt_off, iou_thrs, area_rng, flags, npig):
+        if t.device != dev:
+            raise ValueError('coco_match: tensors on {} and {}'.format(dev, t.device))
+    if n_seg == 0:
+        return flags, npig
+    ws = torch.empty(int(lib().sc2_coco_match_ws_bytes(n_gt)), dtype=torch.uint8, device=dev)
+    with _timed(tag or 'coco_match'):
+        _check(lib().sc2_coco_match(_ptr(dets), _ptr(gts), _ptr(gt_area), _ptr(gt_crowd), _ptr(det_off), _ptr(gt_off), n_seg, n_det, n_gt,
+                                    _ptr(iou_thrs), _ptr(area_rng), _ptr(flags), _ptr(npig), _ptr(ws), _stream()), 'coco_match')
+    return flags, npig
+
+
+def coco_accumulate(order, cat_off, flags, rank, npig, rec_thrs, max_dets, tag=None):
+    """COCOeval's accumulate for every (category, area range, maxDet) in ONE launch (include/sc2_bottleneck.h: sc2_coco_accumulate).
+    order: i32 [n_order], category k's detections in its score-sorted order at cat_off[k] .. cat_off[k+1]-1 (indices into flags / rank);
+    cat_off: i32 [K+1]; flags: i32 [n_det,4] of coco_match; rank: i32 [n_det]; npig: i32 [K,4] category totals; rec_thrs: f64 [101];
+    max_dets: i32 [3] -> (precision f64 [10,101,K,4,3], recall f64 [10,K,4,3]) on the device; nothing synchronises."""
+    n_order, n_det, K = int(order.shape[0]), int(flags.shape[0]), int(cat_off.shape[0]) - 1
+    if K < 0:
+        raise ValueError('coco_accumulate: cat_off is empty (K + 1 offsets)')
+    dev = _coco_arg(order, 'order', torch.int32, (n_order,)).device
+    _coco_arg(cat_off, 'cat_off', torch.int32, (K + 1,))
+    _coco_arg(flags, 'flags', torch.int32, (n_det, COCO_AREAS))
+    _coco_arg(rank, 'rank', torch.int32, (n_det,))
+    _coco_arg(npig, 'npig', torch.int32, (K, COCO_AREAS))
+    _coco_arg(rec_thrs, 'rec_thrs', torch.float64, (COCO_RECS,))
+    _coco_arg(max_dets, 'max_dets', torch.int32, (COCO_MAXDETS,))
+    for t in (cat_off, flags, rank, npig, rec_thrs, max_dets):
+        if t.device != dev:
+            raise ValueError('coco_accumulate: tensors on {} and {}'.format(dev, t.device))
+    precision = torch.empty((COCO_THRS, COCO_RECS, K, COCO_AREAS, COCO_MAXDETS), dtype=torch.float64, device=dev)
+    recall = torch.empty((COCO_THRS, K, COCO_AREAS, COCO_MAXDETS), dtype=torch.float64, device=dev)
+    with _timed(tag or 'coco_accumulate'):
+        _check(lib().sc2_coco_accumulate(_ptr(order), _ptr(cat_off), _ptr(flags), _ptr(rank), _ptr(npig), _ptr(rec_thrs), _ptr(max_dets), K,
+                                         n_order, n_det, _ptr(precision), _ptr(recall), _stream()), 'coco_accumulate')
+    return precision, recall
 
 
 def bn_train_fwd(x_nhwc, gamma, beta, running_mean, running_var, momentum, eps, relu, residual=None, tag=None):

@@ -405,6 +405,13 @@ def pascal_seg_eval_collate_fn(batch):
     return cat_list(images, fill_value=0), cat_list(targets, fill_value=255)
 
 
+@register_collate_func
+def coco_collate_fn(batch):
+    """(image, target dict) pairs of COCO 2017 -> (images as a tuple, targets as a tuple): detection batches are lists, never padded
+    (every `configs/coco2017/**` loader names it)."""
+    return tuple(zip(*batch))
+
+
 # --------------------------------------------------------------------------------------------------------- sc2bench.codec
 def _pil_codec_round_trip(pil_img, save_kwargs, open_kwargs):
     """image -> codec bytes in memory -> reopened image: (image, byte count of the coded file)."""
