@@ -111,6 +111,9 @@ int sc2_avgpool_nhwc(const void *x, float *y_f32, void *y_bf16, int N, int HW, i
  * training: configs/.../splitable_resnet50-fp-beta0.08_from_resnet50.yaml:231-295; sc2bench/models/backbone.py:235-254 runs the blocks).
  *   forward : y = relu?((x - mean) rstd gamma + beta (+ residual)); mean / biased variance over the M rows; running_mean / running_var
  *             (may both be NULL) take the momentum update with the UNBIASED variance, as torch; save_mean / save_rstd [C] for backward
+ *             NaN propagates as in torch: the ReLU zeroes only where its operand is < 0 and the variance is clamped only where it is
+ *             < 0, so one NaN in x makes that channel's save_mean, save_rstd, running statistics and every y of the channel NaN (never
+ *             a channel of zeros), and the backward on them gives a NaN dx for the channel
  *   backward: dz = y ? dy * (y > 0) : dy (y = the forward's output when it applied the ReLU, else NULL); dgamma = sum dz xhat, dbeta =
  *             sum dz; dx = gamma rstd (dz - dbeta / M - xhat dgamma / M); dz (NULL, or bf16 like dx) = the residual operand's gradient
  *   gamma, beta, running_*, save_*, dgamma, dbeta : f32 [C];  ws : f32 scratch of sc2_bn_ws_floats(M, C) floats (per-workgroup partial

@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void bn_fwd_finalize_kernel(const float *__res
         const float inv_m = 1.0f / (float)M;
         const float mu = su * inv_m;
         float var = sq * inv_m - mu * mu;
-        var = var > 0.f ? var : 0.f;
+        var = var < 0.f ? 0.f : var;                    // (the clamp keeps NaN: a NaN channel gets NaN rstd and running_var, as torch)
         const float rs = 1.0f / __builtin_sqrtf(var + eps);
         save_mean[c] = mu;
         save_rstd[c] = rs;
@@ -188,7 +188,7 @@ __global__ __launch_bounds__(256) void bn_fwd_finalize_kernel(const float *__res
     }
 }
 
-// y = relu?(x * scale + shift (+ residual))
+// y = relu?(x * scale + shift (+ residual)); the ReLU propagates NaN
 __global__ __launch_bounds__(256) void bn_apply_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ residual,
                                                        const float *__restrict__ scale, const float *__restrict__ shift, int relu,
                                                        long long chunks, int cpr, uint16_t *__restrict__ y) {
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const uint16_t *__restric
         for (int t = 0; t < 8; ++t) {
             float v = a[t] * sc[t] + sh[t];
             if (residual) v += r[t];
-            o[t] = (relu && !(v > 0.f)) ? 0.f : v;
+            o[t] = (relu && v < 0.f) ? 0.f : v;          // (zero only where v < 0: a NaN stays NaN, as torch.relu and bq.hip's relu_keep_nan)
         }
         reinterpret_cast<uint4 *>(y)[q] = bn_pack8(o);
     }
