@@ -951,6 +951,51 @@ int sc2_coco_accumulate(const int32_t *order, const int32_t *cat_off, const int3
                         void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Codec feature compression (csrc/jpeg.hip): a feature map through baseline JPEG, three channels per image, as the     */
+/* reference's PILTensorModule(format='JPEG') computes it.  tests/ref_jpeg.py restates it as a sequential integer program. */
+/* ------------------------------------------------------------------------------------------ */
+#define SC2_JPEG_MAX_SIDE 64      /* H and W of the feature map: an image's planes, coefficients and bits stay in 53 KB of LDS */
+#define SC2_JPEG_GREY 0
+#define SC2_JPEG_RGB 1
+#define SC2_JPEG_HEADER_GREY 328  /* bytes in front of the entropy-coded segment: SOI, JFIF APP0, one DQT per table, SOF0, one DHT per */
+#define SC2_JPEG_HEADER_RGB 623   /* table, SOS -- the same at every size and quality */
+#define SC2_JPEG_NEGATIVE_MIN 1   /* status bits of an image the kernel leaves to the caller's host path */
+#define SC2_JPEG_ZERO_MAX 2
+#define SC2_JPEG_NOT_FINITE 4
+/* x: f32 [B,C,H,W] contiguous, H and W in 1..SC2_JPEG_MAX_SIDE (SC2_ERR_UNSUPPORTED beyond), quality in 1..100.  Every sample is cut
+ * into C/3 images of three channels (RGB) followed by C%3 images of one channel (grey): n = C/3 + C%3 images per sample, image
+ * `sample * n + g` everywhere below.  ONE launch on `stream`, one workgroup per image, nothing copied to the host.
+ * Per image, with low = min and high = max of its channels:
+ *   status: SC2_JPEG_NOT_FINITE alone (a NaN or an infinity in the group), else SC2_JPEG_NEGATIVE_MIN (low < 0: normalised values
+ *   above 1 would reach an implementation-defined float-to-byte cast) | SC2_JPEG_ZERO_MAX (high <= 0: 0 / 0).  A non-zero status writes
+ *   size 0 and the extrema, and nothing else: the caller runs that sample on its host path.
+ *   p = u8(trunc(((v - low) / high) * 255)): three f32 operations, the division correctly rounded.
+ *   RGB: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + 128 * 65536 + 32767) >> 16,
+ *   Cr = (32768 R - 27439 G - 5329 B + 128 * 65536 + 32767) >> 16; sampling 2x2 / 1x1 / 1x1.  Chroma: rows padded to an even count with
+ *   the last row, columns with the last pixel; (a + b + c + d + bias) >> 2, bias 1, 2, 1, 2 ... along a row; the last row then repeated
+ *   to whole blocks.  Luma and grey planes edge-replicated to whole blocks.
+ *   Level shift by 128; the slow-integer forward DCT with 13-bit constants (rows scaled by 4, columns descaled by 2 / 15, every shift
+ *   rounding half up); coefficient = sign(x) * ((|x| + (8q >> 1)) / (8q)) with the Annex K tables scaled by `quality`
+ *   (s = 5000 / quality below 50, else 200 - 2 quality; q = clamp((base * s + 50) / 100, 1, 255)).
+ *   One scan: interleaved for RGB (MCU = four Y blocks, Cb, Cr), block after block for grey.  A Y block of an MCU beyond the block
+ *   grid is a dummy: no AC, the DC of the block before it in the MCU.  DC as the difference from the previous block of its component,
+ *   the Annex K Huffman tables, ZRL for runs above 15, EOB for trailing zeros, the last byte filled with 1 bits, a zero byte behind
+ *   every 0xFF.
+ *   Decoding from the coefficients on chip: times the table, the slow-integer inverse DCT (columns descaled by 11, rows by 18), + 128
+ *   clamped to 0..255; chroma through the triangle upsampler where the chroma plane has more than two columns (vertically 3 near +
+ *   far, the row beyond an edge equal to the edge row; horizontally (3 s + left + 8) >> 4 and (3 s + right + 7) >> 4, (4 s + 8) >> 4
+ *   and (4 s + 7) >> 4 at the ends), repeated 2 x 2 otherwise; R = Y + ((91881 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16),
+ *   G = Y + ((-22554 cb - 46802 cr + 32768) >> 16) with cb, cr minus 128, clamped.  out = (float(p) / 255) * high + low, unfused.
+ * recon  : f32 [B,C,H,W].  sizes: i32 [B*n], bytes of the complete file: SC2_JPEG_HEADER_* + the entropy-coded segment + 2 (EOI).
+ * extrema: f32 [B*n,2] (low, high).  status: i32 [B*n].
+ * bytes  : NULL (no byte store is issued), or B*n slots of slot_bytes >= sc2_jpeg_max_bytes(RGB if C >= 3 else grey, H, W): the
+ *          segment of image i at bytes + i * slot_bytes.  A block's bits are placed by a prefix sum over the blocks' bit lengths and
+ *          OR-ed into LDS words; the stuffing by a prefix sum over the 0xFF counts: no bit depends on the order of arrival. */
+long long sc2_jpeg_max_bytes(int mode, int H, int W);   /* every scan block at its longest code, every byte stuffed; -1: bad arguments */
+int sc2_jpeg_tensor_codec(const float *x, int B, int C, int H, int W, int quality, float *recon, int32_t *sizes, float *extrema,
+                          int32_t *status, uint8_t *bytes, long long slot_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Diagnostics (csrc/diag.hip; no product path calls these).                                    */
 /* ------------------------------------------------------------------------------------------ */
 /* The shader clock the chip holds while OTHER kernels run: `n_workgroups` probe waves (one per workgroup; launch >= 8 so that

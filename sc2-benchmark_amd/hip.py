@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
     'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_seg_predict', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
+    'sc2_jpeg_max_bytes', 'sc2_jpeg_tensor_codec',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
 ]
 
@@ -66,6 +67,10 @@ ROI_MAX_LEVELS = 5         # SC2_ROI_MAX_LEVELS
 SEG_MAX_CLASSES = 64       # SC2_SEG_MAX_CLASSES
 COCO_THRS, COCO_RECS, COCO_AREAS, COCO_MAXDETS = 10, 101, 4, 3     # SC2_COCO_*
 COCO_TILE_DETS, COCO_TILE_GTS, COCO_SCAN_CHUNK = 100, 64, 1024
+JPEG_MAX_SIDE = 64         # SC2_JPEG_MAX_SIDE
+JPEG_GREY, JPEG_RGB = 0, 1
+JPEG_HEADER_BYTES = {0: 328, 1: 623}     # SC2_JPEG_HEADER_GREY / _RGB: a file is header + segment + 2
+JPEG_NEGATIVE_MIN, JPEG_ZERO_MAX, JPEG_NOT_FINITE = 1, 2, 4     # SC2_JPEG_* status bits
 
 
 class RoiLevel(ctypes.Structure):
@@ -140,6 +145,7 @@ class HostPolicy(object):
     nms_hip = True             # detection.nms / batched_nms of device tensors on sc2_nms (False: the torch-op restatement, A/B)
     roi_align_hip = True       # detection.roi_align / multiscale_roi_align of device tensors on sc2_roi_align (False: torch ops, A/B)
     coco_eval_hip = True       # coco_eval.CocoBoxEvaluator.accumulate of device tensors on sc2_coco_match + sc2_coco_accumulate (False: the torch / numpy host path of the same module; tools/coco_eval_times.py)
+    jpeg_codec_hip = True      # transforms.PILTensorModule(format='JPEG') of f32 device tensors up to 64 x 64 on sc2_jpeg_tensor_codec (False: PIL per channel group on the host, A/B; tools/jpeg_codec_times.py: 0.36 against 42.7 ms at [1,512,28,28])
     seg_predict_hip = True     # dense.seg_labels (BaseSegmentationModel.predict, SegEvaluator.update_logits) of device tensors on sc2_seg_predict (False: interpolate + argmax + bincount, A/B)
 
 
@@ -317,6 +323,9 @@ def lib():
     L.sc2_coco_match_ws_bytes.restype = i64
     L.sc2_coco_match.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.sc2_coco_accumulate.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.sc2_jpeg_max_bytes.argtypes = [i32, i32, i32]
+    L.sc2_jpeg_max_bytes.restype = i64
+    L.sc2_jpeg_tensor_codec.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]
     L.sc2_rans_host_tables_create.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp)]
     L.sc2_rans_host_tables_destroy.argtypes = [vp]
     L.sc2_rans_host_tables_destroy.restype = None
@@ -1227,6 +1236,54 @@ def seg_predict(logits, size, targets=None, mat=None, want_labels=True, tag=None
         _check(lib().sc2_seg_predict(_ptr(logits), 1 if logits.dtype == torch.bfloat16 else 0, N, C, h, w, sn, sc, sh, sw, readable, H, W,
                                      _ptr(targets), _ptr(labels), _ptr(mat), _stream()), 'seg_predict')
     return labels
+
+
+# --------------------------------------------------------------------------------------------- #
+# codec feature compression: a feature map through baseline JPEG, three channels per image (csrc/jpeg.hip)
+# --------------------------------------------------------------------------------------------- #
+JpegCodecResult = collections.namedtuple('JpegCodecResult', ['recon', 'sizes', 'status', 'extrema', 'meta', 'bytes', 'slot_bytes'])
+
+
+def jpeg_max_bytes(mode, H, W):
+    """Upper bound of one image's entropy-coded segment (mode: JPEG_GREY / JPEG_RGB)."""
+    n = int(lib().sc2_jpeg_max_bytes(int(mode), int(H), int(W)))
+    if n < 0:
+        raise Sc2Error('jpeg_max_bytes: mode {} at {}x{} (sides 1..{})'.format(mode, H, W, JPEG_MAX_SIDE))
+    return n
+
+
+def jpeg_tensor_codec(x, quality, want_bytes=False, tag=None):
+    """What the reference's `PILTensorModule(format='JPEG', quality=quality)` computes for every sample of x [B,C,H,W] (f32, H and W
+    at most 64), in ONE launch (include/sc2_bottleneck.h: sc2_jpeg_tensor_codec): n = C // 3 + C % 3 images per sample.
+    -> JpegCodecResult: recon f32 [B,C,H,W]; sizes, status: int32 [B*n] (views of `meta` [2, B*n]: one device-to-host read brings
+    both), sizes = bytes of the complete file (header + segment + EOI); extrema f32 [B*n,2] (low, high); bytes uint8 [B*n, slot_bytes]
+    holding each image's entropy-coded segment (size - JPEG_HEADER_BYTES[mode] - 2 bytes of it), or None.
+    An image whose status is not 0 (JPEG_* bits) has size 0 and an unwritten reconstruction: the caller's host path takes that sample."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise Sc2Error('jpeg_tensor_codec: x must be a tensor on a HIP device (got {}); there is no CPU fallback in this package'
+                       .format('device=' + str(x.device) if isinstance(x, torch.Tensor) else type(x)))
+    if x.dtype != torch.float32:
+        raise Sc2Error('jpeg_tensor_codec: an f32 tensor is required, got {}'.format(x.dtype))
+    if x.dim() != 4 or x.numel() == 0:
+        raise Sc2Error('jpeg_tensor_codec: a non-empty [B,C,H,W] tensor is required, got shape {}'.format(tuple(x.shape)))
+    B, C, H, W = (int(v) for v in x.shape)
+    if H > JPEG_MAX_SIDE or W > JPEG_MAX_SIDE:
+        raise Sc2Error('jpeg_tensor_codec: {}x{} feature maps (at most {} per side)'.format(H, W, JPEG_MAX_SIDE))
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise Sc2Error('jpeg_tensor_codec: quality {!r} (an integer in 1..100)'.format(quality))
+    x = x.detach().contiguous()
+    n_img = B * (C // 3 + C % 3)
+    recon = torch.empty_like(x)
+    meta = torch.empty((2, n_img), dtype=torch.int32, device=x.device)
+    extrema = torch.empty((n_img, 2), dtype=torch.float32, device=x.device)
+    slot, coded = 0, None
+    if want_bytes:
+        slot = jpeg_max_bytes(JPEG_RGB if C >= 3 else JPEG_GREY, H, W)
+        coded = torch.empty((n_img, slot), dtype=torch.uint8, device=x.device)
+    with _timed(tag or 'jpeg_tensor_codec'):
+        _check(lib().sc2_jpeg_tensor_codec(_ptr(x), B, C, H, W, quality, _ptr(recon), _ptr(meta[0]), _ptr(extrema), _ptr(meta[1]),
+                                           _ptr(coded), slot, _stream()), 'jpeg_tensor_codec')
+    return JpegCodecResult(recon, meta[0], meta[1], extrema, meta, coded, slot)
 
 
 # --------------------------------------------------------------------------------------------- #

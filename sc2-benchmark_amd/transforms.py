@@ -5,7 +5,9 @@ image; `config.resolve` maps `torchvision.transforms.<Name>` here).
 * `PILTensorModule` -- sc2bench/transforms/codec.py:114-186: a feature tensor [C,H,W] goes through an image codec three
   channels at a time (config 1: JPEG quality 90, configs/ilsvrc2012/feature_compression/jpeg-resnet50.yaml:42-48).  The
   normalisation is the reference's `(x - min) / max` and `* max + min` (codec.py:159,170) -- not a min-max scaling, kept
-  as is because the reported sizes and accuracies depend on it.
+  as is because the reported sizes and accuracies depend on it.  An f32 device tensor of at most 64 x 64 per channel with plain
+  `format='JPEG'` (optional integer quality) runs on the library's kernel (csrc/jpeg.hip: one launch per batch, `forward_batch`),
+  with the same features and sizes bit for bit; everything else goes through PIL as before.
 * `PILImageModule` -- codec.py:79-111.
 * `AdaptivePad` -- sc2bench/transforms/misc.py:105-154 (tests 'equal_side', otherwise pads right and bottom).
 * `Compose`, `Resize`, `CenterCrop`, `ToTensor`, `Normalize`, `RandomResizedCrop`, `RandomHorizontalFlip` -- torchvision
@@ -460,7 +462,7 @@ class PILTensorModule(nn.Module):
             groups[-1:] = list(groups[-1].split(1, dim=0))
         return groups
 
-    def forward(self, x, *args):
+    def _forward_host(self, x, with_size):
         # written against the behaviour of codec.py:141-186: per channel group, scale with the group's own extrema AS THE
         # REFERENCE DOES -- (v - min) / max on the way in, v * max + min on the way out, which is not a min-max scaling and
         # must not be "fixed"  --, 8-bit image through the codec, back to a tensor on x's device.  The
@@ -476,10 +478,84 @@ class PILTensorModule(nn.Module):
             lows.append(low)
             highs.append(high)
         features = torch.vstack(restored)
-        if not self.returns_file_size:
+        if not with_size:
             return features
         side_info = get_binary_object_size(lows, unit_size=1) + get_binary_object_size(highs, unit_size=1)
         return features, coded_bytes + side_info
+
+    # ---- baseline JPEG of an f32 device tensor: one launch for the whole batch (csrc/jpeg.hip)
+    _side_info_cache = dict()
+
+    def _jpeg_quality(self):
+        """The quality when `save_kwargs` / `open_kwargs` ask for nothing but `format='JPEG'` at an integer quality (Pillow's default
+        is 75) -- the one case the kernel restates --, else None: `optimize`, `subsampling`, `progressive`, other formats stay with PIL."""
+        kw = self.save_kwargs
+        if self.open_kwargs or set(kw) - {'format', 'quality'} or not isinstance(kw.get('format'), str) or kw['format'].upper() != 'JPEG':
+            return None
+        quality = kw.get('quality', 75)
+        if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+            return None
+        return quality
+
+    def _kernel_quality(self, x):
+        """The quality when x [..., C,H,W] goes to the kernel, else None."""
+        quality = self._jpeg_quality()
+        if quality is None or not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.numel() == 0:
+            return None
+        from . import hip
+        if x.shape[-1] > hip.JPEG_MAX_SIDE or x.shape[-2] > hip.JPEG_MAX_SIDE or not hip.host_policy.jpeg_codec_hip:
+            return None
+        return quality
+
+    @classmethod
+    def _side_info_bytes(cls, n, dtype, device):
+        """What the host path adds for the two pickled lists of n 0-dim extrema on `device`: the pickle's length depends on n, dtype
+        and device, not on the values, so it is measured once per key on real 0-dim tensors."""
+        key = (n, dtype, str(device))
+        if key not in cls._side_info_cache:
+            scalars = [torch.zeros((), dtype=dtype, device=device) for _ in range(n)]
+            cls._side_info_cache[key] = 2 * get_binary_object_size(scalars, unit_size=1)
+        return cls._side_info_cache[key]
+
+    def _forward_kernel(self, x, quality):
+        """x [B,C,H,W] on the device -> (features [B,C,H,W], [size per sample]): one launch, one device-to-host read (sizes and status
+        words).  A sample with a group the kernel leaves alone (negative minimum, all zero, NaN / infinity) takes the host path."""
+        from . import hip, jpeg_format
+        res = hip.jpeg_tensor_codec(x, quality)
+        B, C, H, W = (int(v) for v in x.shape)
+        n_rgb, n_grey = C // 3, C % 3
+        n = n_rgb + n_grey
+        meta = res.meta.cpu().reshape(2, B, n)
+        # (the kernel counts whole files; the header length it adds is the one Pillow writes at this size and quality)
+        for count, mode, kernel_mode in ((n_rgb, 'RGB', hip.JPEG_RGB), (n_grey, 'L', hip.JPEG_GREY)):
+            if count and jpeg_format.checked_header_bytes(mode, H, W, quality) != hip.JPEG_HEADER_BYTES[kernel_mode]:
+                raise hip.Sc2Error('jpeg header of {} bytes expected for mode {}'.format(hip.JPEG_HEADER_BYTES[kernel_mode], mode))
+        side_info = self._side_info_bytes(n, x.dtype, x.device)
+        features, sizes = res.recon, []
+        for b in range(B):
+            if bool(meta[1, b].any()):
+                restored, size = self._forward_host(x[b], True)
+                features[b] = restored
+                sizes.append(size)
+            else:
+                sizes.append(int(meta[0, b].sum()) + side_info)
+        return features, sizes
+
+    def forward(self, x, *args):
+        quality = self._kernel_quality(x) if isinstance(x, torch.Tensor) and x.dim() == 3 else None
+        if quality is None:
+            return self._forward_host(x, self.returns_file_size)
+        features, sizes = self._forward_kernel(x.unsqueeze(0), quality)
+        return (features[0], sizes[0]) if self.returns_file_size else features[0]
+
+    def forward_batch(self, x):
+        """x [B,C,H,W] -> (features [B,C,H,W], [file size of every sample]): what `forward` gives sample by sample."""
+        assert x.dim() == 4
+        quality = self._kernel_quality(x)
+        if quality is not None:
+            return self._forward_kernel(x, quality)
+        pairs = [self._forward_host(sample, True) for sample in x]
+        return torch.stack([f for f, _ in pairs]), [size for _, size in pairs]
 
     def __repr__(self):
         return self.__class__.__name__ + '(returns_file_size={}, open_kwargs={}, save_kwargs={})'.format(

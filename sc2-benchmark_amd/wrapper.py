@@ -20,6 +20,7 @@ from .analysis import AnalyzableModule
 from .backbone import UpdatableBackbone
 from .layer import EntropyBottleneckLayer
 from .training import redesign_model
+from .transforms import Compose
 
 WRAPPER_CLASS_DICT = dict()
 
@@ -44,8 +45,26 @@ def _analyzer_configs(analysis_config):
 class _PerSampleCodec(object):
     """codec -> analyze(file size) -> post_transform for every sample of a batch, joined as the reference joins them."""
 
+    def _batch_codec(self):
+        """The codec when it takes a whole batch (`forward_batch` of transforms.PILTensorModule, alone or as the one transform of a
+        `Compose`) and reports sizes, else None."""
+        codec = self.codec_encoder_decoder
+        if isinstance(codec, Compose) and len(codec.transforms) == 1:
+            codec = codec.transforms[0]
+        return codec if hasattr(codec, 'forward_batch') and getattr(codec, 'returns_file_size', False) else None
+
     def _through_codec(self, samples):
         outputs = []
+        codec = self._batch_codec() if isinstance(samples, torch.Tensor) and samples.dim() == 4 else None
+        if codec is not None:
+            features, sizes = codec.forward_batch(samples)
+            for sample, file_size in zip(features, sizes):
+                if not self.training:
+                    self.analyze(file_size)
+                if self.post_transform is not None:
+                    sample = self.post_transform(sample)
+                outputs.append(sample.unsqueeze(0))
+            return torch.hstack(outputs).to(self.device)
         for sample in samples:
             if self.codec_encoder_decoder is not None:
                 sample, file_size = self.codec_encoder_decoder(sample)
