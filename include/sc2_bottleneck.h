@@ -996,6 +996,44 @@ int sc2_jpeg_tensor_codec(const float *x, int B, int C, int H, int W, int qualit
                           int32_t *status, uint8_t *bytes, long long slot_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* Codec input compression (csrc/jpeg_image.hip): 8-bit images through baseline JPEG, as the reference's                  */
+/* PILImageModule(format='JPEG') computes them.  The arithmetic, the tables and the file format are those of                */
+/* sc2_jpeg_tensor_codec above from "RGB: Y = ..." to the colour conversion back; tests/ref_jpeg.py restates them.          */
+/* ------------------------------------------------------------------------------------------ */
+#define SC2_JPEG_IMAGE_MAX_SIDE 2048    /* H and W: 6 * 128 * 128 scan blocks of at most 1660 bits keep every bit offset inside int32 */
+#define SC2_JPEG_IMAGE_CHUNK_BLOCKS 128 /* scan blocks the entropy pass codes per step */
+/* x: u8, element [b,c,y,x] at x + b*sb + c*sc + y*sh + x*sw (non-negative element strides: a CHW tensor and the permuted view of an
+ * HWC one are read in place).  C == 3: RGB with 2x2 / 1x1 / 1x1 sampling; C == 1: grey.  H and W in 1..SC2_JPEG_IMAGE_MAX_SIDE,
+ * quality in 1..100 (SC2_ERR_UNSUPPORTED for another C, side or quality; SC2_ERR_INVALID_ARG for B < 1, a NULL or misaligned pointer,
+ * a short workspace, short byte slots).  The input is 8-bit already: no extrema, no status words.  Three launches on `stream`, whose
+ * boundaries are the only dependencies; no workgroup waits for another, nothing is copied to the host.
+ *   workspace: sc2_jpeg_image_workspace_bytes(B, C, H, W) bytes, 4-byte aligned: i16 [B][n_scan][64], the quantised coefficients of
+ *     every scan block in scan order (RGB: MCU after MCU in rows of ceil(W/16), four Y blocks, Cb, Cr; grey: block rows of ceil(W/8)),
+ *     natural order inside a block.  A Y block of an MCU beyond the block grid is stored as the scan codes it: the DC of the block
+ *     before it in the MCU, AC zero.  Every element is written before it is read; its content before the call does not matter.
+ *   transform: one workgroup per (image, MCU row -- grey: block row --, chunk of 128 pixel columns).  The strip's pixels are
+ *     edge-replicated on chip; a chroma row min(8 r + i, ceil(H/2) - 1) of MCU row r always lies inside r's own 16 pixel rows.
+ *   entropy: one workgroup per image codes SC2_JPEG_IMAGE_CHUNK_BLOCKS scan blocks per step, one lane per block; the chunk's
+ *     coefficients are staged in LDS in zigzag order and a lane visits only the non-zero ones of its block.  A block's DC predecessor
+ *     -- the block before it OF ITS COMPONENT in scan order, also across chunks and strips -- is a stored coefficient (of the chunk
+ *     on chip, or of the workspace for a chunk's first blocks), so no DC predictor is carried.
+ *     The chunk carry is the count of segment bytes written so far (stuffing included) and the 0..7 bits behind the last whole byte,
+ *     which open the next chunk's bit area; bits are placed by a prefix sum over the blocks' lengths and OR-ed into LDS words the kernel
+ *     clears first, the stuffing by a prefix sum over the 0xFF counts of the chunk's whole bytes; the last chunk fills its last byte
+ *     with 1 bits.  No bit depends on the order of arrival.
+ *   decode: one workgroup per strip, from the workspace.  Strip context: the chroma blocks of the MCU row above and below and of the
+ *     MCU column left and right of the strip are decoded with it, so that the triangle upsampler finds the row / column beyond the
+ *     strip; the image's first and last chroma rows repeat themselves, a chroma plane of one or two columns is repeated 2 x 2.
+ * recon: u8 [B,C,H,W] contiguous.  sizes: i32 [B], bytes of the complete file: SC2_JPEG_HEADER_* + the entropy-coded segment + 2.
+ * bytes: NULL (no byte store is issued), or B slots of slot_bytes >= sc2_jpeg_image_max_bytes(C, H, W): image i's segment at
+ *        bytes + i * slot_bytes; nothing behind the segment is written. */
+long long sc2_jpeg_image_max_bytes(int C, int H, int W);            /* the formula of sc2_jpeg_max_bytes without the 64 cap; -1: bad arguments */
+long long sc2_jpeg_image_workspace_bytes(int B, int C, int H, int W);   /* -1: bad arguments */
+int sc2_jpeg_image_codec(const uint8_t *x, long long sb, long long sc, long long sh, long long sw, int B, int C, int H, int W, int quality,
+                         uint8_t *recon, int32_t *sizes, uint8_t *bytes, long long slot_bytes, void *workspace, long long workspace_bytes,
+                         void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Diagnostics (csrc/diag.hip; no product path calls these).                                    */
 /* ------------------------------------------------------------------------------------------ */
 /* The shader clock the chip holds while OTHER kernels run: `n_workgroups` probe waves (one per workgroup; launch >= 8 so that

@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
     'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_seg_predict', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
-    'sc2_jpeg_max_bytes', 'sc2_jpeg_tensor_codec',
+    'sc2_jpeg_max_bytes', 'sc2_jpeg_tensor_codec', 'sc2_jpeg_image_max_bytes', 'sc2_jpeg_image_workspace_bytes', 'sc2_jpeg_image_codec',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
 ]
 
@@ -71,6 +71,8 @@ JPEG_MAX_SIDE = 64         # SC2_JPEG_MAX_SIDE
 JPEG_GREY, JPEG_RGB = 0, 1
 JPEG_HEADER_BYTES = {0: 328, 1: 623}     # SC2_JPEG_HEADER_GREY / _RGB: a file is header + segment + 2
 JPEG_NEGATIVE_MIN, JPEG_ZERO_MAX, JPEG_NOT_FINITE = 1, 2, 4     # SC2_JPEG_* status bits
+JPEG_IMAGE_MAX_SIDE = 2048       # SC2_JPEG_IMAGE_MAX_SIDE
+JPEG_IMAGE_CHUNK_BLOCKS = 128    # SC2_JPEG_IMAGE_CHUNK_BLOCKS
 
 
 class RoiLevel(ctypes.Structure):
@@ -146,6 +148,7 @@ class HostPolicy(object):
     roi_align_hip = True       # detection.roi_align / multiscale_roi_align of device tensors on sc2_roi_align (False: torch ops, A/B)
     coco_eval_hip = True       # coco_eval.CocoBoxEvaluator.accumulate of device tensors on sc2_coco_match + sc2_coco_accumulate (False: the torch / numpy host path of the same module; tools/coco_eval_times.py)
     jpeg_codec_hip = True      # transforms.PILTensorModule(format='JPEG') of f32 device tensors up to 64 x 64 on sc2_jpeg_tensor_codec (False: PIL per channel group on the host, A/B; tools/jpeg_codec_times.py: 0.36 against 42.7 ms at [1,512,28,28])
+    jpeg_image_hip = True      # transforms.PILImageModule(format='JPEG').forward_batch of equal-size RGB / grey PIL images up to 2048 x 2048 on sc2_jpeg_image_codec (False: PIL per image on the host, A/B; tools/jpeg_image_times.py, codec + ToTensor + Normalize to the classifier input: 0.39 against 0.50 ms at [1,3,224,224], 10.4 against 174 ms at [256,3,224,224])
     seg_predict_hip = True     # dense.seg_labels (BaseSegmentationModel.predict, SegEvaluator.update_logits) of device tensors on sc2_seg_predict (False: interpolate + argmax + bincount, A/B)
 
 
@@ -326,6 +329,11 @@ def lib():
     L.sc2_jpeg_max_bytes.argtypes = [i32, i32, i32]
     L.sc2_jpeg_max_bytes.restype = i64
     L.sc2_jpeg_tensor_codec.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i64, vp]
+    L.sc2_jpeg_image_max_bytes.argtypes = [i32, i32, i32]
+    L.sc2_jpeg_image_max_bytes.restype = i64
+    L.sc2_jpeg_image_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    L.sc2_jpeg_image_workspace_bytes.restype = i64
+    L.sc2_jpeg_image_codec.argtypes = [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, i64, vp]
     L.sc2_rans_host_tables_create.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp)]
     L.sc2_rans_host_tables_destroy.argtypes = [vp]
     L.sc2_rans_host_tables_destroy.restype = None
@@ -1284,6 +1292,73 @@ def jpeg_tensor_codec(x, quality, want_bytes=False, tag=None):
         _check(lib().sc2_jpeg_tensor_codec(_ptr(x), B, C, H, W, quality, _ptr(recon), _ptr(meta[0]), _ptr(extrema), _ptr(meta[1]),
                                            _ptr(coded), slot, _stream()), 'jpeg_tensor_codec')
     return JpegCodecResult(recon, meta[0], meta[1], extrema, meta, coded, slot)
+
+
+# --------------------------------------------------------------------------------------------- #
+# codec input compression: 8-bit images through baseline JPEG at full image size (csrc/jpeg_image.hip)
+# --------------------------------------------------------------------------------------------- #
+JpegImageResult = collections.namedtuple('JpegImageResult', ['recon', 'sizes', 'bytes', 'slot_bytes'])
+_jpeg_image_ws = dict()        # (device index, stream, bytes) -> the coefficient workspace of sc2_jpeg_image_codec
+_JPEG_IMAGE_WS_KEPT = 4
+
+
+def jpeg_image_max_bytes(C, H, W):
+    """Upper bound of one image's entropy-coded segment (C: 1 grey, 3 RGB)."""
+    n = int(lib().sc2_jpeg_image_max_bytes(int(C), int(H), int(W)))
+    if n < 0:
+        raise Sc2Error('jpeg_image_max_bytes: {} channels at {}x{} (1 or 3 channels, sides 1..{})'.format(C, H, W, JPEG_IMAGE_MAX_SIDE))
+    return n
+
+
+def _jpeg_image_workspace(device, n_bytes):
+    """One workspace per (device, stream, size): the launches of a stream are ordered, so its next call may write where the last one
+    read.  The few most recent sizes are kept."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream, n_bytes)
+    ws = _jpeg_image_ws.pop(key, None)
+    if ws is None:
+        ws = torch.empty((n_bytes,), dtype=torch.uint8, device=device)
+    _jpeg_image_ws[key] = ws               # (most recent last)
+    while len(_jpeg_image_ws) > _JPEG_IMAGE_WS_KEPT:
+        _jpeg_image_ws.pop(next(iter(_jpeg_image_ws)))
+    return ws
+
+
+def jpeg_image_codec(x_u8, quality, want_bytes=False, tag=None):
+    """What the reference's `PILImageModule(format='JPEG', quality=quality)` computes for every image of x_u8 [B,C,H,W] (uint8 on the
+    device, C 3: RGB, 1: grey; any non-negative strides: the permuted view of an HWC stack is read in place; sides up to
+    JPEG_IMAGE_MAX_SIDE), in three launches (include/sc2_bottleneck.h: sc2_jpeg_image_codec).
+    -> JpegImageResult: recon uint8 [B,C,H,W] contiguous, the decoded pixels; sizes int32 [B], bytes of the complete file (header +
+    segment + EOI); bytes uint8 [B, slot_bytes] holding each image's entropy-coded segment (size - JPEG_HEADER_BYTES[mode] - 2 bytes
+    of it), or None."""
+    if not isinstance(x_u8, torch.Tensor) or not x_u8.is_cuda:
+        raise Sc2Error('jpeg_image_codec: x must be a tensor on a HIP device (got {}); there is no CPU fallback in this package'
+                       .format('device=' + str(x_u8.device) if isinstance(x_u8, torch.Tensor) else type(x_u8)))
+    if x_u8.dtype != torch.uint8:
+        raise Sc2Error('jpeg_image_codec: a uint8 tensor is required, got {}'.format(x_u8.dtype))
+    if x_u8.dim() != 4 or x_u8.numel() == 0:
+        raise Sc2Error('jpeg_image_codec: a non-empty [B,C,H,W] tensor is required, got shape {}'.format(tuple(x_u8.shape)))
+    B, C, H, W = (int(v) for v in x_u8.shape)
+    if C not in (1, 3):
+        raise Sc2Error('jpeg_image_codec: {} channels (1: grey, 3: RGB)'.format(C))
+    if H > JPEG_IMAGE_MAX_SIDE or W > JPEG_IMAGE_MAX_SIDE:
+        raise Sc2Error('jpeg_image_codec: {}x{} images (at most {} per side)'.format(H, W, JPEG_IMAGE_MAX_SIDE))
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise Sc2Error('jpeg_image_codec: quality {!r} (an integer in 1..100)'.format(quality))
+    x_u8 = x_u8.detach()
+    sb, sc, sh, sw = (int(v) for v in x_u8.stride())
+    dev = x_u8.device
+    recon = torch.empty((B, C, H, W), dtype=torch.uint8, device=dev)
+    sizes = torch.empty((B,), dtype=torch.int32, device=dev)
+    slot, coded = 0, None
+    if want_bytes:
+        slot = jpeg_image_max_bytes(C, H, W)
+        coded = torch.empty((B, slot), dtype=torch.uint8, device=dev)
+    ws_bytes = int(lib().sc2_jpeg_image_workspace_bytes(B, C, H, W))
+    ws = _jpeg_image_workspace(dev, ws_bytes)
+    with _timed(tag or 'jpeg_image_codec'):
+        _check(lib().sc2_jpeg_image_codec(_ptr(x_u8), sb, sc, sh, sw, B, C, H, W, quality, _ptr(recon), _ptr(sizes), _ptr(coded), slot,
+                                          _ptr(ws), ws_bytes, _stream()), 'jpeg_image_codec')
+    return JpegImageResult(recon, sizes, coded, slot)
 
 
 # --------------------------------------------------------------------------------------------- #

@@ -8,7 +8,9 @@ image; `config.resolve` maps `torchvision.transforms.<Name>` here).
   as is because the reported sizes and accuracies depend on it.  An f32 device tensor of at most 64 x 64 per channel with plain
   `format='JPEG'` (optional integer quality) runs on the library's kernel (csrc/jpeg.hip: one launch per batch, `forward_batch`),
   with the same features and sizes bit for bit; everything else goes through PIL as before.
-* `PILImageModule` -- codec.py:79-111.
+* `PILImageModule` -- codec.py:79-111.  `forward_batch(images, device)` sends a list of equal-size RGB / grey images with plain
+  `format='JPEG'` through the library's kernels at full image size (csrc/jpeg_image.hip, `hip.host_policy.jpeg_image_hip`), with
+  the same decoded pixels and file sizes bit for bit; everything else goes through PIL image by image.
 * `AdaptivePad` -- sc2bench/transforms/misc.py:105-154 (tests 'equal_side', otherwise pads right and bottom).
 * `Compose`, `Resize`, `CenterCrop`, `ToTensor`, `Normalize`, `RandomResizedCrop`, `RandomHorizontalFlip` -- torchvision
   semantics on PIL images / tensors, PIL + torch only.
@@ -70,8 +72,28 @@ def to_pil_image(pic):
     raise ValueError('to_pil_image: {} channels'.format(arr.shape[2]))
 
 
+_UNIT_TABLES = dict()       # device -> f32 [256]: v / 255 as the host divides
+
+
+def _u8_to_unit(pic):
+    """uint8 tensor -> float32 / 255 on its device, with the host's values: there `.to(float32).div(255)` is a correctly rounded
+    division, while torch's device kernel for a Python-scalar divisor multiplies by the reciprocal (one bit off for some of the 256
+    values); the 256 quotients therefore come from a table built on the host."""
+    if not pic.is_cuda:
+        return pic.to(torch.float32).div(255)
+    table = _UNIT_TABLES.get(pic.device)
+    if table is None:
+        with torch.inference_mode(False):
+            table = _UNIT_TABLES[pic.device] = torch.arange(256, dtype=torch.float32).div(255).to(pic.device)
+    return table[pic.to(torch.int32)]
+
+
 def to_tensor(pic):
-    """8-bit PIL image (or HWC uint8 ndarray) -> float CHW tensor / 255."""
+    """8-bit PIL image (or HWC uint8 ndarray) -> float CHW tensor / 255.  Beyond torchvision: a uint8 torch tensor [C,H,W] or
+    [B,C,H,W] on any device -- decoded pixels that are on the device already (`PILImageModule.forward_batch`) -- gives the values
+    of `.to(float32).div(255)` there, layout unchanged: the same as `to_tensor` of the PIL image of those pixels."""
+    if isinstance(pic, torch.Tensor) and pic.dtype == torch.uint8 and pic.dim() in (3, 4):
+        return _u8_to_unit(pic)
     arr = np.array(pic, copy=True)
     if arr.ndim == 2:
         arr = arr[:, :, None]
@@ -424,9 +446,23 @@ def _pil_codec_round_trip(pil_img, save_kwargs, open_kwargs):
     return Image.open(coded, **open_kwargs), n_bytes
 
 
+def _plain_jpeg_quality(save_kwargs, open_kwargs):
+    """The quality when `save_kwargs` / `open_kwargs` ask for nothing but `format='JPEG'` at an integer quality (Pillow's default
+    is 75) -- the one case the kernels restate --, else None: `optimize`, `subsampling`, `progressive`, other formats stay with PIL."""
+    kw = save_kwargs
+    if open_kwargs or set(kw) - {'format', 'quality'} or not isinstance(kw.get('format'), str) or kw['format'].upper() != 'JPEG':
+        return None
+    quality = kw.get('quality', 75)
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        return None
+    return quality
+
+
 @register_codec_transform_module
 class PILImageModule(nn.Module):
-    """Compresses (and reopens) a PIL image with a PIL codec (codec.py:79-111)."""
+    """Compresses (and reopens) a PIL image with a PIL codec (codec.py:79-111).  `forward_batch` takes a list of images: equal-size
+    RGB / grey ones with plain `format='JPEG'` go up in one copy and through the library's kernels (csrc/jpeg_image.hip) when
+    `hip.host_policy.jpeg_image_hip` is on, with the same pixels and sizes; everything else goes through PIL image by image."""
 
     def __init__(self, returns_file_size=False, open_kwargs=None, **save_kwargs):
         super().__init__()
@@ -437,6 +473,49 @@ class PILImageModule(nn.Module):
     def forward(self, pil_img, *args):
         decoded, n_bytes = _pil_codec_round_trip(pil_img, self.save_kwargs, self.open_kwargs)
         return (decoded, n_bytes) if self.returns_file_size else decoded
+
+    def _jpeg_quality(self):
+        """The gate in front of the kernel, shared with `PILTensorModule`: the quality of plain `format='JPEG'`, else None."""
+        return _plain_jpeg_quality(self.save_kwargs, self.open_kwargs)
+
+    def _kernel_quality(self, images, device):
+        """The quality when this list of PIL images goes to the kernel on `device`, else None: a HIP device, plain JPEG, one size and
+        one mode ('RGB' or 'L') for all, sides within the kernel's limit, and no image with a 'comment' in its `.info` -- Pillow's JPEG
+        writer copies that into a COM segment (ImageNet files carry such comments through convert / resize / crop), so such a batch
+        has to report Pillow's size."""
+        quality = self._jpeg_quality()
+        if quality is None or len(images) == 0 or torch.device(device).type != 'cuda':
+            return None
+        first = images[0]
+        if not _is_pil(first) or first.mode not in ('RGB', 'L'):
+            return None
+        for img in images:
+            if not _is_pil(img) or img.size != first.size or img.mode != first.mode or 'comment' in img.info:
+                return None
+        from . import hip
+        if not hip.host_policy.jpeg_image_hip or max(first.size) > hip.JPEG_IMAGE_MAX_SIDE or min(first.size) < 1:
+            return None
+        return quality
+
+    def forward_batch(self, images, device):
+        """images: list of PIL images -> (decoded, [file size of every image]): what `forward` (with `returns_file_size`) gives image
+        by image.  On the kernel path `decoded` is the uint8 device tensor [B,C,H,W] of the decoded pixels (one host-to-device copy of
+        the stacked images, one device-to-host read of the sizes), otherwise the list of reopened PIL images."""
+        quality = self._kernel_quality(images, device)
+        if quality is None:
+            pairs = [_pil_codec_round_trip(img, self.save_kwargs, self.open_kwargs) for img in images]
+            return [d for d, _ in pairs], [n for _, n in pairs]
+        from . import hip, jpeg_format
+        mode, (W, H) = images[0].mode, images[0].size
+        # (the kernel counts whole files; the header length it adds is the one Pillow writes at this size and quality)
+        kernel_mode = hip.JPEG_RGB if mode == 'RGB' else hip.JPEG_GREY
+        if jpeg_format.checked_header_bytes(mode, H, W, quality) != hip.JPEG_HEADER_BYTES[kernel_mode]:
+            raise hip.Sc2Error('jpeg header of {} bytes expected for mode {}'.format(hip.JPEG_HEADER_BYTES[kernel_mode], mode))
+        stacked = torch.from_numpy(np.stack([np.asarray(img) for img in images]))              # [B,H,W,3] or [B,H,W]
+        stacked = stacked.to(device, non_blocking=True)
+        x = stacked.permute(0, 3, 1, 2) if mode == 'RGB' else stacked.unsqueeze(1)             # read in place: no layout pass
+        res = hip.jpeg_image_codec(x, quality)
+        return res.recon, res.sizes.cpu().tolist()
 
     def __repr__(self):
         return self.__class__.__name__ + '(returns_file_size={}, open_kwargs={}, save_kwargs={})'.format(
@@ -487,15 +566,8 @@ class PILTensorModule(nn.Module):
     _side_info_cache = dict()
 
     def _jpeg_quality(self):
-        """The quality when `save_kwargs` / `open_kwargs` ask for nothing but `format='JPEG'` at an integer quality (Pillow's default
-        is 75) -- the one case the kernel restates --, else None: `optimize`, `subsampling`, `progressive`, other formats stay with PIL."""
-        kw = self.save_kwargs
-        if self.open_kwargs or set(kw) - {'format', 'quality'} or not isinstance(kw.get('format'), str) or kw['format'].upper() != 'JPEG':
-            return None
-        quality = kw.get('quality', 75)
-        if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
-            return None
-        return quality
+        """The gate in front of the kernel, shared with `PILImageModule`: the quality of plain `format='JPEG'`, else None."""
+        return _plain_jpeg_quality(self.save_kwargs, self.open_kwargs)
 
     def _kernel_quality(self, x):
         """The quality when x [..., C,H,W] goes to the kernel, else None."""

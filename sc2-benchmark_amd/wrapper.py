@@ -20,7 +20,7 @@ from .analysis import AnalyzableModule
 from .backbone import UpdatableBackbone
 from .layer import EntropyBottleneckLayer
 from .training import redesign_model
-from .transforms import Compose
+from .transforms import Compose, Normalize, PILImageModule, ToTensor, _is_pil
 
 WRAPPER_CLASS_DICT = dict()
 
@@ -43,20 +43,65 @@ def _analyzer_configs(analysis_config):
 
 
 class _PerSampleCodec(object):
-    """codec -> analyze(file size) -> post_transform for every sample of a batch, joined as the reference joins them."""
+    """codec -> analyze(file size) -> post_transform for every sample of a batch, joined as the reference joins them.  Three forms
+    with one result: the loop; a 4-D tensor through `PILTensorModule.forward_batch`; a list of PIL images through
+    `PILImageModule.forward_batch`."""
 
     def _batch_codec(self):
-        """The codec when it takes a whole batch (`forward_batch` of transforms.PILTensorModule, alone or as the one transform of a
-        `Compose`) and reports sizes, else None."""
+        """The codec when it takes a whole batch (`forward_batch` of transforms.PILTensorModule or PILImageModule, alone or as the one
+        transform of a `Compose`) and reports sizes, else None."""
         codec = self.codec_encoder_decoder
         if isinstance(codec, Compose) and len(codec.transforms) == 1:
             codec = codec.transforms[0]
         return codec if hasattr(codec, 'forward_batch') and getattr(codec, 'returns_file_size', False) else None
 
+    def _image_batch_codec(self, samples):
+        """The codec when `samples` is a list of PIL images, the codec a size-reporting `transforms.PILImageModule` (alone or as the
+        one transform of a `Compose`) and the post_transform one that takes the decoded pixels as a uint8 batch tensor: its
+        `forward_batch` takes the whole list.  Else None: any other post_transform (a `Resize` first, a callable of the caller's)
+        expects the reopened PIL image of the loop, so the decision is made before anything is launched."""
+        if not isinstance(samples, (list, tuple)) or len(samples) == 0 or not all(_is_pil(sample) for sample in samples):
+            return None
+        if not self._post_transform_takes_batches():
+            return None
+        codec = self._batch_codec()
+        return codec if isinstance(codec, PILImageModule) else None
+
+    def _post_transform_takes_batches(self):
+        """None, or a `Compose` of exactly `ToTensor` followed by at most one `Normalize`: element-wise on uint8 pixels, so one call on
+        the decoded batch [B,C,H,W] gives what the calls on its samples give."""
+        post = self.post_transform
+        if post is None:
+            return True
+        if not isinstance(post, Compose) or not 1 <= len(post.transforms) <= 2 or type(post.transforms[0]) is not ToTensor:
+            return False
+        return len(post.transforms) == 1 or type(post.transforms[1]) is Normalize
+
+    def _through_image_batch(self, codec, samples):
+        decoded, sizes = codec.forward_batch(list(samples), self.device)
+        if isinstance(decoded, torch.Tensor):      # the kernel path: uint8 [B,C,H,W] on the device
+            if not self.training:
+                for file_size in sizes:
+                    self.analyze(file_size)
+            batch = decoded if self.post_transform is None else self.post_transform(decoded)
+            # the loop joins its [1,C,H,W] samples with torch.hstack, i.e. along dim 1: [1, B*C, H, W]
+            return batch.reshape(1, -1, batch.shape[-2], batch.shape[-1]).to(self.device)
+        outputs = []                               # the codec's host path: the reopened PIL images, as in the loop
+        for sample, file_size in zip(decoded, sizes):
+            if not self.training:
+                self.analyze(file_size)
+            if self.post_transform is not None:
+                sample = self.post_transform(sample)
+            outputs.append(sample.unsqueeze(0))
+        return torch.hstack(outputs).to(self.device)
+
     def _through_codec(self, samples):
+        codec = self._image_batch_codec(samples)
+        if codec is not None:
+            return self._through_image_batch(codec, samples)
         outputs = []
         codec = self._batch_codec() if isinstance(samples, torch.Tensor) and samples.dim() == 4 else None
-        if codec is not None:
+        if codec is not None and not isinstance(codec, PILImageModule):
             features, sizes = codec.forward_batch(samples)
             for sample, file_size in zip(features, sizes):
                 if not self.training:
