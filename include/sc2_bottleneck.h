@@ -1034,6 +1034,37 @@ int sc2_jpeg_image_codec(const uint8_t *x, long long sb, long long sc, long long
                          void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* The detection transform around the image codec (csrc/rcnn_input.hip): what the reference's                               */
+/* RCNNTransformWithCompression does per image in front of and behind PILImageModule(format='JPEG') -- bilinear resize and  */
+/* `mul(255).byte()`, then `/ 255`, normalise and the copy into the zero-padded batch.  tests/ref_rcnn_input.py restates    */
+/* both.  Streaming kernels, one launch each on `stream`; no LDS, no atomics, nothing is copied to the host.                */
+/* ------------------------------------------------------------------------------------------ */
+/* x: f32, element [c,y,x] at x + c*sc + y*sh + x*sw (non-negative element strides: a CHW tensor and the permuted view of an HWC one
+ * are read in place), 4-byte aligned.  C in {1, 3}; H, W, oh, ow in 1..SC2_JPEG_IMAGE_MAX_SIDE (SC2_ERR_UNSUPPORTED for another C or
+ * side; SC2_ERR_INVALID_ARG for a NULL or misaligned pointer, a negative stride).  oh, ow are the caller's: what
+ * GeneralizedRCNNTransform.resized_size returns.
+ * out: u8 [C,oh,ow] contiguous, any alignment.  Bilinear, align_corners=False, no antialiasing, as aten's upsample_bilinear2d computes
+ *   it in f32 when no scale factor is handed down (F.interpolate(..., recompute_scale_factor=True)), every operation rounded once:
+ *     scale = in / out;  src = max(scale * (d + 0.5) - 0.5, 0);  i0 = min(int(src), in - 1);  i1 = min(i0 + 1, in - 1);
+ *     l1 = src - i0;  l0 = 1 - l1;  v = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d);  byte = (uint8) trunc(v * 255.0f)
+ *   One lane produces four adjacent pixels of a row (one 4-byte store where the address allows, else two 2-byte or four 1-byte ones)
+ *   and reuses its column indices and weights over four rows; one workgroup per (channel, 16 rows, 256 columns).
+ * status: i32 [1], 4-byte aligned, CLEARED BY THE CALLER before the launch: set to 1 (a plain store) by every lane that reads a NaN or
+ *   a value outside [0, 1] -- there the host's `mul(255).byte()` wraps, which the kernel does not imitate: the bytes computed from such
+ *   a value are unspecified (never a fault), the caller redoes the image on the host. */
+int sc2_rcnn_resize_u8(const float *x, long long sc, long long sh, long long sw, int C, int H, int W, uint8_t *out, int oh, int ow,
+                       int32_t *status, void *stream);
+/* pixels: u8 [C,h,w] contiguous (sc2_jpeg_image_codec's recon), any alignment; C in {1, 3}, h and w in 1..SC2_JPEG_IMAGE_MAX_SIDE.
+ * mean, std: C floats each ON THE HOST (read before the call returns).
+ * out: f32 [C,Hp,Wp] contiguous, 4-byte aligned -- one image's slot of the batch tensor --, h <= Hp, w <= Wp (SC2_ERR_INVALID_ARG
+ *   otherwise), Hp and Wp at most 4 * SC2_JPEG_IMAGE_MAX_SIDE (SC2_ERR_UNSUPPORTED beyond).  Inside the image
+ *   fl(fl(fl(p / 255) - mean[c]) / std[c]), both divisions IEEE correctly rounded, nothing contracted: the host's
+ *   `(to_tensor(u8) - mean) / std`; outside +0.0.  EVERY element of the slot is written: the caller clears nothing.  A lane loads four
+ *   pixels and stores 16 bytes where the addresses allow, else element by element. */
+int sc2_rcnn_normalize_pad(const uint8_t *pixels, int C, int h, int w, const float *mean, const float *std, float *out, int Hp, int Wp,
+                           void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Diagnostics (csrc/diag.hip; no product path calls these).                                    */
 /* ------------------------------------------------------------------------------------------ */
 /* The shader clock the chip holds while OTHER kernels run: `n_workgroups` probe waves (one per workgroup; launch >= 8 so that

@@ -24,11 +24,15 @@ from .entropy import GDN  # noqa: F401
 from .transforms import (AdaptivePad, PILImageModule, PILTensorModule, QuantizedTensor, SimpleDequantizer,  # noqa: F401
                          SimpleQuantizer, cat_list, coco_collate_fn, dequantize_tensor, pascal_seg_collate_fn, pascal_seg_eval_collate_fn,
                          quantize_tensor)
+from .detection import RCNNTransformWithCompression  # noqa: F401
 from .wrapper import (WRAPPER_CLASS_DICT, CodecFeatureCompressionClassifier, CodecInputCompressionClassifier,  # noqa: F401
-                      EntropicClassifier, NeuralInputCompressionClassifier, SplitClassifier, wrap_model)
+                      CodecInputCompressionSegmentationModel, EntropicClassifier, InputCompressionDetectionModel,
+                      NeuralInputCompressionClassifier, SplitClassifier, get_wrapped_detection_model,
+                      get_wrapped_segmentation_model, load_detection_model, load_segmentation_model, wrap_model)
 
 from .dense import (DETECTION_MODEL_FUNC_DICT, SEGMENTATION_MODEL_FUNC_DICT, BaseRCNN, BaseSegmentationModel,  # noqa: F401
-                    SegEvaluator, UpdatableBackboneWithFPN, backbone_with_fpn, deeplabv3_model, faster_rcnn_model, seg_labels)
+                    SegEvaluator, UpdatableBackboneWithFPN, backbone_with_fpn, deeplabv3_model, deeplabv3_resnet50,
+                    faster_rcnn_model, fasterrcnn_resnet50_fpn, seg_labels)
 
 from .coco_eval import CocoBoxEvaluator, CocoDictDetection, coco_gt_from_dataset  # noqa: F401
 from .pipeline import StagePipeline, supports_stages  # noqa: F401

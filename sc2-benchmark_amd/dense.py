@@ -13,6 +13,10 @@ paths `backbone.body.bottleneck_layer` / `backbone.bottleneck_layer`, update / a
   and the image-list transform are torchvision's `FasterRCNN` when torchvision is importable; without it they are
   `detection.FasterRCNN`, this package's restatement of the inference path (NMS and RoIAlign on csrc/detect.hip).
 
+* `fasterrcnn_resnet50_fpn`, `deeplabv3_resnet50`: torchvision's plain models (no bottleneck) under the same registries -- the
+  task models of the input-compression baselines (`wrapper.InputCompressionDetectionModel`,
+  `wrapper.CodecInputCompressionSegmentationModel`).
+
 These heads run on torch ops (MIOpen) in f32 or bf16; the bottleneck and the undilated ResNet stacks under them run on
 the HIP library (`FeatureExtractionBackbone.set_compute_dtype('bf16')`).
 """
@@ -455,6 +459,33 @@ def faster_rcnn_model(backbone_config, pretrained=True, pretrained_backbone_name
     return model
 
 
+def _no_pretrained(name, start_ckpt_file_path):
+    if start_ckpt_file_path is None:
+        import logging
+        logging.getLogger(__name__).warning('{}: pretrained weights are a download upstream; pass start_ckpt_file_path to load a '
+                                            'local checkpoint'.format(name))
+
+
+@register_detection_model_func
+def fasterrcnn_resnet50_fpn(pretrained=False, progress=True, num_classes=91, start_ckpt_file_path=None, **kwargs):
+    """torchvision's `fasterrcnn_resnet50_fpn` (the detector of the input-compression baselines): a plain ResNet-50 with
+    FrozenBatchNorm2d under the feature pyramid, `FasterRCNN` from torchvision where it is importable, else `detection.FasterRCNN`
+    (inference only).  State-dict names are torchvision's (`backbone.body.*`, `backbone.fpn.*`, `rpn.*`, `roi_heads.*`)."""
+    from .resnet import resnet50
+    bfpn = backbone_with_fpn(resnet50(norm_layer=FrozenBatchNorm2d))
+    try:
+        from torchvision.models.detection.faster_rcnn import FasterRCNN
+    except ImportError:
+        from .detection import FasterRCNN
+    model = FasterRCNN(bfpn, num_classes, **kwargs)
+    if pretrained:
+        _no_pretrained('fasterrcnn_resnet50_fpn', start_ckpt_file_path)
+    if start_ckpt_file_path is not None:
+        from .ckpt import load_ckpt
+        load_ckpt(start_ckpt_file_path, model=model, strict=False)
+    return model
+
+
 # ------------------------------------------------------------------------------------------------ segmentation
 class BaseSegmentationModel(_UpdatableDenseModel):
     """backbone features -> classifier (-> aux classifier), bilinearly resized to the input (segmentation/base.py:42-81)."""
@@ -524,6 +555,26 @@ def deeplabv3_model(backbone_config, pretrained=True, pretrained_backbone_name=N
         import logging
         logging.getLogger(__name__).warning('deeplabv3_model: pretrained COCO weights are a download upstream; pass '
                                             'start_ckpt_file_path to load a local checkpoint')
+    if start_ckpt_file_path is not None:
+        from .ckpt import load_ckpt
+        load_ckpt(start_ckpt_file_path, model=model, strict=False)
+    return model
+
+
+@register_segmentation_model_func
+def deeplabv3_resnet50(pretrained=False, progress=True, num_classes=21, aux_loss=None, start_ckpt_file_path=None, **kwargs):
+    """torchvision's `deeplabv3_resnet50` (the segmentation model of the input-compression baselines): a plain ResNet-50 with
+    dilated layer3 / layer4, `DeepLabHead`, and the `FCNHead` aux classifier with `aux_loss`.  State-dict names are torchvision's
+    (`backbone.*`, `classifier.*`, `aux_classifier.*`)."""
+    from .resnet import resnet50
+    backbone = resnet50(replace_stride_with_dilation=[False, True, True])
+    return_layer_dict = {'layer4': 'out'}
+    if aux_loss:
+        return_layer_dict['layer3'] = 'aux'
+    body = FeatureExtractionBackbone(backbone, return_layer_dict, list())
+    model = create_deeplabv3(body, uses_aux=bool(aux_loss), num_classes=num_classes)
+    if pretrained:
+        _no_pretrained('deeplabv3_resnet50', start_ckpt_file_path)
     if start_ckpt_file_path is not None:
         from .ckpt import load_ckpt
         load_ckpt(start_ckpt_file_path, model=model, strict=False)

@@ -12,6 +12,9 @@ non-maximum suppression (`nms`, `batched_nms` -> `hip.batched_nms`) and RoIAlign
 torch-op implementation of the same definitions (include/sc2_bottleneck.h states them; tests/ref_detection.py restates
 them independently).  Everything else is small tensor algebra and two small GEMM stacks on torch ops.
 
+`RCNNTransformWithCompression` (sc2bench/models/detection/transform.py) is the transform of the input-compression baseline: a
+codec between resize and normalise; for plain JPEG on device images it runs on csrc/rcnn_input.hip + csrc/jpeg_image.hip.
+
 Training of the RPN / RoI heads (matcher, samplers, losses) is not built: both modules raise NotImplementedError in
 training mode.
 """
@@ -23,6 +26,8 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import hip
+from .analysis import AnalyzableModule
+from .transforms import AdaptivePad, Compose, PILImageModule, to_pil_image, to_tensor
 
 BBOX_XFORM_CLIP = math.log(1000.0 / 16)
 
@@ -567,6 +572,151 @@ class GeneralizedRCNNTransform(nn.Module):
         for i, (pred, im_s, o_im_s) in enumerate(zip(result, image_shapes, original_image_sizes)):
             result[i]['boxes'] = resize_boxes(pred['boxes'], im_s, o_im_s)
         return result
+
+
+class RCNNTransformWithCompression(GeneralizedRCNNTransform, AnalyzableModule):
+    """The R-CNN transform with a codec (or a compression model) between resize and normalise
+    (sc2bench/models/detection/transform.py): per image resize -> compress -> normalise, then the zero-padded batch.  The file size
+    (codec) or the compressed object (model) of every image goes to the analyzers in eval mode.
+
+    `forward` has two forms with one result.  The HOST path is the reference's loop and is always available.  The KERNEL path
+    (`_kernel_plan`: eval mode, `hip.host_policy.rcnn_input_hip` and `jpeg_image_hip` on, no compression model, no pre / post
+    transform, a size-reporting `PILImageModule` with plain JPEG, 3-channel float32 device images whose sides stay within the
+    codec's limit) runs `hip.rcnn_resize_u8` -> `hip.jpeg_image_codec` -> `hip.rcnn_normalize_pad` per image straight into the
+    batch tensor, and reads the file sizes and the status words of all images back ONCE behind the last launch; an image whose
+    status is set (a NaN or a value outside [0, 1], where `mul(255).byte()` wraps) is redone on the host path."""
+
+    def __init__(self, transform, device, codec_encoder_decoder, analyzer_configs, analyzes_after_compress=False,
+                 compression_model=None, uses_cpu4compression_model=False, pre_transform=None, post_transform=None,
+                 adaptive_pad_kwargs=None):
+        GeneralizedRCNNTransform.__init__(self, transform.min_size, transform.max_size, transform.image_mean, transform.image_std)
+        AnalyzableModule.__init__(self, analyzer_configs)
+        self.device = device
+        self.codec_encoder_decoder = codec_encoder_decoder
+        self.analyzes_after_compress = analyzes_after_compress
+        self.pre_transform = pre_transform
+        self.post_transform = post_transform
+        if uses_cpu4compression_model and compression_model is not None:
+            compression_model = compression_model.cpu()
+        self.compression_model = compression_model
+        self.uses_cpu4compression_model = uses_cpu4compression_model
+        self.adaptive_pad = AdaptivePad(**adaptive_pad_kwargs) if isinstance(adaptive_pad_kwargs, dict) else None
+
+    def compress_by_codec(self, org_img):
+        pil_img, file_size = self.codec_encoder_decoder(to_pil_image(org_img))
+        if not self.training:
+            self.analyze(file_size)
+        return to_tensor(pil_img).to(org_img.device)
+
+    def compress_by_model(self, org_img):
+        org_img = org_img.unsqueeze(0)
+        org_height, org_width = None, None
+        if self.adaptive_pad is not None:
+            org_height, org_width = org_img.shape[-2:]
+            org_img = self.adaptive_pad(org_img)
+        compressed_obj = self.compression_model.compress(org_img)
+        if not self.training and self.analyzes_after_compress:
+            self.analyze(compressed_obj if org_height is None or org_width is None else (compressed_obj, org_height, org_width))
+        decompressed = self.compression_model.decompress(**compressed_obj)['x_hat']
+        if org_height is not None and org_width is not None:
+            decompressed = decompressed[..., :org_height, :org_width]
+        return decompressed.squeeze(0)
+
+    def compress(self, org_img):
+        if self.pre_transform is not None:
+            org_img = self.pre_transform(org_img)
+        org_device = org_img.device
+        if self.uses_cpu4compression_model:
+            org_img = org_img.cpu()
+        org_img = self.compress_by_codec(org_img) if self.compression_model is None else self.compress_by_model(org_img)
+        if self.uses_cpu4compression_model:
+            org_img = org_img.to(org_device)
+        if self.post_transform is not None:
+            org_img = self.post_transform(org_img)
+        return org_img
+
+    def _host_image(self, image, target):
+        """one image of the host path: -> (resized, compressed, normalised image, target with resized boxes)"""
+        image, target = self.resize(image, target)
+        shape_before_compression = image.shape
+        image = self.compress(image)
+        assert image.shape == shape_before_compression, \
+            'Compression should not change tensor shape {} -> {}'.format(shape_before_compression, image.shape)
+        return self.normalize(image), target
+
+    def _kernel_plan(self, images):
+        """(JPEG quality, [(oh, ow) of every image]) when this list takes the kernel path, else None.  Decided before anything is
+        launched: the path is one for the whole list."""
+        if self.training or not (hip.host_policy.rcnn_input_hip and hip.host_policy.jpeg_image_hip):
+            return None
+        if self.compression_model is not None or self.pre_transform is not None or self.post_transform is not None:
+            return None
+        if self.fixed_size is not None or len(images) == 0:
+            return None
+        codec = self.codec_encoder_decoder
+        if isinstance(codec, Compose) and len(codec.transforms) == 1:
+            codec = codec.transforms[0]
+        if not isinstance(codec, PILImageModule) or not codec.returns_file_size:
+            return None
+        quality = codec._jpeg_quality()
+        if quality is None:
+            return None
+        sizes = []
+        for image in images:
+            if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dtype == torch.float32 and image.dim() == 3 and
+                    image.shape[0] == 3 and image.device == images[0].device and min(image.shape[-2:]) >= 1):
+                return None
+            oh, ow = self.resized_size(int(image.shape[-2]), int(image.shape[-1]))
+            if max(oh, ow, int(image.shape[-2]), int(image.shape[-1])) > hip.JPEG_IMAGE_MAX_SIDE or min(oh, ow) < 1:
+                return None
+            sizes.append((oh, ow))
+        return quality, sizes
+
+    def _forward_kernels(self, images, targets, quality, sizes):
+        from . import jpeg_format
+        for oh, ow in set(sizes):      # (the kernel counts whole files; the header length it adds is the one Pillow writes)
+            if jpeg_format.checked_header_bytes('RGB', oh, ow, quality) != hip.JPEG_HEADER_BYTES[hip.JPEG_RGB]:
+                raise hip.Sc2Error('jpeg header of {} bytes expected for mode RGB'.format(hip.JPEG_HEADER_BYTES[hip.JPEG_RGB]))
+        dev, n = images[0].device, len(images)
+        stride = float(self.size_divisible)
+        max_h = int(math.ceil(max(s[0] for s in sizes) / stride) * stride)
+        max_w = int(math.ceil(max(s[1] for s in sizes) / stride) * stride)
+        batched = torch.empty((n, 3, max_h, max_w), dtype=torch.float32, device=dev)      # every element is written by the kernel
+        status = torch.zeros((n,), dtype=torch.int32, device=dev)
+        file_sizes = []
+        for i, (image, (oh, ow)) in enumerate(zip(images, sizes)):
+            pixels, _ = hip.rcnn_resize_u8(image, oh, ow, status=status[i:i + 1])
+            coded = hip.jpeg_image_codec(pixels.unsqueeze(0), quality)
+            file_sizes.append(coded.sizes)
+            hip.rcnn_normalize_pad(coded.recon[0], self.image_mean, self.image_std, batched[i])
+            if targets is not None and 'boxes' in targets[i]:
+                targets[i] = dict(targets[i], boxes=resize_boxes(targets[i]['boxes'], tuple(image.shape[-2:]), (oh, ow)))
+        back = torch.cat(file_sizes + [status]).cpu().tolist()      # the one read-back of the list
+        for i, (file_size, flagged) in enumerate(zip(back[:n], back[n:])):      # analysed in image order
+            if flagged:      # out of [0, 1]: what the host computes there (the bytes wrap) is the result
+                image, _ = self._host_image(images[i], None)
+                batched[i].zero_()
+                batched[i, :, :image.shape[-2], :image.shape[-1]].copy_(image)
+            else:
+                self.analyze(file_size)
+        return ImageList(batched, [(int(oh), int(ow)) for oh, ow in sizes]), targets
+
+    def forward(self, images, targets=None):
+        images = [img for img in images]
+        targets = [dict(t) for t in targets] if targets is not None else None
+        for image in images:
+            if image.dim() != 3:
+                raise ValueError('images is expected to be a list of 3d tensors of shape [C, H, W], got {}'.format(tuple(image.shape)))
+        plan = self._kernel_plan(images)
+        if plan is not None:
+            return self._forward_kernels(images, targets, *plan)
+        for i, image in enumerate(images):
+            image, target = self._host_image(image, targets[i] if targets is not None else None)
+            images[i] = image
+            if targets is not None and target is not None:
+                targets[i] = target
+        image_sizes = [(int(img.shape[-2]), int(img.shape[-1])) for img in images]
+        return ImageList(self.batch_images(images), image_sizes), targets
 
 
 class FasterRCNN(nn.Module):

@@ -255,7 +255,10 @@ def _evaluate_detection(model, data_loader, device, evaluator, max_samples, log_
     analysis = []
     if analyzable and model.activated_analysis:
         model.summarize()
-        analysis = [a.summary() for a in model.analyzers if hasattr(a, 'summary') and getattr(a, 'file_size_list', None)]
+        # (an InputCompressionDetectionModel's analyzers are those of its transform)
+        transform = getattr(getattr(model, 'detection_model', None), 'transform', None)
+        analyzers = list(model.analyzers) + list(transform.analyzers if isinstance(transform, AnalyzableModule) else ())
+        analysis = [a.summary() for a in analyzers if hasattr(a, 'summary') and getattr(a, 'file_size_list', None)]
     stats = evaluator.coco_eval[evaluator.iou_types[0]].stats
     return {'map': float(stats[0]), 'stats': stats.tolist(), 'summary': printed.getvalue(), 'samples': seen, 'seconds': time.perf_counter() - t0,
             'analysis': analysis, 'evaluator': evaluator}
@@ -313,6 +316,14 @@ def test_only(config, device, max_samples=None, num_workers=None):
         num_classes = ((model_config.get('kwargs') or {}).get('num_classes') or config['test'].get('num_classes') or
                        _classifier_classes(model))
         return evaluate_segmentation(model, loader, device, num_classes, max_samples=max_samples, title='[Student/model]')
+    from .wrapper import CodecInputCompressionSegmentationModel, InputCompressionDetectionModel
+    if isinstance(model, CodecInputCompressionSegmentationModel):      # the codec baseline: the class count is the inner model's
+        inner = model.segmentation_model
+        num_classes = (((model_config.get('segmentation_model') or {}).get('kwargs') or {}).get('num_classes') or
+                       config['test'].get('num_classes') or _classifier_classes(inner))
+        return evaluate_segmentation(model, loader, device, num_classes, max_samples=max_samples, title='[Student/model]')
+    if isinstance(model, InputCompressionDetectionModel):
+        return evaluate_detection(model, loader, device, max_samples=max_samples, title='[Student/model]')
     from .dense import BaseRCNN
     from .detection import FasterRCNN
     if isinstance(model, (FasterRCNN, BaseRCNN)):

@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
     'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_seg_predict', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
     'sc2_jpeg_max_bytes', 'sc2_jpeg_tensor_codec', 'sc2_jpeg_image_max_bytes', 'sc2_jpeg_image_workspace_bytes', 'sc2_jpeg_image_codec',
+    'sc2_rcnn_resize_u8', 'sc2_rcnn_normalize_pad',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
 ]
 
@@ -149,6 +150,7 @@ class HostPolicy(object):
     coco_eval_hip = True       # coco_eval.CocoBoxEvaluator.accumulate of device tensors on sc2_coco_match + sc2_coco_accumulate (False: the torch / numpy host path of the same module; tools/coco_eval_times.py)
     jpeg_codec_hip = True      # transforms.PILTensorModule(format='JPEG') of f32 device tensors up to 64 x 64 on sc2_jpeg_tensor_codec (False: PIL per channel group on the host, A/B; tools/jpeg_codec_times.py: 0.36 against 42.7 ms at [1,512,28,28])
     jpeg_image_hip = True      # transforms.PILImageModule(format='JPEG').forward_batch of equal-size RGB / grey PIL images up to 2048 x 2048 on sc2_jpeg_image_codec (False: PIL per image on the host, A/B; tools/jpeg_image_times.py, codec + ToTensor + Normalize to the classifier input: 0.39 against 0.50 ms at [1,3,224,224], 10.4 against 174 ms at [256,3,224,224])
+    rcnn_input_hip = True      # detection.RCNNTransformWithCompression (eval, plain JPEG, f32 RGB device images): resize -> codec -> normalise + pad per image on sc2_rcnn_resize_u8 + sc2_jpeg_image_codec + sc2_rcnn_normalize_pad, one read-back per list (False: the reference's loop through Pillow on the host, A/B; tools/rcnn_input_times.py, 480 x 640 -> 800 x 1066 at quality 90: 2.79 against 25.7 ms at one image per call, 16.0 against 88.3 ms at six; the two new kernels alone 0.009 ms each, the codec 2.63 ms)
     seg_predict_hip = True     # dense.seg_labels (BaseSegmentationModel.predict, SegEvaluator.update_logits) of device tensors on sc2_seg_predict (False: interpolate + argmax + bincount, A/B)
 
 
@@ -334,6 +336,8 @@ def lib():
     L.sc2_jpeg_image_workspace_bytes.argtypes = [i32, i32, i32, i32]
     L.sc2_jpeg_image_workspace_bytes.restype = i64
     L.sc2_jpeg_image_codec.argtypes = [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, i64, vp]
+    L.sc2_rcnn_resize_u8.argtypes = [vp, i64, i64, i64, i32, i32, i32, vp, i32, i32, vp, vp]
+    L.sc2_rcnn_normalize_pad.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp]
     L.sc2_rans_host_tables_create.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp)]
     L.sc2_rans_host_tables_destroy.argtypes = [vp]
     L.sc2_rans_host_tables_destroy.restype = None
@@ -1359,6 +1363,63 @@ def jpeg_image_codec(x_u8, quality, want_bytes=False, tag=None):
         _check(lib().sc2_jpeg_image_codec(_ptr(x_u8), sb, sc, sh, sw, B, C, H, W, quality, _ptr(recon), _ptr(sizes), _ptr(coded), slot,
                                           _ptr(ws), ws_bytes, _stream()), 'jpeg_image_codec')
     return JpegImageResult(recon, sizes, coded, slot)
+
+
+# --------------------------------------------------------------------------------------------- #
+# the detection transform around the image codec (csrc/rcnn_input.hip)
+# --------------------------------------------------------------------------------------------- #
+def rcnn_resize_u8(image, oh, ow, out=None, status=None, tag=None):
+    """f32 image [C,H,W] on the device (C 1 or 3, any non-negative strides, values in [0, 1]) -> (uint8 [C,oh,ow], status int32 [1]):
+    `F.interpolate(image[None], ..., mode='bilinear', align_corners=False)[0].mul(255).byte()` at the size (oh, ow) in one launch
+    (include/sc2_bottleneck.h: sc2_rcnn_resize_u8).  status is non-zero when the kernel read a NaN or a value outside [0, 1]: the
+    bytes are then unspecified.  `out`: a contiguous uint8 [C,oh,ow] tensor to write; `status`: an int32 tensor of one element the
+    caller has CLEARED (e.g. one element of a zeroed vector that is read back once for many images)."""
+    _dev(image, 'rcnn_resize_u8: image')
+    if image.dtype != torch.float32 or image.dim() != 3:
+        raise Sc2Error('rcnn_resize_u8: a float32 [C,H,W] tensor is required, got {} {}'.format(image.dtype, tuple(image.shape)))
+    C, H, W = (int(v) for v in image.shape)
+    oh, ow = int(oh), int(ow)
+    if C not in (1, 3):
+        raise Sc2Error('rcnn_resize_u8: {} channels (1 or 3)'.format(C))
+    if not (1 <= min(H, W, oh, ow) and max(H, W, oh, ow) <= JPEG_IMAGE_MAX_SIDE):
+        raise Sc2Error('rcnn_resize_u8: {}x{} -> {}x{} (sides 1..{})'.format(H, W, oh, ow, JPEG_IMAGE_MAX_SIDE))
+    image = image.detach()
+    dev = image.device
+    if out is None:
+        out = torch.empty((C, oh, ow), dtype=torch.uint8, device=dev)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (C, oh, ow) or not out.is_contiguous() or out.device != dev:
+        raise ValueError('rcnn_resize_u8: out must be a contiguous uint8 tensor of shape {} on {}'.format((C, oh, ow), dev))
+    if status is None:
+        status = torch.zeros((1,), dtype=torch.int32, device=dev)
+    elif status.dtype != torch.int32 or status.numel() != 1 or status.device != dev:
+        raise ValueError('rcnn_resize_u8: status must be an int32 tensor of one element on {}'.format(dev))
+    sc, sh, sw = (int(v) for v in image.stride())
+    with _timed(tag or 'rcnn_resize_u8'):
+        _check(lib().sc2_rcnn_resize_u8(_ptr(image), sc, sh, sw, C, H, W, _ptr(out), oh, ow, _ptr(status), _stream()), 'rcnn_resize_u8')
+    return out, status
+
+
+def rcnn_normalize_pad(pixels_u8, mean, std, out_slot, tag=None):
+    """uint8 pixels [C,h,w] on the device (contiguous: the codec's recon) -> out_slot f32 [C,Hp,Wp] (contiguous, Hp >= h, Wp >= w: one
+    image's slot of the batch tensor): `(to_tensor(pixels) - mean) / std` inside the image, +0.0 outside, every element of the slot
+    written, in one launch (include/sc2_bottleneck.h: sc2_rcnn_normalize_pad).  mean, std: C numbers.  -> out_slot."""
+    _dev(pixels_u8, 'rcnn_normalize_pad: pixels')
+    _dev(out_slot, 'rcnn_normalize_pad: out_slot')
+    if pixels_u8.dtype != torch.uint8 or pixels_u8.dim() != 3 or not pixels_u8.is_contiguous():
+        raise Sc2Error('rcnn_normalize_pad: a contiguous uint8 [C,h,w] tensor is required, got {} {}'.format(pixels_u8.dtype, tuple(pixels_u8.shape)))
+    C, h, w = (int(v) for v in pixels_u8.shape)
+    if out_slot.dtype != torch.float32 or out_slot.dim() != 3 or out_slot.shape[0] != C or not out_slot.is_contiguous() or \
+            out_slot.device != pixels_u8.device:
+        raise Sc2Error('rcnn_normalize_pad: out_slot must be a contiguous float32 [{},Hp,Wp] tensor on {}, got {} {}'.format(
+            C, pixels_u8.device, out_slot.dtype, tuple(out_slot.shape)))
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != C or len(std) != C:
+        raise ValueError('rcnn_normalize_pad: {} mean and {} std values for {} channels'.format(len(mean), len(std), C))
+    Hp, Wp = int(out_slot.shape[1]), int(out_slot.shape[2])
+    fm, fs = (ctypes.c_float * C)(*mean), (ctypes.c_float * C)(*std)
+    with _timed(tag or 'rcnn_normalize_pad'):
+        _check(lib().sc2_rcnn_normalize_pad(_ptr(pixels_u8), C, h, w, fm, fs, _ptr(out_slot.detach()), Hp, Wp, _stream()), 'rcnn_normalize_pad')
+    return out_slot
 
 
 # --------------------------------------------------------------------------------------------- #

@@ -7,6 +7,9 @@ registry `WRAPPER_CLASS_DICT`, constructor keywords as the YAML files pass them,
 * `CodecFeatureCompressionClassifier` (wrapper.py:138-193): classifier split into encoder / decoder / classifier by
   `sequential` module lists; each sample's feature map goes through a codec transform (config 1: `PILTensorModule`).
 * `CodecInputCompressionClassifier` (wrapper.py:28-77), `EntropicClassifier` (:196-265), `SplitClassifier` (:268-322).
+* `InputCompressionDetectionModel` (models/detection/wrapper.py:11-95) and `CodecInputCompressionSegmentationModel`
+  (models/segmentation/wrapper.py:11-51): the codec input-compression baselines of the two dense tasks, with their
+  `get_wrapped_*_model` builders.
 
 Reference behaviour kept on purpose: per-sample results are joined with `torch.hstack`, i.e. along dim 1 -- the
 reference evaluates these baselines at test batch size 1 (README.md:100-108), where that equals a batch of one.
@@ -135,6 +138,85 @@ class CodecInputCompressionClassifier(AnalyzableModule, _PerSampleCodec):
 
     def forward(self, x):
         return self.classification_model(self._through_codec(x))
+
+
+@register_wrapper_class
+class CodecInputCompressionSegmentationModel(AnalyzableModule, _PerSampleCodec):
+    """Codec on the input image, then a segmentation model (sc2bench/models/segmentation/wrapper.py:11-51).  `x`: list of PIL
+    images; equal-size images with a `ToTensor` (+ `Normalize`) post-transform take the device codec as the classifier's do."""
+
+    def __init__(self, segmentation_model, device, codec_encoder_decoder=None, post_transform=None, analysis_config=None, **kwargs):
+        super().__init__(_analyzer_configs(analysis_config))
+        self.codec_encoder_decoder = codec_encoder_decoder
+        self.device = device
+        self.segmentation_model = segmentation_model
+        self.post_transform = post_transform
+
+    def forward(self, x):
+        return self.segmentation_model(self._through_codec(x))
+
+
+def _check_if_analyzable(module):
+    return isinstance(module, AnalyzableModule)
+
+
+@register_wrapper_class
+class InputCompressionDetectionModel(AnalyzableModule):
+    """Codec or compression model on the RESIZED input image, then a detection model (sc2bench/models/detection/wrapper.py:11-95):
+    the detector's `transform` is replaced by `detection.RCNNTransformWithCompression`, which holds the analyzers; the five analysis
+    calls are passed on to it."""
+
+    def __init__(self, detection_model, device, codec_encoder_decoder=None, compression_model=None, uses_cpu4compression_model=False,
+                 pre_transform=None, post_transform=None, analysis_config=None, adaptive_pad_kwargs=None, **kwargs):
+        from .detection import RCNNTransformWithCompression
+        analysis_config = analysis_config or dict()
+        super().__init__()
+        detection_model.transform = RCNNTransformWithCompression(
+            detection_model.transform, device, codec_encoder_decoder, _analyzer_configs(analysis_config),
+            analyzes_after_compress=analysis_config.get('analyzes_after_compress', False), compression_model=compression_model,
+            uses_cpu4compression_model=uses_cpu4compression_model, pre_transform=pre_transform, post_transform=post_transform,
+            adaptive_pad_kwargs=adaptive_pad_kwargs)
+        self.device = device
+        self.uses_cpu4compression_model = uses_cpu4compression_model
+        self.detection_model = detection_model
+
+    def use_cpu4compression(self):
+        transform = self.detection_model.transform
+        if self.uses_cpu4compression_model and transform.compression_model is not None:
+            transform.compression_model = transform.compression_model.cpu()
+
+    def forward(self, x):
+        return self.detection_model(x)
+
+    def activate_analysis(self):
+        self.activated_analysis = True
+        if _check_if_analyzable(self.detection_model.transform):
+            self.detection_model.transform.activate_analysis()
+
+    def deactivate_analysis(self):
+        self.activated_analysis = False
+        if _check_if_analyzable(self.detection_model.transform):
+            self.detection_model.transform.deactivate_analysis()
+
+    def analyze(self, compressed_obj):
+        if not self.activated_analysis:
+            return
+        for analyzer in self.analyzers:
+            analyzer.analyze(compressed_obj)
+        if _check_if_analyzable(self.detection_model.transform):
+            self.detection_model.transform.analyze(compressed_obj)
+
+    def summarize(self):
+        for analyzer in self.analyzers:
+            analyzer.summarize()
+        if _check_if_analyzable(self.detection_model.transform):
+            self.detection_model.transform.summarize()
+
+    def clear_analysis(self):
+        for analyzer in self.analyzers:
+            analyzer.clear()
+        if _check_if_analyzable(self.detection_model.transform):
+            self.detection_model.transform.clear_analysis()
 
 
 @register_wrapper_class
@@ -349,6 +431,54 @@ def get_wrapped_classification_model(wrapper_model_config, device):
     if wrapper_model_config.get('src_ckpt') is not None:
         load_ckpt(wrapper_model_config['src_ckpt'], model=wrapped, strict=False)
     return wrapped
+
+
+def _load_dense_model(model_config, device, registry, kind):
+    """`{key, kwargs, src_ckpt?}` -> a model of `registry` on `device` (models/{detection,segmentation}/registry.py)."""
+    from .ckpt import load_ckpt
+    name = model_config['key']
+    if name not in registry:
+        raise KeyError('{} model `{}` is not available in this build (have {})'.format(kind, name, sorted(registry)))
+    model = registry[name](**dict(model_config.get('kwargs') or {}))
+    if model_config.get('src_ckpt') is not None:      # (a download address upstream: `load_ckpt` looks in $SC2_PRETRAINED_DIR)
+        load_ckpt(model_config['src_ckpt'], model=model, strict=False)
+    return model.to(device)
+
+
+def load_detection_model(model_config, device):
+    from .dense import DETECTION_MODEL_FUNC_DICT
+    return _load_dense_model(model_config, device, DETECTION_MODEL_FUNC_DICT, 'detection')
+
+
+def load_segmentation_model(model_config, device):
+    from .dense import SEGMENTATION_MODEL_FUNC_DICT
+    return _load_dense_model(model_config, device, SEGMENTATION_MODEL_FUNC_DICT, 'segmentation')
+
+
+def _get_wrapped_dense_model(wrapper_model_config, device, model):
+    from .ckpt import load_ckpt
+    from .compression import get_compression_model
+    name = wrapper_model_config['key']
+    if name not in WRAPPER_CLASS_DICT:
+        raise ValueError('wrapper_model_name `{}` is not expected'.format(name))
+    compression_model = get_compression_model(wrapper_model_config.get('compression_model', None), device)
+    wrapped = WRAPPER_CLASS_DICT[name](model, compression_model=compression_model, device=device,
+                                       **(wrapper_model_config.get('kwargs') or {}))
+    if wrapper_model_config.get('src_ckpt') is not None:
+        load_ckpt(wrapper_model_config['src_ckpt'], model=wrapped, strict=False)
+    return wrapped
+
+
+def get_wrapped_detection_model(wrapper_model_config, device):
+    """models.model block with a `detection_model` entry -> wrapped model (sc2bench/models/detection/wrapper.py:98-122)."""
+    return _get_wrapped_dense_model(wrapper_model_config, device,
+                                    load_detection_model(wrapper_model_config['detection_model'], device))
+
+
+def get_wrapped_segmentation_model(wrapper_model_config, device):
+    """models.model block with a `segmentation_model` entry -> wrapped model (sc2bench/models/segmentation/wrapper.py:120-144)."""
+    return _get_wrapped_dense_model(wrapper_model_config, device,
+                                    load_segmentation_model(wrapper_model_config['segmentation_model'], device))
 
 
 def load_model(model_config, device):
