@@ -888,6 +888,48 @@ int sc2_seg_predict(const void *logits, int is_bf16, int N, int C, int h, int w,
                     long long stride_h, long long stride_w, int c_readable, int H, int W, const long long *targets, long long *labels,
                     long long *mat, void *stream);
 
+/* Segmentation training loss (csrc/seg_loss.hip): `cross_entropy(interpolate(logits, (H, W), mode='bilinear', align_corners=False),
+ * targets, ignore_index=..)` and its gradient with respect to the LOW-resolution logits, without forming the resized logits or their
+ * gradient.  tests/ref_seg_loss.py restates both in float64.
+ * logits, strides, c_readable, H, W, the limits on sizes and classes: as for sc2_seg_predict, and at most 65535 images.  The resized
+ * value v[p,c] of output pixel p and class c is sc2_seg_predict's formula (the kernels share its code: csrc/seg_common.h).
+ * targets: int64 [N,H,W] contiguous.  A pixel is VALID when 0 <= target < C and target != ignore_index.  A pixel whose target equals
+ * ignore_index is skipped (torch's rule); a target that is neither valid nor ignore_index is skipped too and counted as BAD (torch
+ * trips a device assert there; no label may fault the device). */
+#define SC2_SEG_CE_MEAN 0
+#define SC2_SEG_CE_SUM 1
+#define SC2_SEG_CE_NONE 2
+/* Bytes of workspace a forward call needs for its per-workgroup partials (0 for sizes the kernels refuse). */
+long long sc2_seg_ce_ws_bytes(int N, int H, int W);
+/* Per valid pixel  loss_p = lse_p - v[p,target_p],  lse_p = m + logf(sum_c expf(v[p,c] - m)),  m = max_c v[p,c]: f32, accurate expf /
+ * logf, one online pass over the classes (running maximum; the running sum is rescaled by expf(m_old - m_new) when the maximum moves).
+ * pixel_loss: f32 [N,H,W] or NULL; skipped pixels get 0 (reduction='none').  lse: f32 [N,H,W] or NULL; written for every pixel,
+ *             what the backward call reads.
+ * sums      : three 8-byte words of device memory: float64 sum of loss_p over the valid pixels, int64 number of valid pixels, int64
+ *             number of bad targets.  Nothing is read back; the caller divides on the device.
+ * ws        : sc2_seg_ce_ws_bytes(N, H, W) bytes, 8-byte aligned.  Every workgroup leaves one float64 partial (and its two counts)
+ *             there; a second launch of one workgroup adds them in a fixed order (consecutive runs of partials per thread, then a
+ *             fixed tree).  No atomics: the sum has the same bits on every call, whatever order the workgroups ran in.
+ * Two launches on `stream`, no host synchronisation. */
+int sc2_seg_ce_forward(const void *logits, int is_bf16, int N, int C, int h, int w, long long stride_n, long long stride_c,
+                       long long stride_h, long long stride_w, int c_readable, int H, int W, const long long *targets,
+                       long long ignore_index, float *pixel_loss, float *lse, void *sums, void *ws, void *stream);
+/* dx[n,c,i,j] = g * sum_p w_p(i,j) * (expf(v[p,c] - lse_p) - [c == target_p])  over the valid output pixels p whose bilinear footprint
+ * holds source pixel (i,j).  w_p(i,j) is the product of the two axis weights: (1 - lambda) where i is the axis' i0, lambda where it is
+ * i1, their sum where i0 == i1 at the clamped edge.
+ * lse, sums : what the forward call wrote (sums[1], the number of valid pixels, is read on the device).
+ * reduction : SC2_SEG_CE_MEAN: g = *grad_out / count, and every dx is 0 when count == 0 (torch: a NaN loss with a zero gradient);
+ *             SC2_SEG_CE_SUM: g = *grad_out;  SC2_SEG_CE_NONE: grad_out is f32 [N,H,W], the factor of pixel p goes into its term, g = 1.
+ * dx        : the logits' dtype (a bf16 gradient is rounded once from the f32 sum), addressed by its own four element strides.  EVERY
+ *             element of [N,C,h,w] is written; source pixels no output pixel touches (downsampling) get 0.
+ * A gather: the output rows that touch source row i are seg-axis-first(i-1) .. seg-axis-first(i+1) - 1, computable from integers because
+ * i0(d) does not decrease with d, and likewise for columns; one thread owns one (source pixel, class) and adds its terms in f32,
+ * row by row and left to right.  No atomics: dx has the same bits on every call.  One launch on `stream`. */
+int sc2_seg_ce_backward(const void *logits, int is_bf16, int N, int C, int h, int w, long long stride_n, long long stride_c,
+                        long long stride_h, long long stride_w, int c_readable, int H, int W, const long long *targets,
+                        long long ignore_index, const float *lse, const void *sums, const float *grad_out, int reduction, void *dx,
+                        long long dx_stride_n, long long dx_stride_c, long long dx_stride_h, long long dx_stride_w, void *stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* COCO box AP (csrc/coco.hip): COCOeval's `bbox` protocol with its default parameters, written from the published     */
 /* protocol.  tests/ref_coco.py restates it as a sequential float64 loop; both kernels reproduce that bit for bit.    */

@@ -31,8 +31,8 @@ from .wrapper import (WRAPPER_CLASS_DICT, CodecFeatureCompressionClassifier, Cod
                       get_wrapped_segmentation_model, load_detection_model, load_segmentation_model, wrap_model)
 
 from .dense import (DETECTION_MODEL_FUNC_DICT, SEGMENTATION_MODEL_FUNC_DICT, BaseRCNN, BaseSegmentationModel,  # noqa: F401
-                    SegEvaluator, UpdatableBackboneWithFPN, backbone_with_fpn, deeplabv3_model, deeplabv3_resnet50,
-                    faster_rcnn_model, fasterrcnn_resnet50_fpn, seg_labels)
+                    ResizedLogits, SegEvaluator, UpdatableBackboneWithFPN, backbone_with_fpn, deeplabv3_model, deeplabv3_resnet50,
+                    faster_rcnn_model, fasterrcnn_resnet50_fpn, seg_cross_entropy, seg_labels)
 
 from .coco_eval import CocoBoxEvaluator, CocoDictDetection, coco_gt_from_dataset  # noqa: F401
 from .pipeline import StagePipeline, supports_stages  # noqa: F401

@@ -155,10 +155,27 @@ def _sc2bench_attr(key):
     return Placeholder(key)
 
 
+def get_num_iterations(dataset, batch_size, world_size=1):
+    """`utils.dataset.get_num_iterations` of the reference's task scripts (the PASCAL poly schedule's length in iterations per epoch):
+    ceil(len(dataset) / batch_size / world_size), [recalled].  A dataset that is itself a `Placeholder` (its package is
+    not available) or whose directory is absent leaves a `Placeholder`, which `training.poly_lr_scheduler` refuses by name."""
+    import math
+    unresolved = Placeholder('utils.dataset.get_num_iterations', (), dict(dataset=dataset, batch_size=batch_size, world_size=world_size))
+    if isinstance(dataset, Placeholder):
+        return unresolved
+    try:
+        size = len(dataset)
+    except (FileNotFoundError, TypeError):      # a dataset directory that is absent must not keep the file from parsing
+        return unresolved
+    return int(math.ceil(size / batch_size / world_size))
+
+
 def resolve(key):
     """Dotted name -> object, with the substitutions listed in the module docstring."""
     if key.startswith('sc2bench.'):
         return _sc2bench_attr(key)
+    if key == 'utils.dataset.get_num_iterations':
+        return get_num_iterations
     if key.startswith('torchvision.datasets.'):
         return ImageFolder
     if key.startswith('torchvision.models.') and key.endswith('_Weights'):

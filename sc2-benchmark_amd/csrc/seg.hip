@@ -4,15 +4,12 @@
 // tests/ref_seg.py restates it in float64.
 // Plain kernels: every index checked against its array before use, one kind of global atomic (a 64-bit integer vector add per
 // non-zero bin of a workgroup's histogram), no workgroup waits for another.
-#include "sc2_common.h"
-
-#pragma clang fp contract(off)   // `(1-ly)*((1-lx)*a + lx*b) + ly*(...)`: every step rounded once, the same for every class
+#include "seg_common.h"      // the axis map, the class loads and the resized value, shared with seg_loss.hip
 
 namespace {
 
 constexpr int SEG_TW = 32, SEG_TH = 8;       // output pixels of one tile: a wave covers two rows of 32
 constexpr int SEG_THREADS = SEG_TW * SEG_TH;
-constexpr int SEG_MAX_DIM = 32768;           // (2 d + 1) * h - H stays inside 32 bits
 constexpr long long SEG_MAX_TILES_PER_WG = 1ll << 22;      // x 256 pixels: a workgroup's int32 bins cannot overflow
 
 struct SegArgs {
@@ -23,52 +20,6 @@ struct SegArgs {
     long long sN, sC, sH, sW;      // element strides of the logits
     long long n_tiles;
     int N, C, h, w, H, W, tiles_x, tiles_y;
-};
-
-// Source index pair and weight of output index d along one axis (align_corners=False), in integers: t = (2d+1)*in - out is the
-// source coordinate times 2*out.  t <= 0 is the clamp at the first pixel.
-__device__ __forceinline__ void seg_axis(int d, int in, int out, int &i0, int &i1, float &l) {
-    const int t = (2 * d + 1) * in - out;
-    if (t <= 0) {
-        i0 = 0;
-        l = 0.0f;
-    } else {
-        const unsigned den = 2u * (unsigned)out;
-        const unsigned q = (unsigned)t / den;
-        i0 = (int)q;
-        l = (float)((unsigned)t - q * den) / (float)den;
-    }
-    i1 = min(i0 + 1, in - 1);
-}
-
-template <bool BF16>
-struct SegVec;
-template <>
-struct SegVec<false> {     // 4 f32 classes per 16-byte load
-    static constexpr int V = 4;
-    typedef float elem;
-    __device__ static __forceinline__ void load(const void *base, long long at, float (&v)[4]) {
-        const float4 q = *reinterpret_cast<const float4 *>(static_cast<const float *>(base) + at);
-        v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    }
-    __device__ static __forceinline__ float load1(const void *base, long long at) { return static_cast<const float *>(base)[at]; }
-};
-template <>
-struct SegVec<true> {      // 8 bf16 classes per 16-byte load
-    static constexpr int V = 8;
-    typedef uint16_t elem;
-    __device__ static __forceinline__ void load(const void *base, long long at, float (&v)[8]) {
-        const uint4 q = *reinterpret_cast<const uint4 *>(static_cast<const uint16_t *>(base) + at);
-        const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            v[2 * i] = __builtin_bit_cast(float, w[i] << 16);
-            v[2 * i + 1] = __builtin_bit_cast(float, w[i] & 0xFFFF0000u);
-        }
-    }
-    __device__ static __forceinline__ float load1(const void *base, long long at) {
-        return bf16_bits_to_f32(static_cast<const uint16_t *>(base)[at]);
-    }
 };
 
 // first index holding the maximum, a NaN larger than any number and the first NaN final (torch.argmax)
@@ -87,7 +38,6 @@ __device__ __forceinline__ void seg_take(float v, int c, float &best, int &label
 template <bool BF16, bool VEC, bool HIST>
 __global__ __launch_bounds__(SEG_THREADS) void seg_predict_kernel(const SegArgs a) {
     extern __shared__ __attribute__((aligned(16))) int hist[];
-    constexpr int V = SegVec<BF16>::V;
     const int tid = threadIdx.x;
     const int bins = a.C * a.C;
     if (HIST) {
@@ -112,35 +62,12 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_predict_kernel(const SegArgs 
         const long long p10 = img + y1 * a.sH + x0 * a.sW, p11 = img + y1 * a.sH + x1 * a.sW;
         float best = 0.0f;
         int label = 0;
-        if (VEC) {
-            for (int c0 = 0; c0 < a.C; c0 += V) {
-                float va[V], vb[V], vc[V], vd[V];
-                SegVec<BF16>::load(a.logits, p00 + c0, va);
-                SegVec<BF16>::load(a.logits, p01 + c0, vb);
-                SegVec<BF16>::load(a.logits, p10 + c0, vc);
-                SegVec<BF16>::load(a.logits, p11 + c0, vd);
-#pragma unroll
-                for (int v = 0; v < V; ++v) {
-                    const float val = hy * (hx * va[v] + lx * vb[v]) + ly * (hx * vc[v] + lx * vd[v]);
-                    if (c0 + v == 0) {
-                        best = val;
-                    } else if (c0 + v < a.C) {      // the pad channels of the last piece never take part
-                        seg_take(val, c0 + v, best, label);
-                    }
-                }
-            }
-        } else {
-            for (int c = 0; c < a.C; ++c) {
-                const long long o = c * a.sC;
-                const float va = SegVec<BF16>::load1(a.logits, p00 + o), vb = SegVec<BF16>::load1(a.logits, p01 + o);
-                const float vc = SegVec<BF16>::load1(a.logits, p10 + o), vd = SegVec<BF16>::load1(a.logits, p11 + o);
-                const float val = hy * (hx * va + lx * vb) + ly * (hx * vc + lx * vd);
-                if (c == 0)
-                    best = val;
-                else
-                    seg_take(val, c, best, label);
-            }
-        }
+        seg_for_each_class<BF16, VEC>(a.logits, a.C, a.sC, p00, p01, p10, p11, hy, hx, ly, lx, [&](int c, float val) {
+            if (c == 0)
+                best = val;
+            else
+                seg_take(val, c, best, label);
+        });
         const long long at = ((long long)n * a.H + oy) * a.W + ox;
         if (a.labels) a.labels[at] = label;
         if (HIST) {
@@ -193,10 +120,7 @@ extern "C" int sc2_seg_predict(const void *logits, int is_bf16, int N, int C, in
     a.tiles_x = (W + SEG_TW - 1) / SEG_TW;
     a.tiles_y = (H + SEG_TH - 1) / SEG_TH;
     a.n_tiles = (long long)N * a.tiles_x * a.tiles_y;
-    // 16-byte class loads: consecutive classes, every pixel's first class on a 16-byte boundary, and the whole last piece readable
-    const int V = is_bf16 ? 8 : 4;
-    const bool vec = stride_c == 1 && c_readable >= (C + V - 1) / V * V && (reinterpret_cast<uintptr_t>(logits) & 15u) == 0 &&
-                     stride_n % V == 0 && stride_h % V == 0 && stride_w % V == 0;
+    const bool vec = seg_vec_ok(logits, is_bf16, C, stride_n, stride_c, stride_h, stride_w, c_readable);
     const long long cap = (long long)sc2_device_cus() * 8;
     long long grid = a.n_tiles < cap ? a.n_tiles : cap;
     const long long floor_wgs = (a.n_tiles + SEG_MAX_TILES_PER_WG - 1) / SEG_MAX_TILES_PER_WG;

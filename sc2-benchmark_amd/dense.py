@@ -496,6 +496,7 @@ class BaseSegmentationModel(_UpdatableDenseModel):
         self.backbone = backbone
         self.classifier = classifier
         self.aux_classifier = aux_classifier
+        self.defer_resize = False     # True (training mode only): forward returns `ResizedLogits`, the criterion resizes inside its loss kernel
 
     def _body(self):
         return self.backbone
@@ -508,7 +509,10 @@ class BaseSegmentationModel(_UpdatableDenseModel):
         return hd(feat) if hd is not None else head(feat)
 
     def _head(self, head, feat, size):
-        return F.interpolate(self._logits(head, feat), size=size, mode='bilinear', align_corners=False)
+        logits = ResizedLogits(self._logits(head, feat), size)
+        if self.defer_resize and self.training:
+            return logits
+        return logits.resized()
 
     def _finish(self, features, input_shape):
         result = OrderedDict()
@@ -588,6 +592,65 @@ def _count_pairs(mat, target, prediction):
     keep = (target >= 0) & (target < n)
     inds = n * target[keep].to(torch.int64) + prediction[keep]
     mat += torch.bincount(inds, minlength=n ** 2).reshape(n, n)
+
+
+class ResizedLogits(object):
+    """Low-resolution logits [N,C,h,w] and the size they are to be resized to: what `BaseSegmentationModel.forward` returns per head
+    with `defer_resize` in training mode, for a criterion that takes the resize into its own kernel (`seg_cross_entropy`)."""
+
+    def __init__(self, logits, size):
+        self.logits = logits
+        self.size = (int(size[0]), int(size[1]))
+
+    def resized(self):
+        return F.interpolate(self.logits, size=self.size, mode='bilinear', align_corners=False)
+
+
+class _SegCrossEntropyFn(torch.autograd.Function):
+    """sc2_seg_ce_forward / sc2_seg_ce_backward; the loss leaves as an f32 device scalar ('mean', 'sum') or f32 [N,H,W] ('none')"""
+
+    @staticmethod
+    def forward(ctx, logits, size, targets, ignore_index, reduction):
+        from . import hip
+        res = hip.seg_ce_forward(logits, size, targets, ignore_index, want_pixel_loss=reduction == hip.SEG_CE_NONE)
+        ctx.save_for_backward(logits, targets, res.lse, res.sums)
+        ctx.size, ctx.ignore_index, ctx.reduction = size, ignore_index, reduction
+        ctx.mark_non_differentiable(res.sums)
+        if reduction == hip.SEG_CE_NONE:
+            return res.pixel_loss, res.sums
+        if reduction == hip.SEG_CE_SUM:
+            return res.sums[0].float(), res.sums
+        return (res.sums[0] / res.sums.view(torch.int64)[1]).float(), res.sums      # 0 / 0 = NaN, as torch
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_sums):
+        from . import hip
+        logits, targets, lse, sums = ctx.saved_tensors
+        dx = hip.seg_ce_backward(logits, ctx.size, targets, lse, sums, grad_out.float().contiguous(), ctx.ignore_index, ctx.reduction)
+        return dx, None, None, None, None
+
+
+def seg_cross_entropy(logits, size, targets, ignore_index=255, reduction='mean', strict=False, weight=None, label_smoothing=0.0):
+    """`F.cross_entropy(F.interpolate(logits, size, mode='bilinear', align_corners=False), targets, ignore_index=.., reduction=..)` from
+    the LOW-resolution logits [N,C,h,w].  Device tensors of up to 64 classes (f32 / bf16, no class weights, no label smoothing, with
+    `host_policy.seg_loss_hip` on) go to `sc2_seg_ce_forward` and, through autograd, `sc2_seg_ce_backward`: f32 arithmetic on the
+    unrounded logits, neither the resized logits nor their gradient are formed, the loss is an f32 device scalar and nothing is read
+    back.  Anything else takes the two torch ops.  A target outside 0..C-1 that is not `ignore_index` is skipped and counted by the
+    kernels (torch asserts on the device); `strict=True` reads the count back and raises ValueError."""
+    from . import hip
+    size = (int(size[0]), int(size[1]))
+    code = {'mean': hip.SEG_CE_MEAN, 'sum': hip.SEG_CE_SUM, 'none': hip.SEG_CE_NONE}.get(reduction)
+    if (logits.is_cuda and targets.is_cuda and hip.host_policy.seg_loss_hip and code is not None and weight is None and not label_smoothing and
+            logits.dim() == 4 and logits.shape[1] <= hip.SEG_MAX_CLASSES and logits.dtype in (torch.float32, torch.bfloat16)):
+        loss, sums = _SegCrossEntropyFn.apply(logits, size, targets.to(torch.int64).contiguous(), int(ignore_index), code)
+        if strict:
+            bad = int(sums.view(torch.int64)[2])
+            if bad:
+                raise ValueError('seg_cross_entropy: {} targets outside 0..{} that are not ignore_index={}'.format(
+                    bad, logits.shape[1] - 1, ignore_index))
+        return loss
+    resized = F.interpolate(logits, size=size, mode='bilinear', align_corners=False)
+    return F.cross_entropy(resized, targets, weight=weight, ignore_index=ignore_index, reduction=reduction, label_smoothing=label_smoothing)
 
 
 def seg_labels(logits, size, targets=None, mat=None, want_labels=True):

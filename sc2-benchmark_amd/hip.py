@@ -38,7 +38,7 @@ ABI_SYMBOLS = [
     'sc2_mse_partial_len', 'sc2_mse_sum_bf16', 'sc2_mse_grad_bf16', 'sc2_relu_bwd_bf16', 'sc2_relu_bwd_mse_bf16',
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
-    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_seg_predict', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
+    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
     'sc2_jpeg_max_bytes', 'sc2_jpeg_tensor_codec', 'sc2_jpeg_image_max_bytes', 'sc2_jpeg_image_workspace_bytes', 'sc2_jpeg_image_codec',
     'sc2_rcnn_resize_u8', 'sc2_rcnn_normalize_pad',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
@@ -66,6 +66,7 @@ class ArScanArgs(ctypes.Structure):
 NMS_MAX_BOXES = 16384      # SC2_NMS_MAX_BOXES
 ROI_MAX_LEVELS = 5         # SC2_ROI_MAX_LEVELS
 SEG_MAX_CLASSES = 64       # SC2_SEG_MAX_CLASSES
+SEG_CE_MEAN, SEG_CE_SUM, SEG_CE_NONE = 0, 1, 2     # SC2_SEG_CE_*
 COCO_THRS, COCO_RECS, COCO_AREAS, COCO_MAXDETS = 10, 101, 4, 3     # SC2_COCO_*
 COCO_TILE_DETS, COCO_TILE_GTS, COCO_SCAN_CHUNK = 100, 64, 1024
 JPEG_MAX_SIDE = 64         # SC2_JPEG_MAX_SIDE
@@ -152,6 +153,7 @@ class HostPolicy(object):
     jpeg_image_hip = True      # transforms.PILImageModule(format='JPEG').forward_batch of equal-size RGB / grey PIL images up to 2048 x 2048 on sc2_jpeg_image_codec (False: PIL per image on the host, A/B; tools/jpeg_image_times.py, codec + ToTensor + Normalize to the classifier input: 0.39 against 0.50 ms at [1,3,224,224], 10.4 against 174 ms at [256,3,224,224])
     rcnn_input_hip = True      # detection.RCNNTransformWithCompression (eval, plain JPEG, f32 RGB device images): resize -> codec -> normalise + pad per image on sc2_rcnn_resize_u8 + sc2_jpeg_image_codec + sc2_rcnn_normalize_pad, one read-back per list (False: the reference's loop through Pillow on the host, A/B; tools/rcnn_input_times.py, 480 x 640 -> 800 x 1066 at quality 90: 2.79 against 25.7 ms at one image per call, 16.0 against 88.3 ms at six; the two new kernels alone 0.009 ms each, the codec 2.63 ms)
     seg_predict_hip = True     # dense.seg_labels (BaseSegmentationModel.predict, SegEvaluator.update_logits) of device tensors on sc2_seg_predict (False: interpolate + argmax + bincount, A/B)
+    seg_loss_hip = True        # dense.seg_cross_entropy (DictLossWrapper over a deferred-resize segmentation student) of device tensors on sc2_seg_ce_forward + sc2_seg_ce_backward (False: F.interpolate + F.cross_entropy + autograd, A/B; tools/seg_loss_times.py, out + aux forward + backward at [8,21,65,65] -> 513 x 513: 1.27 against 2.70 ms with f32 logits, 1.27 against 1.72 ms with bf16, 20 against 707 MB of peak allocation)
 
 
 host_policy = HostPolicy()
@@ -324,6 +326,10 @@ def lib():
     L.sc2_nms.argtypes = [vp, vp, i32, f32, vp, vp, vp, vp]
     L.sc2_roi_align.argtypes = [RoiLevels, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]
     L.sc2_seg_predict.argtypes = [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, i32, vp, vp, vp, vp]
+    L.sc2_seg_ce_ws_bytes.argtypes = [i32, i32, i32]
+    L.sc2_seg_ce_ws_bytes.restype = i64
+    L.sc2_seg_ce_forward.argtypes = [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, i32, vp, i64, vp, vp, vp, vp, vp]
+    L.sc2_seg_ce_backward.argtypes = [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, i32, vp, i64, vp, vp, vp, i32, vp, i64, i64, i64, i64, vp]
     L.sc2_coco_match_ws_bytes.argtypes = [i64]
     L.sc2_coco_match_ws_bytes.restype = i64
     L.sc2_coco_match.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
@@ -1236,6 +1242,14 @@ def seg_predict(logits, size, targets=None, mat=None, want_labels=True, tag=None
         assert targets.dtype == torch.int64 and targets.shape == (N, H, W) and targets.is_contiguous() and targets.device == logits.device
         assert mat.dtype == torch.int64 and mat.shape == (C, C) and mat.is_contiguous() and mat.device == logits.device
     labels = torch.empty((N, H, W), dtype=torch.int64, device=logits.device) if want_labels else None
+    with _timed(tag or 'seg_predict'):
+        _check(lib().sc2_seg_predict(*(_seg_logits_args(logits) + (H, W, _ptr(targets), _ptr(labels), _ptr(mat), _stream()))), 'seg_predict')
+    return labels
+
+
+def _seg_logits_args(logits):
+    """the leading arguments of the sc2_seg_* calls: pointer, is_bf16, N, C, h, w, the four element strides, c_readable"""
+    N, C, h, w = (int(v) for v in logits.shape)
     sn, sc, sh, sw = (int(v) for v in logits.stride())
     # elements readable behind every pixel's class 0: the kernel's 16-byte class loads run up to C rounded up to 8 (bf16) / 4 (f32)
     readable = C
@@ -1244,10 +1258,66 @@ def seg_predict(logits, size, targets=None, mat=None, want_labels=True, tag=None
         last = logits.storage_offset() + (N - 1) * sn + (h - 1) * sh + (w - 1) * sw
         if last + (C + vec - 1) // vec * vec <= logits.untyped_storage().nbytes() // logits.element_size():
             readable = (C + vec - 1) // vec * vec
-    with _timed(tag or 'seg_predict'):
-        _check(lib().sc2_seg_predict(_ptr(logits), 1 if logits.dtype == torch.bfloat16 else 0, N, C, h, w, sn, sc, sh, sw, readable, H, W,
-                                     _ptr(targets), _ptr(labels), _ptr(mat), _stream()), 'seg_predict')
-    return labels
+    return (_ptr(logits), 1 if logits.dtype == torch.bfloat16 else 0, N, C, h, w, sn, sc, sh, sw, readable)
+
+
+# --------------------------------------------------------------------------------------------- #
+# segmentation training loss: cross entropy of the resized logits, forward and backward, from the low-resolution map (csrc/seg_loss.hip)
+# --------------------------------------------------------------------------------------------- #
+SegCeForward = collections.namedtuple('SegCeForward', ['sums', 'lse', 'pixel_loss'])
+
+
+def _seg_ce_check(logits, size, targets, who):
+    _dev(logits, 'logits')
+    _dev(targets, 'targets')
+    assert logits.dim() == 4 and logits.dtype in (torch.float32, torch.bfloat16)
+    N = int(logits.shape[0])
+    H, W = int(size[0]), int(size[1])
+    assert targets.dtype == torch.int64 and targets.shape == (N, H, W) and targets.is_contiguous() and targets.device == logits.device, who
+    return N, H, W
+
+
+def seg_ce_forward(logits, size, targets, ignore_index=255, want_pixel_loss=False, want_lse=True, tag=None):
+    """Cross entropy of `F.interpolate(logits, size, mode='bilinear', align_corners=False)` against `targets`, in f32 on the unrounded
+    logits, without the resized tensor (include/sc2_bottleneck.h: sc2_seg_ce_forward).  logits: [N,C,h,w] f32 or bf16 with any
+    non-negative strides, C <= 64 (more raises Sc2Error); targets: int64 [N,H,W] contiguous.
+    -> SegCeForward(sums, lse, pixel_loss): sums = 24 device bytes viewed as float64 [3] (view(torch.int64)[1:] are the number of valid
+    pixels and of bad targets), lse f32 [N,H,W] (what seg_ce_backward reads) or None, pixel_loss f32 [N,H,W] (0 at skipped pixels) or
+    None.  Nothing is read back."""
+    N, H, W = _seg_ce_check(logits, size, targets, 'seg_ce_forward')
+    dev = logits.device
+    sums = torch.empty(3, dtype=torch.float64, device=dev)
+    ws = torch.empty(max(int(lib().sc2_seg_ce_ws_bytes(N, H, W)), 8) // 8, dtype=torch.float64, device=dev)
+    lse = torch.empty((N, H, W), dtype=torch.float32, device=dev) if want_lse else None
+    pixel_loss = torch.empty((N, H, W), dtype=torch.float32, device=dev) if want_pixel_loss else None
+    with _timed(tag or 'seg_ce_forward'):
+        _check(lib().sc2_seg_ce_forward(*(_seg_logits_args(logits) + (H, W, _ptr(targets), int(ignore_index), _ptr(pixel_loss), _ptr(lse),
+                                                                      _ptr(sums), _ptr(ws), _stream()))), 'seg_ce_forward')
+    return SegCeForward(sums, lse, pixel_loss)
+
+
+def seg_ce_backward(logits, size, targets, lse, sums, grad_out, ignore_index=255, reduction=SEG_CE_MEAN, out=None, tag=None):
+    """The gradient of `seg_ce_forward`'s loss with respect to the low-resolution logits (include/sc2_bottleneck.h:
+    sc2_seg_ce_backward): a gather, no atomics, every element written.  lse, sums: what the forward returned; grad_out: f32 device
+    scalar (SEG_CE_MEAN, SEG_CE_SUM) or f32 [N,H,W] (SEG_CE_NONE); out: a tensor of the logits' shape and dtype with any non-negative
+    strides, or None (then contiguous in the logits' memory format is allocated).  -> dx"""
+    N, H, W = _seg_ce_check(logits, size, targets, 'seg_ce_backward')
+    dev = logits.device
+    for name, t in (('lse', lse), ('sums', sums), ('grad_out', grad_out)):
+        _dev(t, name)
+    assert lse.dtype == torch.float32 and lse.shape == (N, H, W) and lse.is_contiguous() and lse.device == dev
+    assert sums.dtype == torch.float64 and sums.numel() == 3 and sums.is_contiguous() and sums.device == dev
+    assert reduction in (SEG_CE_MEAN, SEG_CE_SUM, SEG_CE_NONE)
+    assert grad_out.dtype == torch.float32 and grad_out.is_contiguous() and grad_out.device == dev
+    assert grad_out.shape == (N, H, W) if reduction == SEG_CE_NONE else grad_out.numel() == 1
+    if out is None:
+        out = torch.empty_like(logits)      # (preserve_format: a permuted NHWC view gets a dense gradient of the same layout)
+    assert out.shape == logits.shape and out.dtype == logits.dtype and out.device == dev and all(int(v) >= 0 for v in out.stride())
+    with _timed(tag or 'seg_ce_backward'):
+        _check(lib().sc2_seg_ce_backward(*(_seg_logits_args(logits) + (H, W, _ptr(targets), int(ignore_index), _ptr(lse), _ptr(sums),
+                                                                       _ptr(grad_out), int(reduction), _ptr(out)) +
+                                           tuple(int(v) for v in out.stride()) + (_stream(),))), 'seg_ce_backward')
+    return out
 
 
 # --------------------------------------------------------------------------------------------- #

@@ -5,7 +5,9 @@ restated in SURVEY.md appendix C).  What the hot path needs from it is small and
 config keys: per-model `sequential` / `frozen_modules` / `forward_hook` / `requires_grad`, the forward-hook IO
 dict, `WeightedSumLoss` over `SimpleLossWrapper(MSELoss | ...)` and mid-level losses (`BppLoss`), optimizer /
 scheduler by key, the separate `aux_loss` backward (image_classification.py:74-77), and -- instead of DDP -- the
-flat-bucket gradient all-reduce of `dataparallel.py`.
+flat-bucket gradient all-reduce of `dataparallel.py`.  The PASCAL segmentation blocks add `DictLossWrapper` (cross entropy
+over the `out` / `aux` heads, on the fused resize + loss kernels when the student defers its resize), `poly_lr_scheduler`
+stepped per iteration (`scheduling_step`) and per-module optimizer groups (`module_wise_kwargs`).
 """
 from collections import OrderedDict
 
@@ -135,7 +137,60 @@ class SimpleLossWrapper(nn.Module):
         return self.low_level_loss(x.float(), y.float())
 
 
+class DictLossWrapper(SimpleLossWrapper):
+    """sum_key weights[key] * single_loss(input[key], target): one criterion over every entry of a model output that is a dict (a
+    segmentation model's `out` / `aux` heads).  Semantics are torchdistill's DictLossWrapper, [recalled]: the input
+    comes from the io dicts as in `SimpleLossWrapper._extract`, the target is `targets` with `target: {uses_label: True}`, else it is
+    extracted likewise; the weighted terms are added in the order of `weights`.
+    An entry that is a `dense.ResizedLogits` (a segmentation student with `defer_resize`) goes to `dense.seg_cross_entropy` -- the
+    resize happens inside the loss kernels -- when `single_loss` is a CrossEntropyLoss without class weights or label smoothing and
+    with reduction 'mean' or 'sum'; with any other loss it is materialised with `.resized()` first."""
+
+    def __init__(self, single_loss, weights, input, target, **kwargs):
+        super().__init__(single_loss, input, target)
+        self.weights = dict(weights)
+
+    def _fused_ce(self):
+        loss = self.low_level_loss
+        return (type(loss) is nn.CrossEntropyLoss and loss.weight is None and not loss.label_smoothing and
+                loss.reduction in ('mean', 'sum'))
+
+    def forward(self, student_io_dict, teacher_io_dict, targets=None, *args, **kwargs):
+        from .dense import ResizedLogits, seg_cross_entropy
+        x = self._extract(self.input_cfg, student_io_dict, teacher_io_dict)
+        y = targets if self.target_cfg.get('uses_label') else self._extract(self.target_cfg, student_io_dict, teacher_io_dict)
+        total = None
+        for key, weight in self.weights.items():
+            entry = x[key]
+            if isinstance(entry, ResizedLogits):
+                if self._fused_ce():
+                    term = seg_cross_entropy(entry.logits, entry.size, y, ignore_index=self.low_level_loss.ignore_index,
+                                             reduction=self.low_level_loss.reduction)
+                else:
+                    term = self.low_level_loss(entry.resized(), y)
+            else:
+                term = self.low_level_loss(entry, y)
+            total = weight * term if total is None else total + weight * term
+        return total
+
+
 LOW_LEVEL_LOSSES = {'MSELoss': nn.MSELoss, 'L1Loss': nn.L1Loss, 'CrossEntropyLoss': nn.CrossEntropyLoss}
+LOSS_WRAPPERS = {'SimpleLossWrapper': SimpleLossWrapper, 'DictLossWrapper': DictLossWrapper}
+
+
+def poly_lr_scheduler(optimizer, num_iterations, num_epochs, power=0.9):
+    """LambdaLR with (1 - x / (num_iterations * num_epochs)) ** power, x the number of scheduler steps: torchdistill's
+    `poly_lr_scheduler`, [recalled]; stepped per iteration with `scheduling_step: 1`."""
+    from .config import Placeholder
+    for name, value in (('num_iterations', num_iterations), ('num_epochs', num_epochs)):
+        if isinstance(value, Placeholder) or not isinstance(value, (int, float)) or value <= 0:
+            raise ValueError('poly_lr_scheduler: kwarg `{}` is {!r}, not a positive number (a dataset that is not available '
+                             'leaves `utils.dataset.get_num_iterations` unresolved)'.format(name, value))
+    total = float(num_iterations * num_epochs)
+    return torch.optim.lr_scheduler.LambdaLR(optimizer, lambda x: max(1 - x / total, 0.0) ** power)
+
+
+LR_SCHEDULERS = {'poly_lr_scheduler': poly_lr_scheduler}     # looked up before torch.optim.lr_scheduler
 
 
 class WeightedSumLoss(nn.Module):
@@ -150,7 +205,10 @@ class WeightedSumLoss(nn.Module):
             key, ckw = crit_cfg['key'], dict(crit_cfg.get('kwargs') or {})
             if 'criterion_wrapper' in cfg:
                 wkw = dict(cfg['criterion_wrapper'].get('kwargs') or {})
-                term = SimpleLossWrapper(LOW_LEVEL_LOSSES[key](**ckw), **wkw)
+                wrapper_key = cfg['criterion_wrapper'].get('key') or 'SimpleLossWrapper'
+                if wrapper_key not in LOSS_WRAPPERS:
+                    raise KeyError('criterion `{}` is not available'.format(wrapper_key))
+                term = LOSS_WRAPPERS[wrapper_key](LOW_LEVEL_LOSSES[key](**ckw), **wkw)
             elif key in MIDDLE_LEVEL_LOSS_DICT:
                 term = MIDDLE_LEVEL_LOSS_DICT[key](**ckw)
             elif key == 'KDLoss':
@@ -208,18 +266,46 @@ class DistillationStage(object):
         self.t_hooks = ForwardHookManager(self.teacher, t_cfg.get('forward_hook'))
         self.s_hooks = ForwardHookManager(self.student, s_cfg.get('forward_hook'))
         self.criterion = build_criterion(stage_config['criterion'])
+        self._set_defer_resize(s_cfg)
         # as torchdistill does, the optimizer (and the gradient buckets) see the REDESIGNED student: modules left out
         # of `sequential` (avgpool / fc in stage 1) take no part in the step
-        params = [p for p in self.student.parameters() if p.requires_grad]
-        self.reducer = FlatGradAllReducer(params, bucket_mb=bucket_mb)
         o_cfg = stage_config['optimizer']
         okw = dict(o_cfg.get('kwargs') or {})
         if 'lr' in okw:
             okw['lr'] = okw['lr'] * lr_factor
-        self.optimizer = getattr(torch.optim, o_cfg['key'])(params, **okw)
+        if o_cfg.get('module_wise_kwargs'):
+            # one parameter group per entry with the entry's own kwargs over the optimizer's (torchdistill's `module_wise_kwargs`,
+            # [recalled]): PASCAL's aux classifier at ten times the learning rate.  A per-group lr scales like the global one.
+            groups = []
+            for entry in o_cfg['module_wise_kwargs']:
+                group = dict(entry.get('kwargs') or {})
+                if 'lr' in group:
+                    group['lr'] = group['lr'] * lr_factor
+                group['params'] = [p for p in get_module(self.student, entry['module']).parameters() if p.requires_grad]
+                if group['params']:
+                    groups.append(group)
+            params = [p for group in groups for p in group['params']]
+            self.reducer = FlatGradAllReducer(params, bucket_mb=bucket_mb)
+            self.optimizer = getattr(torch.optim, o_cfg['key'])(groups, **okw)
+        else:
+            params = [p for p in self.student.parameters() if p.requires_grad]
+            self.reducer = FlatGradAllReducer(params, bucket_mb=bucket_mb)
+            self.optimizer = getattr(torch.optim, o_cfg['key'])(params, **okw)
         s = stage_config.get('scheduler')
-        self.lr_scheduler = getattr(torch.optim.lr_scheduler, s['key'])(self.optimizer, **(s.get('kwargs') or {})) \
-            if s else None
+        self.lr_scheduler = None
+        # `scheduling_step: k` (> 0): the scheduler steps after every k-th optimizer step instead of once per epoch (torchdistill, [recalled])
+        self.scheduling_step = int((s or {}).get('scheduling_step') or 0)
+        self._optimizer_steps = 0
+        if s:
+            skw = dict(s.get('kwargs') or {})
+            if s['key'] in LR_SCHEDULERS:
+                if 'num_epochs' not in skw and stage_config.get('num_epochs') is not None:
+                    # (the PASCAL entropic-student files indent `num_epochs` / `power` under the `!import_call` of `num_iterations`,
+                    #  where the tag drops them: the stage's own `num_epochs` is what they alias)
+                    skw['num_epochs'] = stage_config['num_epochs']
+                self.lr_scheduler = LR_SCHEDULERS[s['key']](self.optimizer, **skw)
+            else:
+                self.lr_scheduler = getattr(torch.optim.lr_scheduler, s['key'])(self.optimizer, **skw)
         self.student_full.train()
         for path in s_cfg.get('frozen_modules') or list():   # frozen BatchNorm layers keep their statistics
             get_module(student, path).eval()
@@ -394,14 +480,42 @@ class DistillationStage(object):
         self.reducer.all_reduce()
         self.optimizer.step()
         self.reducer.zero_grad()
+        self._optimizer_steps += 1
+        if self.lr_scheduler is not None and self.scheduling_step > 0 and self._optimizer_steps % self.scheduling_step == 0:
+            self.lr_scheduler.step()
 
     def post_epoch_process(self):
-        if self.lr_scheduler is not None:
+        if self.lr_scheduler is not None and self.scheduling_step <= 0:
             self.lr_scheduler.step()
+
+    def _set_defer_resize(self, s_cfg):
+        """A segmentation student whose resized logits only a DictLossWrapper reads hands over `dense.ResizedLogits` instead: every
+        criterion term that reads the model's own output ('.') must be a DictLossWrapper (a term of another kind -- KDLoss, a plain
+        wrapper -- expects tensors), and no forward hook may ask for it."""
+        from .dense import BaseSegmentationModel
+        if not (isinstance(self.student, BaseSegmentationModel) and self.student is self.student_full):
+            return
+        hooked = s_cfg.get('forward_hook') or {}
+        if any(q in ('.', '') for q in list(hooked.get('input') or []) + list(hooked.get('output') or [])):
+            return
+        readers = []
+        for term in self.criterion.terms.values():
+            if isinstance(term, SimpleLossWrapper):
+                cfgs = [c for c in (term.input_cfg, term.target_cfg) if 'module_path' in c and not c.get('is_from_teacher')]
+                if any(c['module_path'] in ('.', '') for c in cfgs):
+                    readers.append(term)
+            elif getattr(term, 'sp', None) in ('.', ''):      # KDLoss reads the student's own output
+                return
+        if readers and all(isinstance(term, DictLossWrapper) for term in readers):
+            self._restore_defer_resize = (self.student, self.student.defer_resize)
+            self.student.defer_resize = True
 
     def clean_modules(self):
         self.t_hooks.clear()
         self.s_hooks.clear()
+        restore = self.__dict__.pop('_restore_defer_resize', None)
+        if restore is not None:
+            restore[0].defer_resize = restore[1]
         # the decoder's output format was switched to bf16 NHWC for THIS stage's bf16 tail: a student that goes on with an f32
         # tail must get f32 NCHW features again (ADVICE r3)
         restore = self.__dict__.pop('_restore_output_format', None)
