@@ -930,6 +930,47 @@ int sc2_seg_ce_backward(const void *logits, int is_bf16, int N, int C, int h, in
                         long long ignore_index, const float *lse, const void *sums, const float *grad_out, int reduction, void *dx,
                         long long dx_stride_n, long long dx_stride_c, long long dx_stride_h, long long dx_stride_w, void *stream);
 
+/* Segmentation training input (csrc/seg_augment.hip): the PASCAL VOC augmentation chain of a whole batch -- Pillow's bilinear resize
+ * of the 8-bit RGB image and its nearest resize of the 8-bit mask, horizontal flip, pad right / bottom, crop, ToTensor, Normalize, and
+ * the collator's padded batch -- from the source bytes straight to the batch tensors.  Only the output window is computed: neither the
+ * resized image nor the intermediate of Pillow's two passes is written to memory.  tests/ref_pil_resize.py restates the two resizes;
+ * the result equals the host chain (Pillow + torch) bit for bit.
+ * buf    : nbytes (1 .. 2^31-1) of device memory holding every sample's image (h*w*3 bytes, HWC, rows dense) and mask (h*w bytes).
+ * desc   : int32 [n, SC2_SEG_AUGMENT_DESC_INTS] on the device, one row per sample:
+ *            [0] image offset in buf   [1] mask offset in buf   [2] h  [3] w (source)   [4] nh  [5] nw (resized)   [6] flip (0 / 1)
+ *            [7] top  [8] left (origin of the output window in the padded, flipped, resized image)
+ *            [9] ext_h  [10] ext_w (extent of the sample inside its [oh, ow] slot)   [11..15] unused by the kernels (the wrapper keeps
+ *            the padded size there to refuse a window outside the padded image before the launch)
+ * Output pixel (y, x) of sample i: outside ext_h x ext_w the image is 0.0f and the target 255 (the collator's fill); else it shows
+ * position (top + y, left + x) of the padded image: beyond nh x nw the image is (0 / 255 - mean) / std and the target 255 (the pad
+ * area); else the resized pixel of that row and of column left + x, or nw - 1 - (left + x) when flipped, as
+ * (float(p) / 255.0f - mean[c]) / std[c] with two correctly rounded f32 divisions, and the resized mask's byte as int64.
+ * Image pixels: Pillow's ImagingResample with the bilinear filter -- per axis n_in -> n_out in float64, every operation rounded once:
+ * scale = n_in / n_out, support = filterscale = max(scale, 1), center = (xx + 0.5) * scale, first = max(int(center - support + 0.5), 0),
+ * count = min(int(center + support + 0.5), n_in) - first, weight max(0, 1 - |(x + first - center + 0.5) * (1 / filterscale)|), weights
+ * divided by their left-to-right sum, k = int(0.5 + w * 2^22); a pass is clip((2^21 + sum(pixel * k)) >> 22, 0, 255); the horizontal
+ * pass first, to 8 bits, the vertical pass on those.  (A pass of equal lengths, which Pillow skips, has the one coefficient 2^22.)
+ * Mask pixels: Pillow's nearest resize -- source index int(xo) with xo = a * 0.5 at output 0 and xo += a per output, a = n_in / n_out.
+ * mean, std : three f32 each, HOST memory (std != 0).
+ * images : f32 [n,3,oh,ow];  targets : int64 [n,oh,ow];  both contiguous, every element of an accepted sample written.
+ * ws     : sc2_seg_augment_workspace(n, oh, ow) bytes, 4-byte aligned.  Per sample ow column entries, then oh row entries, of
+ *          SC2_SEG_AUGMENT_ENTRY_INTS int32 each: first source index, count, nine coefficients, the nearest resize's source index;
+ *          entries of positions that show no resized pixel are zero.
+ * status : int32 [n], written for every sample: 0, or SC2_SEG_AUGMENT_RATIO when an axis shrinks by more than 4 (filterscale > 4: more
+ *          than nine taps), or SC2_SEG_AUGMENT_BAD for a row with offsets outside buf, sides outside 1 .. SC2_SEG_AUGMENT_MAX_SIDE, a
+ *          negative origin or an extent beyond the slot.  Such a sample's outputs and tables are left unwritten; no address is formed
+ *          from it.  The caller redoes the batch on the host.
+ * Two launches on `stream` (tables, then one workgroup per 16 x 64 output tile), no atomics, no host synchronisation. */
+#define SC2_SEG_AUGMENT_DESC_INTS 16
+#define SC2_SEG_AUGMENT_ENTRY_INTS 12
+#define SC2_SEG_AUGMENT_MAX_SIDE 16384
+#define SC2_SEG_AUGMENT_MAX_BATCH 65535
+#define SC2_SEG_AUGMENT_RATIO 1
+#define SC2_SEG_AUGMENT_BAD 2
+long long sc2_seg_augment_workspace(int n, int oh, int ow);
+int sc2_seg_augment(const uint8_t *buf, long long nbytes, const int32_t *desc, int n, int oh, int ow, const float *mean,
+                    const float *std, float *images, long long *targets, void *ws, int32_t *status, void *stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* COCO box AP (csrc/coco.hip): COCOeval's `bbox` protocol with its default parameters, written from the published     */
 /* protocol.  tests/ref_coco.py restates it as a sequential float64 loop; both kernels reproduce that bit for bit.    */

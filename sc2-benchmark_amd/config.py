@@ -6,7 +6,9 @@ into packages that are not installed here (`torchvision`, `torchdistill`) or tha
 (`sc2bench`).  This loader resolves
 
 * `sc2bench.*`      -> the registries of this package (same keys: layers, backbones, losses, analyzers),
-* `torchvision.datasets.*` -> this module's `ImageFolder` (root/<class>/<image>; a missing directory raises on first
+* `torchvision.datasets.VOCSegmentation` -> this module's class of that name, `custom.transform.*` (the PASCAL pair transforms of
+  the reference's task scripts) -> `sc2bench_amd.transforms.CUSTOM_TRANSFORM_DICT`,
+* other `torchvision.datasets.*` -> this module's `ImageFolder` (root/<class>/<image>; a missing directory raises on first
   use unless SC2_SYNTHETIC_DATA=1 opts in to random images),
 * `torchvision.models.resnet.*Weights` -> an inert enum (pretrained weights need the network),
 * `torchvision.transforms.{Compose,Resize,CenterCrop,ToTensor,Normalize,RandomResizedCrop,RandomHorizontalFlip}` ->
@@ -124,6 +126,60 @@ class ImageFolder(torch.utils.data.Dataset):
         return img, target
 
 
+def _given(transform):
+    return transform is not None and not isinstance(transform, Placeholder)
+
+
+class VOCSegmentation(torch.utils.data.Dataset):
+    """`torchvision.datasets.VOCSegmentation`: root/VOCdevkit/VOC<year>/{JPEGImages/<id>.jpg, SegmentationClass/<id>.png}, the ids of
+    ImageSets/Segmentation/<image_set>.txt.  `download` is accepted and ignored: nothing here fetches.  The tree is read on first use,
+    so a config whose dataset directory does not exist still PARSES; `len()` and indexing then raise FileNotFoundError.
+    `__getitem__` -> `transforms(image, target)` of the RGB image and the mask as it opens.  When `transforms` can plan the sample
+    (`transforms.CustomCompose.plan`: the PASCAL chains) and `hip.host_policy.seg_augment_hip` is on, the item is
+    (`DeferredSegSample`, None) instead -- source bytes and the drawn parameters; the collate functions and
+    `DeferredSegBatch.materialize` finish it, on the device where there is one."""
+
+    def __init__(self, root=None, year='2012', image_set='train', download=False, transform=None, target_transform=None, transforms=None):
+        self.root = None if root is None else os.path.expanduser(str(root))
+        self.year, self.image_set = str(year), image_set
+        self.transform, self.target_transform, self.transforms = transform, target_transform, transforms
+        self._pairs = None
+
+    def _scan(self):
+        if self._pairs is not None:
+            return
+        base = os.path.join(self.root or '', 'VOCdevkit', 'VOC{}'.format(self.year))
+        split = os.path.join(base, 'ImageSets', 'Segmentation', '{}.txt'.format(self.image_set))
+        if self.root is None or not os.path.isfile(split):
+            raise FileNotFoundError('VOCSegmentation: {} does not exist (nothing is downloaded here)'.format(split))
+        with open(split) as f:
+            ids = [line.strip() for line in f if line.strip()]
+        self._pairs = [(os.path.join(base, 'JPEGImages', i + '.jpg'), os.path.join(base, 'SegmentationClass', i + '.png')) for i in ids]
+
+    def __len__(self):
+        self._scan()
+        return len(self._pairs)
+
+    def __getitem__(self, index):
+        self._scan()
+        from PIL import Image
+        image_path, mask_path = self._pairs[index]
+        image, target = Image.open(image_path).convert('RGB'), Image.open(mask_path)
+        if _given(self.transforms):
+            plan = getattr(self.transforms, 'plan', None)
+            if plan is not None:
+                from . import hip
+                deferred = plan(image, target) if hip.host_policy.seg_augment_hip else None
+                if deferred is not None:
+                    return deferred, None
+            return self.transforms(image, target)
+        if _given(self.transform):
+            image = self.transform(image)
+        if _given(self.target_transform):
+            target = self.target_transform(target)
+        return image, target
+
+
 class _WeightsEnum(object):
     """Inert stand-in for torchvision's `ResNet50_Weights` etc. (`!getattr [*, 'IMAGENET1K_V1']` must resolve)."""
 
@@ -176,8 +232,14 @@ def resolve(key):
         return _sc2bench_attr(key)
     if key == 'utils.dataset.get_num_iterations':
         return get_num_iterations
+    if key == 'torchvision.datasets.VOCSegmentation':
+        return VOCSegmentation
     if key.startswith('torchvision.datasets.'):
         return ImageFolder
+    if key.startswith('custom.transform.'):
+        from . import transforms as tr
+        if key.split('.')[-1] in tr.CUSTOM_TRANSFORM_DICT:
+            return tr.CUSTOM_TRANSFORM_DICT[key.split('.')[-1]]
     if key.startswith('torchvision.models.') and key.endswith('_Weights'):
         return _WeightsEnum(key)
     if key.startswith('torchvision.transforms.'):

@@ -1,0 +1,291 @@
+// The PASCAL VOC augmentation chain of a batch, from the source bytes to the finished training tensors (script/task/custom/transform.py
+// of the reference: CustomRandomResize -> [flip] -> [pad + crop] -> ToTensor -> Normalize, then the collator's padded batch):
+//   seg_augment_tables_kernel   per sample, the window's rows and columns: Pillow's bilinear bounds and 22-bit fixed-point coefficients
+//                               (float64, every operation rounded once) and the nearest resize's source indices (a running float64 sum)
+//   seg_augment_tile_kernel     per (sample, 16 output rows, 64 output columns): the horizontally resampled source rows the band needs
+//                               as 8-bit pixels (one word each) in LDS, the vertical pass from there, `(p / 255 - mean) / std`, the mask gather
+// Only the output window is computed; neither the resized image nor the intermediate of Pillow's two passes exists in memory.
+// include/sc2_bottleneck.h states the contract; tests/ref_pil_resize.py restates the two resizes.
+// Plain kernels: every index checked against its array before use, no atomics, no workgroup waits for another.
+#include "sc2_common.h"
+
+#pragma clang fp contract(off)   // int() truncates and the sums are ordered: a fused multiply-add in `center` moves xmin for some sizes
+
+namespace {
+
+constexpr int SA_DESC = SC2_SEG_AUGMENT_DESC_INTS;       // int32 words of a descriptor row
+constexpr int SA_ENTRY = SC2_SEG_AUGMENT_ENTRY_INTS;     // int32 words of a table entry: first, count, 9 coefficients, nearest index
+constexpr int SA_TAPS = 9;                               // ksize at filterscale 4
+constexpr int SA_BITS = 22;                              // Pillow's PRECISION_BITS for 8-bit channels
+constexpr int SA_TH = 16, SA_TW = 64;                    // output rows and columns of a tile
+constexpr int SA_THREADS = 256;
+constexpr int SA_ROWS = 4 * SA_TH + SA_TAPS;             // source rows a band can need: (TH - 1) * 4 + 2 * 4 + 1 and some
+constexpr int SA_MAX_SIDE = SC2_SEG_AUGMENT_MAX_SIDE;
+
+struct Desc {
+    int img, mask, h, w, nh, nw, flip, top, left, eh, ew;
+};
+
+__device__ __forceinline__ Desc sa_desc(const int32_t *table, int i) {
+    const int32_t *d = table + (size_t)i * SA_DESC;
+    Desc s;
+    s.img = d[0]; s.mask = d[1]; s.h = d[2]; s.w = d[3]; s.nh = d[4]; s.nw = d[5];
+    s.flip = d[6]; s.top = d[7]; s.left = d[8]; s.eh = d[9]; s.ew = d[10];
+    return s;
+}
+
+// 0: the kernels take the sample; SC2_SEG_AUGMENT_RATIO: a pass shrinks by more than 4; SC2_SEG_AUGMENT_BAD: a field no launch may
+// follow (the wrapper refuses those before the launch; the kernels make sure on their own that no such row moves an address)
+__device__ __forceinline__ int sa_status(const Desc &s, long long nbytes, int OH, int OW) {
+    const bool sides = s.h >= 1 && s.w >= 1 && s.nh >= 1 && s.nw >= 1 && s.h <= SA_MAX_SIDE && s.w <= SA_MAX_SIDE && s.nh <= SA_MAX_SIDE &&
+                       s.nw <= SA_MAX_SIDE;
+    if (!sides) return SC2_SEG_AUGMENT_BAD;
+    const long long px = (long long)s.h * s.w;
+    const bool ok = s.img >= 0 && s.mask >= 0 && s.img + 3 * px <= nbytes && s.mask + px <= nbytes && s.top >= 0 && s.left >= 0 &&
+                    s.top <= SA_MAX_SIDE && s.left <= SA_MAX_SIDE && s.eh >= 0 && s.ew >= 0 && s.eh <= OH && s.ew <= OW &&
+                    (s.flip == 0 || s.flip == 1);
+    if (!ok) return SC2_SEG_AUGMENT_BAD;
+    if (s.h > 4 * s.nh || s.w > 4 * s.nw) return SC2_SEG_AUGMENT_RATIO;
+    return 0;
+}
+
+// The table of sample i: OW column entries, then OH row entries.
+__device__ __forceinline__ int32_t *sa_table(void *ws, int i, int OH, int OW) {
+    return static_cast<int32_t *>(ws) + (size_t)i * (OH + OW) * SA_ENTRY;
+}
+
+struct TableArgs {
+    const int32_t *desc;
+    void *ws;
+    int32_t *status;
+    long long nbytes;
+    int OH, OW, blocks;      // blocks: workgroups along x that compute coefficients; one more walks the nearest sums
+};
+
+// Pillow's precompute_coeffs + normalize_coeffs_8bpc for output index xx of an axis n_in -> n_out with the bilinear filter.
+__device__ __forceinline__ void sa_coeffs(int n_in, int n_out, int xx, int32_t *e) {
+    const double scale = (double)n_in / (double)n_out;
+    const double fs = scale < 1.0 ? 1.0 : scale;
+    const double support = fs, ss = 1.0 / fs;
+    const double center = ((double)xx + 0.5) * scale;
+    int xmin = (int)(center - support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + support + 0.5);
+    if (xmax > n_in) xmax = n_in;
+    xmax -= xmin;
+    if (xmax > SA_TAPS) xmax = SA_TAPS;      // (cannot happen at filterscale <= 4: 2 * support + 1 <= 9)
+    if (xmax < 0) xmax = 0;
+    double wt[SA_TAPS];
+    double ww = 0.0;
+#pragma unroll
+    for (int x = 0; x < SA_TAPS; ++x) {
+        const double v = fabs(((double)(x + xmin) - center + 0.5) * ss);
+        wt[x] = (x < xmax && v < 1.0) ? 1.0 - v : 0.0;
+        if (x < xmax) ww += wt[x];
+    }
+    e[0] = xmin;
+    e[1] = xmax;
+#pragma unroll
+    for (int x = 0; x < SA_TAPS; ++x) {
+        const double p = ww != 0.0 ? wt[x] / ww : wt[x];
+        e[2 + x] = x < xmax ? (int)(0.5 + p * (double)(1 << SA_BITS)) : 0;
+    }
+}
+
+__global__ __launch_bounds__(SA_THREADS) void seg_augment_tables_kernel(const TableArgs a) {
+    const int i = blockIdx.z, axis = blockIdx.y;      // axis 0: columns, 1: rows
+    const Desc s = sa_desc(a.desc, i);
+    const int st = sa_status(s, a.nbytes, a.OH, a.OW);
+    if (blockIdx.x == 0 && axis == 0 && threadIdx.x == 0) a.status[i] = st;
+    if (st != 0) return;
+    int32_t *tab = sa_table(a.ws, i, a.OH, a.OW) + (axis == 0 ? 0 : (size_t)a.OW * SA_ENTRY);
+    const int len = axis == 0 ? a.OW : a.OH;
+    const int n_in = axis == 0 ? s.w : s.h, n_out = axis == 0 ? s.nw : s.nh;
+    const int origin = axis == 0 ? s.left : s.top, ext = axis == 0 ? s.ew : s.eh;
+    const bool flip = axis == 0 && s.flip != 0;
+    if ((int)blockIdx.x < a.blocks) {
+        const int o = blockIdx.x * SA_THREADS + threadIdx.x;
+        if (o >= len) return;
+        const int r = origin + o;                    // position in the padded, flipped, resized image
+        int32_t e[SA_ENTRY];
+        if (o < ext && r < n_out) {
+            sa_coeffs(n_in, n_out, flip ? n_out - 1 - r : r, e);
+        } else {
+#pragma unroll
+            for (int k = 0; k < SA_ENTRY; ++k) e[k] = 0;
+        }
+        int32_t *dst = tab + (size_t)o * SA_ENTRY;
+#pragma unroll
+        for (int k = 0; k < SA_ENTRY - 1; ++k) dst[k] = e[k];
+        if (!(o < ext && r < n_out)) dst[SA_ENTRY - 1] = 0;
+        return;
+    }
+    // ImagingScaleAffine's index table: a running sum, so entry j depends on the j additions in front of it -- one lane walks it
+    if (threadIdx.x != 0) return;
+    const double step = (double)n_in / (double)n_out;
+    double xo = step * 0.5;
+    int last = origin + ext;                         // resized positions [origin, last) are in the window
+    if (last > n_out) last = n_out;
+    const int lo = flip ? n_out - last : origin, hi = flip ? n_out - origin : last;      // the same range as resized indices
+    for (int j = 0; j < hi; ++j) {
+        if (j >= lo) {
+            int src = (int)xo;
+            if (src > n_in - 1) src = n_in - 1;
+            const int o = (flip ? n_out - 1 - j : j) - origin;
+            if (o >= 0 && o < len) tab[(size_t)o * SA_ENTRY + SA_ENTRY - 1] = src;
+        }
+        xo += step;
+    }
+}
+
+// The three bytes of the pixel at byte offset `off` of an image of `bytes` bytes, R in the low byte: one unaligned four-byte load where
+// the byte behind the pixel is still the image's (every pixel but the last), three byte loads otherwise.
+__device__ __forceinline__ uint32_t sa_pixel(const uint8_t *img, size_t off, size_t bytes) {
+    if (off + 4 <= bytes) {
+        uint32_t v;
+        __builtin_memcpy(&v, img + off, 4);
+        return v;
+    }
+    return (uint32_t)img[off] | (uint32_t)img[off + 1] << 8 | (uint32_t)img[off + 2] << 16;
+}
+
+struct TileArgs {
+    const uint8_t *buf;
+    const int32_t *desc;
+    const void *ws;
+    float *images;
+    long long *targets;
+    long long nbytes;
+    float mean[3], std[3];
+    int OH, OW;
+};
+
+__global__ __launch_bounds__(SA_THREADS) void seg_augment_tile_kernel(const TileArgs a) {
+    __shared__ uint32_t hbuf[SA_ROWS * SA_TW];      // [source row][tile column]: the horizontal pass's 8-bit output, R | G << 8 | B << 16
+    const int i = blockIdx.z;
+    const Desc s = sa_desc(a.desc, i);
+    if (sa_status(s, a.nbytes, a.OH, a.OW) != 0) return;      // (wave-uniform: the whole workgroup leaves)
+    const int y0 = blockIdx.y * SA_TH, x0 = blockIdx.x * SA_TW;
+    const int32_t *cols = static_cast<const int32_t *>(a.ws) + (size_t)i * (a.OH + a.OW) * SA_ENTRY;
+    const int32_t *rows = cols + (size_t)a.OW * SA_ENTRY;
+    // the part of the tile that shows resized pixels: rows [y0, yv), columns [x0, xv)
+    const int yv = min(min(y0 + SA_TH, s.eh), s.nh - s.top), xv = min(min(x0 + SA_TW, s.ew), s.nw - s.left);
+    const int lx = threadIdx.x & (SA_TW - 1), ly = threadIdx.x / SA_TW;      // a wave owns a row, its lanes the columns
+    const int x = x0 + lx;
+    int r_first = 0, r_count = 0;
+    if (yv > y0 && xv > x0) {
+        // the bounds do not decrease with the output index, so the band's source rows run from its first row's to its last row's
+        const int32_t *ef = rows + (size_t)y0 * SA_ENTRY, *el = rows + (size_t)(yv - 1) * SA_ENTRY;
+        r_first = ef[0];
+        r_count = min(el[0] + el[1] - r_first, SA_ROWS);
+        if (x < xv) {
+            const int32_t *e = cols + (size_t)x * SA_ENTRY;
+            const int first = e[0], count = e[1];
+            int k[SA_TAPS];
+#pragma unroll
+            for (int t = 0; t < SA_TAPS; ++t) k[t] = e[2 + t];
+            const uint8_t *img = a.buf + s.img;
+            const size_t img_bytes = (size_t)s.h * s.w * 3;
+            for (int r = ly; r < r_count; r += SA_THREADS / SA_TW) {
+                const int sr = min(max(r_first + r, 0), s.h - 1);
+                int acc0 = 1 << (SA_BITS - 1), acc1 = acc0, acc2 = acc0;
+#pragma unroll
+                for (int t = 0; t < SA_TAPS; ++t) {
+                    if (t < count) {
+                        const uint32_t p = sa_pixel(img, ((size_t)sr * s.w + min(max(first + t, 0), s.w - 1)) * 3, img_bytes);
+                        acc0 += (int)(p & 0xFFu) * k[t];
+                        acc1 += (int)((p >> 8) & 0xFFu) * k[t];
+                        acc2 += (int)((p >> 16) & 0xFFu) * k[t];
+                    }
+                }
+                hbuf[r * SA_TW + lx] = (uint32_t)min(max(acc0 >> SA_BITS, 0), 255) | (uint32_t)min(max(acc1 >> SA_BITS, 0), 255) << 8 |
+                                       (uint32_t)min(max(acc2 >> SA_BITS, 0), 255) << 16;
+            }
+        }
+    }
+    __syncthreads();
+    if (x >= a.OW) return;
+    const size_t plane = (size_t)a.OH * a.OW;
+    float *out = a.images + (size_t)i * 3 * plane;
+    long long *tgt = a.targets + (size_t)i * plane;
+    const uint8_t *mask = a.buf + s.mask;
+    const int mcol = x < xv ? min(max(cols[(size_t)x * SA_ENTRY + SA_ENTRY - 1], 0), s.w - 1) : 0;
+    for (int y = y0 + ly; y < min(y0 + SA_TH, a.OH); y += SA_THREADS / SA_TW) {
+        float v0, v1, v2;
+        long long label = 255;
+        if (y >= s.eh || x >= s.ew) {                 // outside the sample's extent: the collator's fill
+            v0 = v1 = v2 = 0.0f;
+        } else if (y >= yv || x >= xv) {              // pad_if_smaller's area: a zero pixel, normalised
+            v0 = __fdiv_rn(0.0f - a.mean[0], a.std[0]);
+            v1 = __fdiv_rn(0.0f - a.mean[1], a.std[1]);
+            v2 = __fdiv_rn(0.0f - a.mean[2], a.std[2]);
+        } else {
+            const int32_t *e = rows + (size_t)y * SA_ENTRY;
+            const int first = e[0] - r_first, count = e[1];
+            int acc0 = 1 << (SA_BITS - 1), acc1 = acc0, acc2 = acc0;
+#pragma unroll
+            for (int t = 0; t < SA_TAPS; ++t) {
+                if (t < count) {
+                    const int kt = e[2 + t];
+                    const uint32_t p = hbuf[min(max(first + t, 0), SA_ROWS - 1) * SA_TW + lx];
+                    acc0 += (int)(p & 0xFFu) * kt;
+                    acc1 += (int)((p >> 8) & 0xFFu) * kt;
+                    acc2 += (int)((p >> 16) & 0xFFu) * kt;
+                }
+            }
+            const float p0 = (float)min(max(acc0 >> SA_BITS, 0), 255), p1 = (float)min(max(acc1 >> SA_BITS, 0), 255),
+                        p2 = (float)min(max(acc2 >> SA_BITS, 0), 255);
+            v0 = __fdiv_rn(__fdiv_rn(p0, 255.0f) - a.mean[0], a.std[0]);
+            v1 = __fdiv_rn(__fdiv_rn(p1, 255.0f) - a.mean[1], a.std[1]);
+            v2 = __fdiv_rn(__fdiv_rn(p2, 255.0f) - a.mean[2], a.std[2]);
+            const int mrow = min(max(e[SA_ENTRY - 1], 0), s.h - 1);
+            label = (long long)mask[(size_t)mrow * s.w + mcol];
+        }
+        const size_t o = (size_t)y * a.OW + x;
+        out[o] = v0;
+        out[plane + o] = v1;
+        out[2 * plane + o] = v2;
+        tgt[o] = label;
+    }
+}
+
+bool sa_sizes_ok(int n, int oh, int ow) {
+    return n >= 1 && n <= SC2_SEG_AUGMENT_MAX_BATCH && oh >= 1 && ow >= 1 && oh <= SA_MAX_SIDE && ow <= SA_MAX_SIDE;
+}
+
+}  // namespace
+
+extern "C" long long sc2_seg_augment_workspace(int n, int oh, int ow) {
+    if (!sa_sizes_ok(n, oh, ow)) return 0;
+    return (long long)n * (oh + ow) * SA_ENTRY * (long long)sizeof(int32_t);
+}
+
+extern "C" int sc2_seg_augment(const uint8_t *buf, long long nbytes, const int32_t *desc, int n, int oh, int ow, const float *mean,
+                               const float *std, float *images, long long *targets, void *ws, int32_t *status, void *stream) {
+    SC2_REQUIRE(sa_sizes_ok(n, oh, ow), SC2_ERR_UNSUPPORTED, "seg_augment: %d samples of %dx%d (1..%d samples, sides 1..%d)", n, oh, ow,
+                SC2_SEG_AUGMENT_MAX_BATCH, SA_MAX_SIDE);
+    SC2_REQUIRE(nbytes >= 1 && nbytes <= 0x7FFFFFFFLL, SC2_ERR_UNSUPPORTED, "seg_augment: a source buffer of %lld bytes (1..2^31-1)", nbytes);
+    SC2_REQUIRE(buf && desc && mean && std && images && targets && ws && status, SC2_ERR_INVALID_ARG, "seg_augment: null pointer");
+    SC2_REQUIRE(((reinterpret_cast<uintptr_t>(desc) | reinterpret_cast<uintptr_t>(images) | reinterpret_cast<uintptr_t>(ws) |
+                  reinterpret_cast<uintptr_t>(status)) & 3u) == 0 && (reinterpret_cast<uintptr_t>(targets) & 7u) == 0,
+                SC2_ERR_INVALID_ARG, "seg_augment: misaligned pointer");
+    for (int c = 0; c < 3; ++c)
+        SC2_REQUIRE(std[c] != 0.0f, SC2_ERR_INVALID_ARG, "seg_augment: std[%d] is zero", c);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    TableArgs t;
+    t.desc = desc; t.ws = ws; t.status = status; t.nbytes = nbytes; t.OH = oh; t.OW = ow;
+    t.blocks = ((oh > ow ? oh : ow) + SA_THREADS - 1) / SA_THREADS;
+    hipLaunchKernelGGL(seg_augment_tables_kernel, dim3((unsigned)t.blocks + 1, 2, (unsigned)n), dim3(SA_THREADS), 0, s, t);
+    SC2_CHECK_LAUNCH();
+    TileArgs a;
+    a.buf = buf; a.desc = desc; a.ws = ws; a.images = images; a.targets = targets; a.nbytes = nbytes;
+    for (int c = 0; c < 3; ++c) {
+        a.mean[c] = mean[c];
+        a.std[c] = std[c];
+    }
+    a.OH = oh; a.OW = ow;
+    const dim3 grid((unsigned)((ow + SA_TW - 1) / SA_TW), (unsigned)((oh + SA_TH - 1) / SA_TH), (unsigned)n);
+    hipLaunchKernelGGL(seg_augment_tile_kernel, grid, dim3(SA_THREADS), 0, s, a);
+    SC2_CHECK_LAUNCH();
+    return SC2_OK;
+}

@@ -181,8 +181,12 @@ def _evaluate_segmentation(model, data_loader, device, num_classes, evaluator, m
     fused = callable(getattr(model, 'predict', None))
     t0 = time.perf_counter()
     seen = 0
+    from .transforms import DeferredSegBatch
     for i, batch in enumerate(data_loader):
-        images, targets = batch[0], batch[1]
+        if isinstance(batch, DeferredSegBatch):     # a planned PASCAL batch: resize, ToTensor and Normalize run here, on `device`
+            images, targets = batch.materialize(device)
+        else:
+            images, targets = batch[0], batch[1]
         if isinstance(images, torch.Tensor):
             images = images.to(device, non_blocking=True)
         if isinstance(targets, torch.Tensor):

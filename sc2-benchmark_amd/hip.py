@@ -38,7 +38,7 @@ ABI_SYMBOLS = [
     'sc2_mse_partial_len', 'sc2_mse_sum_bf16', 'sc2_mse_grad_bf16', 'sc2_relu_bwd_bf16', 'sc2_relu_bwd_mse_bf16',
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
-    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
+    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_seg_augment_workspace', 'sc2_seg_augment', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
     'sc2_jpeg_max_bytes', 'sc2_jpeg_tensor_codec', 'sc2_jpeg_image_max_bytes', 'sc2_jpeg_image_workspace_bytes', 'sc2_jpeg_image_codec',
     'sc2_rcnn_resize_u8', 'sc2_rcnn_normalize_pad',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
@@ -74,6 +74,9 @@ JPEG_GREY, JPEG_RGB = 0, 1
 JPEG_HEADER_BYTES = {0: 328, 1: 623}     # SC2_JPEG_HEADER_GREY / _RGB: a file is header + segment + 2
 JPEG_NEGATIVE_MIN, JPEG_ZERO_MAX, JPEG_NOT_FINITE = 1, 2, 4     # SC2_JPEG_* status bits
 JPEG_IMAGE_MAX_SIDE = 2048       # SC2_JPEG_IMAGE_MAX_SIDE
+SEG_AUGMENT_DESC_INTS, SEG_AUGMENT_ENTRY_INTS = 16, 12      # SC2_SEG_AUGMENT_*
+SEG_AUGMENT_MAX_SIDE, SEG_AUGMENT_MAX_BATCH = 16384, 65535
+SEG_AUGMENT_RATIO, SEG_AUGMENT_BAD = 1, 2
 JPEG_IMAGE_CHUNK_BLOCKS = 128    # SC2_JPEG_IMAGE_CHUNK_BLOCKS
 
 
@@ -152,6 +155,7 @@ class HostPolicy(object):
     jpeg_codec_hip = True      # transforms.PILTensorModule(format='JPEG') of f32 device tensors up to 64 x 64 on sc2_jpeg_tensor_codec (False: PIL per channel group on the host, A/B; tools/jpeg_codec_times.py: 0.36 against 42.7 ms at [1,512,28,28])
     jpeg_image_hip = True      # transforms.PILImageModule(format='JPEG').forward_batch of equal-size RGB / grey PIL images up to 2048 x 2048 on sc2_jpeg_image_codec (False: PIL per image on the host, A/B; tools/jpeg_image_times.py, codec + ToTensor + Normalize to the classifier input: 0.39 against 0.50 ms at [1,3,224,224], 10.4 against 174 ms at [256,3,224,224])
     rcnn_input_hip = True      # detection.RCNNTransformWithCompression (eval, plain JPEG, f32 RGB device images): resize -> codec -> normalise + pad per image on sc2_rcnn_resize_u8 + sc2_jpeg_image_codec + sc2_rcnn_normalize_pad, one read-back per list (False: the reference's loop through Pillow on the host, A/B; tools/rcnn_input_times.py, 480 x 640 -> 800 x 1066 at quality 90: 2.79 against 25.7 ms at one image per call, 16.0 against 88.3 ms at six; the two new kernels alone 0.009 ms each, the codec 2.63 ms)
+    seg_augment_hip = True     # transforms.DeferredSegBatch.materialize (the PASCAL CustomCompose chain, planned in the data-loader workers) on sc2_seg_augment: one copy up and two launches per batch (False: Pillow + torch on the host with the recorded draws, A/B; tools/seg_augment_times.py, 16 sources of 375 x 500 -> 513 x 513: 0.38 ms per batch with the copy up and the read-back, the launches alone 0.102 ms, against 86.0 ms through Pillow on one core)
     seg_predict_hip = True     # dense.seg_labels (BaseSegmentationModel.predict, SegEvaluator.update_logits) of device tensors on sc2_seg_predict (False: interpolate + argmax + bincount, A/B)
     seg_loss_hip = True        # dense.seg_cross_entropy (DictLossWrapper over a deferred-resize segmentation student) of device tensors on sc2_seg_ce_forward + sc2_seg_ce_backward (False: F.interpolate + F.cross_entropy + autograd, A/B; tools/seg_loss_times.py, out + aux forward + backward at [8,21,65,65] -> 513 x 513: 1.27 against 2.70 ms with f32 logits, 1.27 against 1.72 ms with bf16, 20 against 707 MB of peak allocation)
 
@@ -344,6 +348,9 @@ def lib():
     L.sc2_jpeg_image_codec.argtypes = [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, i64, vp]
     L.sc2_rcnn_resize_u8.argtypes = [vp, i64, i64, i64, i32, i32, i32, vp, i32, i32, vp, vp]
     L.sc2_rcnn_normalize_pad.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp]
+    L.sc2_seg_augment_workspace.argtypes = [i32, i32, i32]
+    L.sc2_seg_augment_workspace.restype = i64
+    L.sc2_seg_augment.argtypes = [vp, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.sc2_rans_host_tables_create.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp)]
     L.sc2_rans_host_tables_destroy.argtypes = [vp]
     L.sc2_rans_host_tables_destroy.restype = None
@@ -1490,6 +1497,102 @@ def rcnn_normalize_pad(pixels_u8, mean, std, out_slot, tag=None):
     with _timed(tag or 'rcnn_normalize_pad'):
         _check(lib().sc2_rcnn_normalize_pad(_ptr(pixels_u8), C, h, w, fm, fs, _ptr(out_slot.detach()), Hp, Wp, _stream()), 'rcnn_normalize_pad')
     return out_slot
+
+
+# --------------------------------------------------------------------------------------------- #
+# segmentation training input: the PASCAL augmentation chain of a batch from its source bytes (csrc/seg_augment.hip)
+# --------------------------------------------------------------------------------------------- #
+SEG_AUGMENT_FIELDS = ('image_offset', 'mask_offset', 'h', 'w', 'nh', 'nw', 'flip', 'top', 'left', 'ext_h', 'ext_w', 'pad_h', 'pad_w')
+SegAugment = collections.namedtuple('SegAugment', ['images', 'targets', 'status', 'workspace'])
+
+
+def seg_augment_desc(**fields):
+    """One descriptor row (int32 [SEG_AUGMENT_DESC_INTS]) from SEG_AUGMENT_FIELDS by name; pad_h / pad_w (the padded size, which only
+    `seg_augment_check` reads) default to max(nh, top + ext_h) / max(nw, left + ext_w)."""
+    import numpy as np
+    fields.setdefault('pad_h', max(fields['nh'], fields['top'] + fields['ext_h']))
+    fields.setdefault('pad_w', max(fields['nw'], fields['left'] + fields['ext_w']))
+    row = np.zeros(SEG_AUGMENT_DESC_INTS, dtype=np.int32)
+    for k, name in enumerate(SEG_AUGMENT_FIELDS):
+        row[k] = int(fields.pop(name))
+    assert not fields, 'seg_augment_desc: unknown fields {}'.format(sorted(fields))
+    return row
+
+
+def seg_augment_check(desc, nbytes, oh, ow):
+    """Refuses a malformed descriptor table on the host, before any launch (ValueError naming the sample and the field): sides below
+    1 or above SEG_AUGMENT_MAX_SIDE, offsets outside the buffer, a flip that is not 0 / 1, an extent outside its slot, a padded size
+    smaller than the resized one, a window outside the padded image.  desc: integer array [n, SEG_AUGMENT_DESC_INTS]."""
+    import numpy as np
+    desc = np.asarray(desc)
+    if desc.ndim != 2 or desc.shape[1] != SEG_AUGMENT_DESC_INTS or desc.shape[0] < 1 or desc.shape[0] > SEG_AUGMENT_MAX_BATCH:
+        raise ValueError('seg_augment: a descriptor table [1..{}, {}] is required, got {}'.format(
+            SEG_AUGMENT_MAX_BATCH, SEG_AUGMENT_DESC_INTS, desc.shape))
+    if not (1 <= oh <= SEG_AUGMENT_MAX_SIDE and 1 <= ow <= SEG_AUGMENT_MAX_SIDE):
+        raise ValueError('seg_augment: a {} x {} output slot (sides 1..{})'.format(oh, ow, SEG_AUGMENT_MAX_SIDE))
+    if not 1 <= nbytes <= 0x7FFFFFFF:
+        raise ValueError('seg_augment: a source buffer of {} bytes (1..2^31-1)'.format(nbytes))
+    for i, row in enumerate(desc.tolist()):
+        f = dict(zip(SEG_AUGMENT_FIELDS, row))
+
+        def refuse(name, why):
+            raise ValueError('seg_augment: sample {}: {} = {}: {}'.format(i, name, f[name], why))
+        for name in ('h', 'w', 'nh', 'nw'):
+            if not 1 <= f[name] <= SEG_AUGMENT_MAX_SIDE:
+                refuse(name, 'sides are 1..{}'.format(SEG_AUGMENT_MAX_SIDE))
+        if f['image_offset'] < 0 or f['image_offset'] + 3 * f['h'] * f['w'] > nbytes:
+            refuse('image_offset', 'the image lies outside the buffer of {} bytes'.format(nbytes))
+        if f['mask_offset'] < 0 or f['mask_offset'] + f['h'] * f['w'] > nbytes:
+            refuse('mask_offset', 'the mask lies outside the buffer of {} bytes'.format(nbytes))
+        if f['flip'] not in (0, 1):
+            refuse('flip', '0 or 1')
+        for name, limit in (('ext_h', oh), ('ext_w', ow)):
+            if not 1 <= f[name] <= limit:
+                refuse(name, 'the extent is 1..{}'.format(limit))
+        for name, resized in (('pad_h', 'nh'), ('pad_w', 'nw')):
+            if f[name] < f[resized] or f[name] > SEG_AUGMENT_MAX_SIDE:
+                refuse(name, 'the padded size is {}..{}'.format(f[resized], SEG_AUGMENT_MAX_SIDE))
+        for name, ext, padded in (('top', 'ext_h', 'pad_h'), ('left', 'ext_w', 'pad_w')):
+            if f[name] < 0 or f[name] + f[ext] > f[padded]:
+                refuse(name, 'the window of {} lies outside the padded image of {}'.format(f[ext], f[padded]))
+    return desc
+
+
+def seg_augment(buf, desc, size, mean, std, images_out=None, targets_out=None, return_workspace=False, tag=None):
+    """The augmentation chain of a batch on the device (include/sc2_bottleneck.h: sc2_seg_augment).  buf: uint8 device tensor holding the
+    sources and masks; desc: integer array / CPU tensor [n, SEG_AUGMENT_DESC_INTS] (rows from `seg_augment_desc`), checked by
+    `seg_augment_check` before anything is launched; size: (oh, ow); mean, std: three numbers each.  images_out f32 [n,3,oh,ow] /
+    targets_out int64 [n,oh,ow]: a caller's contiguous tensors to write into.
+    -> SegAugment(images, targets, status int32 [n] on the device, workspace): nothing is read back; a sample whose status is not 0
+    (SEG_AUGMENT_RATIO: an axis shrinks by more than 4) has unspecified outputs.  `workspace` (tests) is the int32 table
+    [n, ow + oh, SEG_AUGMENT_ENTRY_INTS] when asked for, else None."""
+    import numpy as np
+    _dev(buf, 'seg_augment: buf')
+    if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
+        raise Sc2Error('seg_augment: a flat contiguous uint8 buffer is required, got {} {}'.format(buf.dtype, tuple(buf.shape)))
+    oh, ow = int(size[0]), int(size[1])
+    table = np.ascontiguousarray(desc.numpy() if isinstance(desc, torch.Tensor) else desc)
+    seg_augment_check(table, int(buf.numel()), oh, ow)
+    n, dev = int(table.shape[0]), buf.device
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3 or any(v == 0.0 for v in std):
+        raise ValueError('seg_augment: three mean and three non-zero std values are required')
+    d_desc = torch.from_numpy(table.astype(np.int32)).to(dev, non_blocking=True)
+    images = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=dev) if images_out is None else _dev(images_out, 'seg_augment: images_out')
+    targets = torch.empty((n, oh, ow), dtype=torch.int64, device=dev) if targets_out is None else _dev(targets_out, 'seg_augment: targets_out')
+    if images.dtype != torch.float32 or tuple(images.shape) != (n, 3, oh, ow) or not images.is_contiguous() or images.device != dev:
+        raise Sc2Error('seg_augment: images_out must be a contiguous float32 [{},3,{},{}] tensor on {}'.format(n, oh, ow, dev))
+    if targets.dtype != torch.int64 or tuple(targets.shape) != (n, oh, ow) or not targets.is_contiguous() or targets.device != dev:
+        raise Sc2Error('seg_augment: targets_out must be a contiguous int64 [{},{},{}] tensor on {}'.format(n, oh, ow, dev))
+    ws_bytes = int(lib().sc2_seg_augment_workspace(n, oh, ow))
+    assert ws_bytes == n * (oh + ow) * SEG_AUGMENT_ENTRY_INTS * 4
+    ws = torch.empty((n, ow + oh, SEG_AUGMENT_ENTRY_INTS), dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    fm, fs = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    with _timed(tag or 'seg_augment'):
+        _check(lib().sc2_seg_augment(_ptr(buf), int(buf.numel()), _ptr(d_desc), n, oh, ow, fm, fs, _ptr(images), _ptr(targets), _ptr(ws),
+                                     _ptr(status), _stream()), 'seg_augment')
+    return SegAugment(images, targets, status, ws if return_workspace else None)
 
 
 # --------------------------------------------------------------------------------------------- #

@@ -427,6 +427,9 @@ class DistillationStage(object):
             return self.teacher(tb)
 
     def forward_process(self, batch, targets=None):
+        from .transforms import DeferredSegBatch
+        if isinstance(batch, DeferredSegBatch):     # a planned PASCAL batch: the augmentation runs here, on the stage's device
+            batch, targets = batch.materialize(self.device)
         side = self._teacher_side_stream(batch)
         if side is None:
             t_out = self._teacher_forward(batch)

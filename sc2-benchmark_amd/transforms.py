@@ -14,6 +14,12 @@ image; `config.resolve` maps `torchvision.transforms.<Name>` here).
 * `AdaptivePad` -- sc2bench/transforms/misc.py:105-154 (tests 'equal_side', otherwise pads right and bottom).
 * `Compose`, `Resize`, `CenterCrop`, `ToTensor`, `Normalize`, `RandomResizedCrop`, `RandomHorizontalFlip` -- torchvision
   semantics on PIL images / tensors, PIL + torch only.
+* `CustomCompose`, `CustomRandomResize`, `CustomRandomHorizontalFlip`, `CustomRandomCrop`, `CustomCenterCrop`, `CustomToTensor`,
+  `CustomNormalize`, `pad_if_smaller` -- script/task/custom/transform.py, the (image, target) transforms of PASCAL VOC 2012
+  (`CUSTOM_TRANSFORM_DICT`; `config.resolve` maps `custom.transform.<Name>` here), and misc.py's `CustomToTensor`.
+  `CustomCompose.plan` records the draws of the train / evaluation chain in a `DeferredSegSample`; the collate functions pack those
+  into a `DeferredSegBatch`, whose `materialize(device)` runs the whole chain on the library's kernel (csrc/seg_augment.hip,
+  `hip.host_policy.seg_augment_hip`) with the host chain's tensors bit for bit, or on the host without a device.
 * `SimpleQuantizer` / `SimpleDequantizer` -- misc.py:181-231, the 8-bit affine quantizer of the CR+BQ baseline, with
   torchdistill's `QuantizedTensor` / `quantize_tensor` / `dequantize_tensor` (tensor_util) restated here.  On a device tensor the
   8-bit form runs on the library's kernels (csrc/bq.hip), on a CPU tensor on torch ops; both give the same bits.
@@ -417,14 +423,22 @@ register_collate_func(default_collate_w_pil)
 @register_collate_func
 def pascal_seg_collate_fn(batch):
     """(image, target, supplementary dict) triplets of PASCAL VOC 2012 -> (images padded with 0, targets padded with the ignore
-    label 255, the dicts as a tuple)."""
+    label 255, the dicts as a tuple).  Triplets whose first item is a `DeferredSegSample` (its target slot is ignored) -> one
+    `DeferredSegBatch` with the dicts in `.extra[0]`."""
+    deferred = _collate_deferred(batch, True)
+    if deferred is not None:
+        return deferred
     images, targets, supp_dicts = zip(*batch)
     return cat_list(images, fill_value=0), cat_list(targets, fill_value=255), supp_dicts
 
 
 @register_collate_func
 def pascal_seg_eval_collate_fn(batch):
-    """(image, target) pairs -> (images padded with 0, targets padded with 255)."""
+    """(image, target) pairs -> (images padded with 0, targets padded with 255); pairs whose first item is a `DeferredSegSample` ->
+    one `DeferredSegBatch`."""
+    deferred = _collate_deferred(batch, False)
+    if deferred is not None:
+        return deferred
     images, targets = zip(*batch)
     return cat_list(images, fill_value=0), cat_list(targets, fill_value=255)
 
@@ -632,6 +646,334 @@ class PILTensorModule(nn.Module):
     def __repr__(self):
         return self.__class__.__name__ + '(returns_file_size={}, open_kwargs={}, save_kwargs={})'.format(
             self.returns_file_size, self.open_kwargs, self.save_kwargs)
+
+
+# ----------------------------------------------------------------------------------------- custom.transform (PASCAL VOC)
+# script/task/custom/transform.py of the reference, restated under its names: transforms of (image, target) PAIRS.  The random draws
+# come from the reference's generators in the reference's order: `random.randint` (resize), `random.random` (flip), `torch.randint`
+# twice (crop), so a seeded run draws what the reference draws.
+def _resized_hw(h, w, size):
+    """torchvision's `resize` size rule (the one `Resize` above uses): int -> the short side becomes `size`, the long side
+    int(size * long / short); [h, w] -> exact."""
+    if isinstance(size, int):
+        short, long_ = (w, h) if w <= h else (h, w)
+        new_short, new_long = size, int(size * long_ / short)
+        return (new_long, new_short) if w <= h else (new_short, new_long)
+    return int(size[0]), int(size[1])
+
+
+def _resize_to(x, nh, nw, nearest):
+    if _is_pil(x):
+        return x.resize((nw, nh), 0 if nearest else 2)
+    t = x.reshape((1,) * (4 - x.dim()) + tuple(x.shape))
+    if nearest:
+        out = F.interpolate(t.float(), size=(nh, nw), mode='nearest').to(x.dtype)
+    else:
+        out = F.interpolate(t.float(), size=(nh, nw), mode='bilinear', align_corners=False, antialias=True)
+    return out.reshape(tuple(x.shape[:-2]) + (nh, nw))
+
+
+def _hflip(x):
+    if _is_pil(x):
+        from PIL import Image
+        return x.transpose(Image.FLIP_LEFT_RIGHT)
+    return x.flip(-1)
+
+
+def _crop(x, top, left, height, width):
+    if _is_pil(x):
+        return x.crop((left, top, left + width, top + height))
+    return x[..., top:top + height, left:left + width]
+
+
+def random_crop_params(h, w, th, tw):
+    """torchvision's `RandomCrop.get_params` for an h x w image and a th x tw crop -> (top, left).  [recalled: torchvision is not
+    installed here] it raises when the crop is larger than the image, draws NOTHING when the image is exactly th x tw, and otherwise
+    draws `torch.randint(0, h - th + 1, (1,)).item()` and then `torch.randint(0, w - tw + 1, (1,)).item()`."""
+    if h < th or w < tw:
+        raise ValueError('Required crop size {} is larger than input image size {}'.format((th, tw), (h, w)))
+    if w == tw and h == th:
+        return 0, 0
+    top = torch.randint(0, h - th + 1, size=(1,)).item()
+    left = torch.randint(0, w - tw + 1, size=(1,)).item()
+    return top, left
+
+
+def pad_if_smaller(img, size, fill=0):
+    """Pads right and bottom so that both sides reach `size` (transform.py:27-34)."""
+    h, w = _size_hw(img)
+    if min(h, w) < size:
+        img = pad(img, [0, 0, size - w if w < size else 0, size - h if h < size else 0], fill=fill)
+    return img
+
+
+CUSTOM_TRANSFORM_DICT = dict()
+
+
+def register_custom_transform(cls):
+    CUSTOM_TRANSFORM_DICT[cls.__name__] = cls
+    return cls
+
+
+@register_custom_transform
+class CustomRandomResize(object):
+    """Short side -> random.randint(min_size, max_size) (both sides when `square`), the image bilinear, the target nearest;
+    `jpeg_quality`: the image goes through Pillow's JPEG first, on the host."""
+
+    def __init__(self, min_size, max_size=None, square=False, jpeg_quality=None):
+        self.min_size = min_size
+        self.max_size = min_size if max_size is None else max_size
+        self.square = square
+        self.jpeg_quality = jpeg_quality
+
+    def draw(self):
+        size = random.randint(self.min_size, self.max_size)
+        return [size, size] if self.square else size
+
+    def __call__(self, image, target):
+        if self.jpeg_quality is not None:
+            from PIL import Image
+            coded = BytesIO()
+            image.save(coded, 'JPEG', quality=self.jpeg_quality)
+            image = Image.open(coded)
+        nh, nw = _resized_hw(*_size_hw(image), self.draw())
+        return _resize_to(image, nh, nw, False), _resize_to(target, nh, nw, True)
+
+
+@register_custom_transform
+class CustomRandomHorizontalFlip(object):
+    def __init__(self, p):
+        self.p = p
+
+    def draw(self):
+        return random.random() < self.p
+
+    def __call__(self, image, target):
+        if self.draw():
+            image, target = _hflip(image), _hflip(target)
+        return image, target
+
+
+@register_custom_transform
+class CustomRandomCrop(object):
+    """`pad_if_smaller` (image 0, target 255), then a random size x size crop at `random_crop_params`."""
+
+    def __init__(self, size):
+        self.size = size
+
+    def __call__(self, image, target):
+        image = pad_if_smaller(image, self.size)
+        target = pad_if_smaller(target, self.size, fill=255)
+        top, left = random_crop_params(*_size_hw(image), self.size, self.size)
+        return _crop(image, top, left, self.size, self.size), _crop(target, top, left, self.size, self.size)
+
+
+@register_custom_transform
+class CustomCenterCrop(object):
+    def __init__(self, size):
+        self.size = size
+        self._crop = CenterCrop(size)
+
+    def __call__(self, image, target):
+        return self._crop(image), self._crop(target)
+
+
+def _pair_to_tensor(image, target, converts_sample=True, converts_target=True):
+    if converts_sample:
+        image = to_tensor(image)
+    if converts_target:
+        target = torch.as_tensor(np.array(target), dtype=torch.int64)
+    return image, target
+
+
+@register_custom_transform
+@register_misc_transform_module
+class CustomToTensor(nn.Module):
+    """Both `custom.transform.CustomToTensor` (no arguments) and `sc2bench.transforms.misc.CustomToTensor` (misc.py:158-178): ToTensor of
+    the sample and / or `as_tensor(int64)` of the target."""
+
+    def __init__(self, converts_sample=True, converts_target=True):
+        super().__init__()
+        self.converts_sample = converts_sample
+        self.converts_target = converts_target
+
+    def forward(self, image, target):
+        return _pair_to_tensor(image, target, self.converts_sample, self.converts_target)
+
+
+@register_custom_transform
+class CustomNormalize(object):
+    def __init__(self, mean, std):
+        self.mean, self.std = list(mean), list(std)
+        self._normalize = Normalize(mean, std)
+
+    def __call__(self, image, target):
+        return self._normalize(image), target
+
+
+class DeferredSegSample(object):
+    """What `CustomCompose.plan` hands out in place of the transformed pair: the source bytes and every drawn parameter, as numpy, so
+    that a data-loader worker neither resizes nor opens the device.  image uint8 [h,w,3], mask uint8 [h,w]; (nh, nw) the resized
+    size, flip, (top, left) the crop's origin in the padded, flipped, resized image, (out_h, out_w) the size of the finished
+    tensors, (pad_h, pad_w) that of the padded image, mean / std of the normalisation."""
+    __slots__ = ('image', 'mask', 'nh', 'nw', 'flip', 'top', 'left', 'out_h', 'out_w', 'pad_h', 'pad_w', 'mean', 'std')
+
+    def __init__(self, image, mask, nh, nw, flip, top, left, out_h, out_w, pad_h, pad_w, mean, std):
+        self.image, self.mask = image, mask
+        self.nh, self.nw, self.flip, self.top, self.left = int(nh), int(nw), bool(flip), int(top), int(left)
+        self.out_h, self.out_w, self.pad_h, self.pad_w = int(out_h), int(out_w), int(pad_h), int(pad_w)
+        self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+
+    def __getstate__(self):
+        return {k: getattr(self, k) for k in self.__slots__}
+
+    def __setstate__(self, state):
+        for k, v in state.items():
+            setattr(self, k, v)
+
+    def host(self):
+        """The pair `CustomCompose.__call__` returns for these draws: Pillow and torch on the host."""
+        from PIL import Image
+        image, target = Image.fromarray(self.image), Image.fromarray(self.mask)
+        image, target = _resize_to(image, self.nh, self.nw, False), _resize_to(target, self.nh, self.nw, True)
+        if self.flip:
+            image, target = _hflip(image), _hflip(target)
+        if (self.pad_h, self.pad_w) != (self.nh, self.nw):
+            image = pad(image, [0, 0, self.pad_w - self.nw, self.pad_h - self.nh], fill=0)
+            target = pad(target, [0, 0, self.pad_w - self.nw, self.pad_h - self.nh], fill=255)
+        if (self.top, self.left, self.out_h, self.out_w) != (0, 0, self.pad_h, self.pad_w):
+            image = _crop(image, self.top, self.left, self.out_h, self.out_w)
+            target = _crop(target, self.top, self.left, self.out_h, self.out_w)
+        image, target = _pair_to_tensor(image, target)
+        return Normalize(self.mean, self.std)(image), target
+
+
+@register_custom_transform
+class CustomCompose(object):
+    def __init__(self, transforms):
+        self.transforms = transforms
+
+    def __call__(self, image, target):
+        for t in self.transforms:
+            image, target = t(image, target)
+        return image, target
+
+    def _chain(self):
+        """(resize, flip or None, crop or None, normalize) when the transforms are CustomRandomResize (no jpeg_quality) -> [flip] -> [crop]
+        -> a CustomToTensor converting both -> CustomNormalize, else None."""
+        ts = list(self.transforms)
+        if len(ts) < 3 or not isinstance(ts[0], CustomRandomResize) or ts[0].jpeg_quality is not None:
+            return None
+        if not isinstance(ts[-1], CustomNormalize) or not isinstance(ts[-2], CustomToTensor):
+            return None
+        if not (ts[-2].converts_sample and ts[-2].converts_target) or len(ts[-1].mean) != 3 or len(ts[-1].std) != 3:
+            return None
+        middle = ts[1:-2]
+        flip = middle.pop(0) if middle and isinstance(middle[0], CustomRandomHorizontalFlip) else None
+        crop = middle.pop(0) if middle and isinstance(middle[0], CustomRandomCrop) else None
+        if middle or (crop is not None and not isinstance(crop.size, int)):
+            return None
+        return ts[0], flip, crop, ts[-1]
+
+    def plan(self, image, target):
+        """The PASCAL train chain (resize -> [flip] -> [crop] -> ToTensor -> Normalize) or its evaluation form on an 8-bit RGB image
+        and an 8-bit single-channel mask of one size: draws what `__call__` would draw, in its order, and returns the
+        `DeferredSegSample` -- no pixel is touched.  Any other chain or input: None (and nothing drawn)."""
+        chain = self._chain()
+        if chain is None or not _is_pil(image) or not _is_pil(target) or image.mode != 'RGB' or target.mode not in ('L', 'P') or \
+                image.size != target.size or min(image.size) < 1:
+            return None
+        resize, flip, crop, normalize = chain
+        w, h = image.size
+        nh, nw = _resized_hw(h, w, resize.draw())
+        if nh < 1 or nw < 1:
+            return None
+        flipped = flip.draw() if flip is not None else False
+        pad_h, pad_w, out_h, out_w, top, left = nh, nw, nh, nw, 0, 0
+        if crop is not None:
+            pad_h, pad_w, out_h, out_w = max(nh, crop.size), max(nw, crop.size), crop.size, crop.size
+            top, left = random_crop_params(pad_h, pad_w, out_h, out_w)
+        return DeferredSegSample(np.asarray(image), np.asarray(target), nh, nw, flipped, top, left, out_h, out_w, pad_h, pad_w,
+                                 normalize.mean, normalize.std)
+
+
+class DeferredSegBatch(object):
+    """A batch of `DeferredSegSample`s as the collate functions pack it: `buf`, one flat CPU uint8 tensor with every image and mask;
+    `desc`, the int32 descriptor table of `hip.seg_augment` [n, 16]; `size`, the (height, width) of the batch (the largest sample's);
+    mean / std; `extra`, whatever else the collate function returns behind (images, targets).  `materialize(device)` gives the two
+    tensors the host transforms and the collate function would have given -- on a HIP device with `hip.host_policy.seg_augment_hip`
+    on by one copy up and sc2_seg_augment, otherwise by the host transforms with the recorded draws."""
+    fallbacks = 0       # batches a status word sent back to the host path (process-wide, for the tests and the tools)
+
+    def __init__(self, samples, extra=()):
+        assert len(samples) >= 1 and all(isinstance(s, DeferredSegSample) for s in samples)
+        if any((s.mean, s.std) != (samples[0].mean, samples[0].std) for s in samples):
+            raise ValueError('DeferredSegBatch: samples of different normalisations')
+        from . import hip
+        self.mean, self.std = samples[0].mean, samples[0].std
+        self.size = (max(s.out_h for s in samples), max(s.out_w for s in samples))
+        self.extra = tuple(extra)
+        rows, chunks, offset = [], [], 0
+        for s in samples:
+            img, mask = np.ascontiguousarray(s.image).reshape(-1), np.ascontiguousarray(s.mask).reshape(-1)
+            h, w = s.mask.shape
+            rows.append(hip.seg_augment_desc(image_offset=offset, mask_offset=offset + img.size, h=h, w=w, nh=s.nh, nw=s.nw,
+                                             flip=int(s.flip), top=s.top, left=s.left, ext_h=s.out_h, ext_w=s.out_w, pad_h=s.pad_h,
+                                             pad_w=s.pad_w))
+            chunks += [img, mask]
+            offset += img.size + mask.size
+        self.buf = torch.from_numpy(np.concatenate(chunks))
+        self.desc = torch.from_numpy(np.stack(rows))
+
+    def __len__(self):
+        return int(self.desc.shape[0])
+
+    def samples(self):
+        """The `DeferredSegSample`s again, as views of `buf`."""
+        out, buf = [], self.buf.numpy()
+        for row in self.desc.tolist():
+            io, mo, h, w, nh, nw, flip, top, left, eh, ew, ph, pw = row[:13]
+            out.append(DeferredSegSample(buf[io:io + 3 * h * w].reshape(h, w, 3), buf[mo:mo + h * w].reshape(h, w), nh, nw, flip, top, left,
+                                         eh, ew, ph, pw, self.mean, self.std))
+        return out
+
+    def materialize_host(self, device=None):
+        pairs = [s.host() for s in self.samples()]
+        images, targets = cat_list([p[0] for p in pairs], fill_value=0), cat_list([p[1] for p in pairs], fill_value=255)
+        if device is not None:
+            images, targets = images.to(device, non_blocking=True), targets.to(device, non_blocking=True)
+        return images, targets
+
+    def materialize(self, device=None):
+        """-> (images f32 [n,3,H,W], targets int64 [n,H,W]) on `device`."""
+        from . import hip
+        device = torch.device('cpu' if device is None else device)
+        if device.type != 'cuda' or not hip.host_policy.seg_augment_hip:
+            return self.materialize_host(device)
+        with torch.cuda.device(device):         # (the launches go to the current device's current stream)
+            buf = self.buf.to(device, non_blocking=True)
+            res = hip.seg_augment(buf, self.desc, self.size, self.mean, self.std)
+            # (the kernels read `buf` on the current stream: the allocator must not hand its block out before they have run)
+            buf.record_stream(torch.cuda.current_stream(device))
+            flagged = bool(res.status.cpu().any())      # the one read-back of a batch: a sample beyond the kernels' ratio cap
+        if flagged:
+            DeferredSegBatch.fallbacks += 1
+            return self.materialize_host(device)
+        return res.images, res.targets
+
+    def pin_memory(self):
+        self.buf = self.buf.pin_memory()
+        return self
+
+
+def _collate_deferred(batch, with_supp):
+    """A batch of planned samples -> the tuple the collate function returns, with one DeferredSegBatch in place of (images, targets)."""
+    firsts = [item[0] for item in batch]
+    if not any(isinstance(f, DeferredSegSample) for f in firsts):
+        return None
+    if not all(isinstance(f, DeferredSegSample) for f in firsts):
+        raise TypeError('a batch mixes planned and transformed samples')
+    return DeferredSegBatch(firsts, extra=(tuple(item[2] for item in batch),) if with_supp else ())
 
 
 def get_transform(name):
