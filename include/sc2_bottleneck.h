@@ -101,6 +101,9 @@ int sc2_device_count(void);
 int sc2_nchw_f32_to_nhwc_bf16(const float *x, void *y, int N, int C, int H, int W, int Cpad, void *stream);
 /* x: bf16 NHWC [N,H,W,C] -> y: f32 NCHW [N,C,H,W] (what a reference caller sees). */
 int sc2_nhwc_bf16_to_nchw_f32(const void *x, float *y, int N, int C, int H, int W, void *stream);
+/* Workgroups along x of both conversions' grids for `pixels` = N H W (y = the channel groups): min(ceil(pixels / 256), 16 384), each
+ * thread striding over the pixels; 0 for pixels <= 0.  What the launchers use, exported for the tests' restated launch arithmetic. */
+long long sc2_layout_blocks(long long pixels);
 
 /* AdaptiveAvgPool2d((1,1)) + flatten of a bf16 NHWC feature map [N, HW, C] (torchvision ResNet.avgpool,
  * sc2bench/models/backbone.py:250-252): mean over HW in f32 -> y_f32 [N, C] and / or y_bf16 [N, C] (either may be NULL). */
@@ -270,6 +273,9 @@ int sc2_gdn1_rows_bwd(const void *x, const void *gy, const void *gamma_frag, con
                       void *d_norm, void *dx, float *d_beta, long long M, int C, int inverse, void *stream);
 /* column sums of a bf16 [M, C] tensor in f32 (d_beta = sum over pixels of d_norm): out f32 [C], C % 8 == 0, C <= 2048. */
 int sc2_colsum_bf16(const void *x, long long M, int C, float *out, void *stream);
+/* its grid: min(ceil(M / (1024 / (C / 8))), 256) workgroups of 1 024 threads, four pixels per thread and iteration; 0 for dims the
+ * launcher refuses. */
+long long sc2_colsum_blocks(long long M, int C);
 
 /* Two consecutive 1x1 layers of the ResNet tail across a block boundary in ONE launch (torchvision Bottleneck blocks b and
  * b + 1 of layer2, eval mode, BatchNorm folded; sc2bench/models/backbone.py:235-254 runs them one after the other):
@@ -533,6 +539,10 @@ int sc2_conv2d_wgrad(const sc2_conv_desc *d, const void *x, const void *gy, floa
 int sc2_gdn_bwd_pre(const void *gy, const void *x, const void *norm, long long M, int C, int inverse, void *d_norm,
                     void *dx_direct, float *d_beta, void *stream);
 int sc2_gdn_bwd_post(const void *dx_direct, const void *x, const void *t, long long n_elements, void *dx, void *stream);
+/* their grids (workgroups of 256 threads): pre min(ceil(M / (256 / (C / 8))), 1 024), two pixels per thread and iteration; post
+ * min(ceil(n_elements / 8 / 256), 8 192), grid-stride; 0 for arguments the launchers refuse. */
+long long sc2_gdn_bwd_pre_blocks(long long M, int C);
+long long sc2_gdn_bwd_post_blocks(long long n_elements);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Entropy bottleneck (factorised prior), filters fixed to (3,3,3,3) as sc2bench uses them     */

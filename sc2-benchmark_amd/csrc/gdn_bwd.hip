@@ -150,16 +150,37 @@ __global__ __launch_bounds__(CS_THREADS) void colsum_bf16_kernel(const uint16_t 
 
 }  // namespace
 
+// the launch grids, named: what the launchers below use, and what a test compares its own restatement of this arithmetic with
+extern "C" long long sc2_colsum_blocks(long long M, int C) {
+    if (!(M > 0 && C > 0 && C % 8 == 0 && C / 8 <= 256)) return 0;
+    const int ppi = CS_THREADS / (C / 8);
+    const long long blocks = (M + ppi - 1) / ppi;
+    return blocks > 256 ? 256 : blocks;   // (one atomic per channel and workgroup on the same C addresses: keep the workgroups few)
+}
+
+extern "C" long long sc2_gdn_bwd_pre_blocks(long long M, int C) {
+    if (!(M > 0 && C > 0 && C % 8 == 0 && C / 8 <= 256)) return 0;
+    const int pix_per_iter = 256 / (C / 8);
+    const long long blocks = (M + pix_per_iter - 1) / pix_per_iter;
+    // every workgroup ends with one f32 atomic per channel on the SAME C addresses: they serialise in L2 (~0.15 us each), so the
+    // launch cannot be shorter than (workgroups x that) -- with 4 096 workgroups the 48-channel layer (0.4 GB) took 0.61 ms, as
+    // long as layers ten times its size (kernel trace).  1 024 workgroups, two pixels per thread and iteration.
+    return blocks > 1024 ? 1024 : blocks;
+}
+
+extern "C" long long sc2_gdn_bwd_post_blocks(long long n_elements) {
+    if (!(n_elements > 0 && n_elements % 8 == 0)) return 0;
+    const long long blocks = (n_elements / 8 + 255) / 256;
+    return blocks > 8192 ? 8192 : blocks;
+}
+
 extern "C" int sc2_colsum_bf16(const void *x, long long M, int C, float *out, void *stream) {
     SC2_REQUIRE(x && out, SC2_ERR_INVALID_ARG, "colsum_bf16: null argument");
     SC2_REQUIRE(M > 0 && C > 0 && C % 8 == 0 && C / 8 <= 256, SC2_ERR_INVALID_ARG, "colsum_bf16: bad dims M=%lld C=%d", M, C);
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e = hipMemsetAsync(out, 0, (size_t)C * sizeof(float), s);
     SC2_REQUIRE(e == hipSuccess, SC2_ERR_LAUNCH, "colsum_bf16: memset failed: %s", hipGetErrorString(e));
-    const int ppi = CS_THREADS / (C / 8);
-    long long blocks = (M + ppi - 1) / ppi;
-    if (blocks > 256) blocks = 256;      // (one atomic per channel and workgroup on the same C addresses: keep the workgroups few)
-    hipLaunchKernelGGL(colsum_bf16_kernel, dim3((unsigned)blocks), dim3(CS_THREADS), 0, s, static_cast<const uint16_t *>(x), M, C, out);
+    hipLaunchKernelGGL(colsum_bf16_kernel, dim3((unsigned)sc2_colsum_blocks(M, C)), dim3(CS_THREADS), 0, s, static_cast<const uint16_t *>(x), M, C, out);
     SC2_CHECK_LAUNCH();
     return SC2_OK;
 }
@@ -171,13 +192,7 @@ extern "C" int sc2_gdn_bwd_pre(const void *gy, const void *x, const void *norm, 
     hipStream_t s = static_cast<hipStream_t>(stream);
     hipError_t e = hipMemsetAsync(d_beta, 0, (size_t)C * sizeof(float), s);
     SC2_REQUIRE(e == hipSuccess, SC2_ERR_LAUNCH, "gdn_bwd_pre: memset failed: %s", hipGetErrorString(e));
-    const int pix_per_iter = 256 / (C / 8);
-    long long blocks = (M + pix_per_iter - 1) / pix_per_iter;
-    // every workgroup ends with one f32 atomic per channel on the SAME C addresses: they serialise in L2 (~0.15 us each), so the
-    // launch cannot be shorter than (workgroups x that) -- with 4 096 workgroups the 48-channel layer (0.4 GB) took 0.61 ms, as
-    // long as layers ten times its size (kernel trace).  1 024 workgroups, two pixels per thread and iteration.
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(gdn_bwd_pre_kernel, dim3((unsigned)blocks), dim3(256), 0, s, static_cast<const uint16_t *>(gy),
+    hipLaunchKernelGGL(gdn_bwd_pre_kernel, dim3((unsigned)sc2_gdn_bwd_pre_blocks(M, C)), dim3(256), 0, s, static_cast<const uint16_t *>(gy),
                        static_cast<const uint16_t *>(x), static_cast<const uint16_t *>(norm), C, M, inverse,
                        static_cast<uint16_t *>(d_norm), static_cast<uint16_t *>(dx_direct), d_beta);
     SC2_CHECK_LAUNCH();
@@ -189,9 +204,7 @@ extern "C" int sc2_gdn_bwd_post(const void *dx_direct, const void *x, const void
     SC2_REQUIRE(dx_direct && x && t && dx, SC2_ERR_INVALID_ARG, "gdn_bwd_post: null argument");
     SC2_REQUIRE(n_elements > 0 && n_elements % 8 == 0, SC2_ERR_INVALID_ARG, "gdn_bwd_post: element count %% 8 != 0");
     const long long chunks = n_elements / 8;
-    long long blocks = (chunks + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(gdn_bwd_post_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL(gdn_bwd_post_kernel, dim3((unsigned)sc2_gdn_bwd_post_blocks(n_elements)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint16_t *>(dx_direct), static_cast<const uint16_t *>(x),
                        static_cast<const uint16_t *>(t), chunks, static_cast<uint16_t *>(dx));
     SC2_CHECK_LAUNCH();

@@ -58,12 +58,20 @@ __global__ __launch_bounds__(256) void nhwc_bf16_to_nchw_f32_kernel(const uint16
 
 }  // namespace
 
+// the x extent of both conversions' grids (y = the channel groups), named: the launchers below use it, a test compares it with its
+// own restatement
+extern "C" long long sc2_layout_blocks(long long pixels) {
+    if (pixels <= 0) return 0;
+    const long long blocks = (pixels + 255) / 256;
+    return blocks < 16384 ? blocks : 16384;
+}
+
 extern "C" int sc2_nchw_f32_to_nhwc_bf16(const float *x, void *y, int N, int C, int H, int W, int Cpad, void *stream) {
     SC2_REQUIRE(x && y, SC2_ERR_INVALID_ARG, "nchw_to_nhwc: null argument");
     SC2_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && Cpad >= C && Cpad % 4 == 0, SC2_ERR_INVALID_ARG,
                 "nchw_to_nhwc: bad dims N=%d C=%d H=%d W=%d Cpad=%d", N, C, H, W, Cpad);
     const long long total = (long long)N * H * W;
-    const int gx = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    const int gx = (int)sc2_layout_blocks(total);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (Cpad % 8 == 0)
         hipLaunchKernelGGL(nchw_f32_to_nhwc_bf16_kernel<8>, dim3(gx, Cpad / 8), dim3(256), 0, s, x,
@@ -271,7 +279,7 @@ extern "C" int sc2_nhwc_bf16_to_nchw_f32(const void *x, float *y, int N, int C, 
     SC2_REQUIRE(N > 0 && C > 0 && H > 0 && W > 0 && C % 8 == 0, SC2_ERR_INVALID_ARG,
                 "nhwc_to_nchw: bad dims N=%d C=%d H=%d W=%d (C %% 8 != 0)", N, C, H, W);
     const long long total = (long long)N * H * W;
-    const int gx = (int)((total + 255) / 256 < 16384 ? (total + 255) / 256 : 16384);
+    const int gx = (int)sc2_layout_blocks(total);
     hipLaunchKernelGGL(nhwc_bf16_to_nchw_f32_kernel, dim3(gx, C / 8), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const uint16_t *>(x), y, C, H * W, total);
     SC2_CHECK_LAUNCH();

@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     'sc2_pmf_to_quantized_cdf',
     'sc2_rans_max_bytes', 'sc2_rans_workspace_bytes', 'sc2_rans_encode_batch', 'sc2_rans_decode_batch', 'sc2_rans_decode_dequantize_batch', 'sc2_rans_decode_dequantize_batch_ev',
     'sc2_mse_partial_len', 'sc2_mse_sum_bf16', 'sc2_mse_grad_bf16', 'sc2_relu_bwd_bf16', 'sc2_relu_bwd_mse_bf16',
+    'sc2_gdn_bwd_pre_blocks', 'sc2_colsum_blocks', 'sc2_gdn_bwd_post_blocks', 'sc2_layout_blocks',
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
     'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_seg_augment_workspace', 'sc2_seg_augment', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
@@ -289,6 +290,10 @@ def lib():
     L.sc2_gdn1_rows_bwd.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_longlong, i32, i32, vp]
     L.sc2_gdn_bwd_pre.argtypes = [vp, vp, vp, ctypes.c_longlong, i32, i32, vp, vp, vp, vp]
     L.sc2_gdn_bwd_post.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp]
+    for name, args in (('sc2_gdn_bwd_pre_blocks', [ctypes.c_longlong, i32]), ('sc2_colsum_blocks', [ctypes.c_longlong, i32]),
+                       ('sc2_gdn_bwd_post_blocks', [ctypes.c_longlong]), ('sc2_layout_blocks', [ctypes.c_longlong])):
+        getattr(L, name).argtypes = args
+        getattr(L, name).restype = ctypes.c_longlong
     L.sc2_eb_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp]
     L.sc2_eb_backward.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp]
     L.sc2_eb_bits_partial_len.argtypes = [i32, i32, i32]
@@ -691,6 +696,32 @@ def colsum_bf16(x, C):
     return out
 
 
+def gdn_bwd_pre(gy, x, norm, inverse):
+    """First element-wise half of the five-launch GDN1 backward; gy, x, norm: bf16 [..., C] of one shape -> (d_norm bf16, dx_direct
+    bf16, d_beta f32 [C]): d_norm = -gy x / norm^2 (inverse: gy x), dx_direct = gy / norm (inverse: gy norm), d_beta = column sums
+    of the unrounded d_norm."""
+    for t, name in ((gy, 'gy'), (x, 'x'), (norm, 'norm')):
+        _dev(t, name)
+        assert t.dtype == torch.bfloat16 and t.is_contiguous() and t.numel() == x.numel()
+    C = x.shape[-1]
+    d_norm = torch.empty_like(x)
+    dxd = torch.empty_like(x)
+    d_beta = torch.empty((C,), dtype=torch.float32, device=x.device)
+    _check(lib().sc2_gdn_bwd_pre(_ptr(gy), _ptr(x), _ptr(norm), x.numel() // C, C, 1 if inverse else 0, _ptr(d_norm),
+                                 _ptr(dxd), _ptr(d_beta), _stream()), 'gdn_bwd_pre')
+    return d_norm, dxd, d_beta
+
+
+def gdn_bwd_post(dx_direct, x, t):
+    """Second element-wise half: dx = dx_direct + sign(x) t (t = gamma^T d_norm); bf16 tensors of one shape -> bf16."""
+    for v, name in ((dx_direct, 'dx_direct'), (x, 'x'), (t, 't')):
+        _dev(v, name)
+        assert v.dtype == torch.bfloat16 and v.is_contiguous() and v.numel() == x.numel()
+    dx = torch.empty_like(x)
+    _check(lib().sc2_gdn_bwd_post(_ptr(dx_direct), _ptr(x), _ptr(t), x.numel(), _ptr(dx), _stream()), 'gdn_bwd_post')
+    return dx
+
+
 def gdn1_backward(gy_nhwc, x_nhwc, beta, gamma, inverse):
     """Backward of GDN1 / inverse GDN1 on the HIP kernels: returns (dx bf16 NHWC, d_beta f32 [C], d_gamma f32 [C,C]).
 
@@ -719,15 +750,9 @@ def gdn1_backward(gy_nhwc, x_nhwc, beta, gamma, inverse):
         return dx, d_beta, d_gamma
     norm = conv2d_fwd(x_nhwc, pack_conv_weight(gamma.detach().reshape(C, C, 1, 1)), C, 1, 1, 1, 0, a_op=AOP_ABS,
                       epilogue=EPI_BIAS, ep_beta=beta, tag='gdn.bwd.norm')
-    d_norm = torch.empty_like(x_nhwc)
-    dxd = torch.empty_like(x_nhwc)
-    d_beta = torch.empty((C,), dtype=torch.float32, device=x_nhwc.device)
-    _check(lib().sc2_gdn_bwd_pre(_ptr(gy_nhwc), _ptr(x_nhwc), _ptr(norm), M, C, 1 if inverse else 0, _ptr(d_norm),
-                                 _ptr(dxd), _ptr(d_beta), _stream()), 'gdn_bwd_pre')
+    d_norm, dxd, d_beta = gdn_bwd_pre(gy_nhwc, x_nhwc, norm, inverse)
     t = conv2d_fwd(d_norm, pack_conv_weight(gamma.detach().t().reshape(C, C, 1, 1)), C, 1, 1, 1, 0, tag='gdn.bwd.gT')
-    dx = torch.empty_like(x_nhwc)
-    _check(lib().sc2_gdn_bwd_post(_ptr(dxd), _ptr(x_nhwc), _ptr(t), x_nhwc.numel(), _ptr(dx), _stream()),
-           'gdn_bwd_post')
+    dx = gdn_bwd_post(dxd, x_nhwc, t)
     d_gamma = conv2d_wgrad(x_nhwc, d_norm, 1, 1, 1, 0, x_abs=True).reshape(C, C)
     return dx, d_beta, d_gamma
 
