@@ -271,6 +271,11 @@ int sc2_gdn1_rows_fwd(const void *x, const void *gamma_frag, const float *beta, 
                       void *stream);
 int sc2_gdn1_rows_bwd(const void *x, const void *gy, const void *gamma_frag, const void *gamma_t_frag, const float *beta,
                       void *d_norm, void *dx, float *d_beta, long long M, int C, int inverse, void *stream);
+/* their launch geometry: tiles of 128 pixels (C = 256 / 512) or strips of 32 pixels (C = 96) that M pixels make, and the persistent
+ * workgroups that share them: min(tiles, CUs), or min(ceil(strips / 8), CUs) workgroups of eight one-strip waves; 0 for dims the
+ * launchers refuse. */
+long long sc2_gdn1_rows_units(long long M, int C);
+long long sc2_gdn1_rows_workgroups(long long M, int C);
 /* column sums of a bf16 [M, C] tensor in f32 (d_beta = sum over pixels of d_norm): out f32 [C], C % 8 == 0, C <= 2048. */
 int sc2_colsum_bf16(const void *x, long long M, int C, float *out, void *stream);
 /* its grid: min(ceil(M / (1024 / (C / 8))), 256) workgroups of 1 024 threads, four pixels per thread and iteration; 0 for dims the

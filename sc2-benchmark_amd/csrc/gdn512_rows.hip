@@ -523,6 +523,13 @@ __global__ __launch_bounds__(512, 2) void gdn512_rows_kernel(const RowsArgs p) {
 #undef SC2_ROWS_STEP
 }
 
+// the launch geometry, named: 128-pixel tiles; persistent workgroups, one per CU, no more than there are tiles
+long long rows_tiles(long long M) { return (M + BM - 1) / BM; }
+int rows_grid(long long n_tiles) {
+    const int cus = sc2_device_cus();
+    return (int)(n_tiles < cus ? n_tiles : cus);
+}
+
 template <int CH, int MODE, bool INVERSE>
 int launch_rows(const RowsArgs &a, hipStream_t s) {
     constexpr int lds = RowsGeo<CH>::LDS_BYTES;
@@ -534,8 +541,7 @@ int launch_rows(const RowsArgs &a, hipStream_t s) {
                                   lds);
         attr_set = true;
     }
-    const int g_cus_rows = sc2_device_cus();
-    const int grid = a.n_tiles < g_cus_rows ? a.n_tiles : g_cus_rows;
+    const int grid = rows_grid(a.n_tiles);
     hipLaunchKernelGGL((gdn512_rows_kernel<CH, MODE, INVERSE>), dim3(grid), dim3(512), lds, s, a);
     SC2_CHECK_LAUNCH();
     return SC2_OK;
@@ -560,7 +566,7 @@ int rows_args(RowsArgs &a, const void *x, const void *gy, const void *g1, const 
     a.out = static_cast<uint16_t *>(out);
     a.dn = static_cast<uint16_t *>(dn);
     a.M = (int)M;
-    a.n_tiles = (int)((M + BM - 1) / BM);
+    a.n_tiles = (int)rows_tiles(M);
     a.bytes = (unsigned)(M * (C * 2));
     return SC2_OK;
 }
@@ -572,7 +578,21 @@ int sc2_gdn96_strips(int mode, const void *x, const void *gy, const void *g1, co
                      float *d_beta, long long M, int inverse, hipStream_t s);
 extern "C" int sc2_colsum_bf16(const void *x, long long M, int C, float *out, void *stream);
 
+long long sc2_gdn96_strips_units(long long M);
+long long sc2_gdn96_strips_workgroups(long long M);
+
 extern "C" int sc2_gdn1_rows_supported(int C) { return C == 512 || C == 256 || C == 96 ? 1 : 0; }
+
+// the launch geometry, named: what the launchers use, and what a test compares its own restatement of this arithmetic with
+extern "C" long long sc2_gdn1_rows_units(long long M, int C) {
+    if (!(sc2_gdn1_rows_supported(C) && M > 0 && M * (C * 2) < 0x7FF00000LL)) return 0;
+    return C == 96 ? sc2_gdn96_strips_units(M) : rows_tiles(M);
+}
+
+extern "C" long long sc2_gdn1_rows_workgroups(long long M, int C) {
+    if (sc2_gdn1_rows_units(M, C) == 0) return 0;
+    return C == 96 ? sc2_gdn96_strips_workgroups(M) : rows_grid(rows_tiles(M));
+}
 
 extern "C" int sc2_gdn1_rows_fwd(const void *x, const void *gamma_frag, const float *beta, void *y, long long M, int C, int inverse,
                                  void *stream) {
@@ -588,6 +608,8 @@ extern "C" int sc2_gdn1_rows_bwd(const void *x, const void *gy, const void *gamm
                                  void *d_norm, void *dx, float *d_beta, long long M, int C, int inverse, void *stream) {
     SC2_REQUIRE(x && gy && gamma_frag && gamma_t_frag && beta && d_norm && dx, SC2_ERR_INVALID_ARG, "gdn1_rows_bwd: null argument");
     SC2_REQUIRE(sc2_gdn1_rows_supported(C), SC2_ERR_UNSUPPORTED, "gdn1_rows_bwd: C = %d (96, 256 or 512)", C);
+    SC2_REQUIRE(M > 0 && M * (C * 2) < 0x7FF00000LL, SC2_ERR_UNSUPPORTED, "gdn1_rows_bwd: %lld pixels x %d channels exceed 2 GB (32-bit buffer offsets)",
+                M, C);   // (here too: a refused call leaves d_beta as it was)
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (d_beta && C != 512) {   // accumulated by the kernels (atomics)
         hipError_t e = hipMemsetAsync(d_beta, 0, (size_t)C * sizeof(float), s);

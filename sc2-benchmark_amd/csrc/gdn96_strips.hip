@@ -284,6 +284,18 @@ __global__ __launch_bounds__(WAVES * 64, 2) void gdn96_strips_kernel(const Strip
 
 int g_cus_strips = 0;
 
+// the launch grid, named: one 8-wave workgroup per CU (148 KB of LDS), no more than the strips fill
+int strips_grid(long long n_strips) {
+    if (g_cus_strips == 0) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+            n = 256;
+        g_cus_strips = n;
+    }
+    const long long wgs = (n_strips + WAVES - 1) / WAVES;
+    return (int)(wgs < g_cus_strips ? wgs : g_cus_strips);
+}
+
 template <int MODE, bool INVERSE>
 int launch_strips(const StripArgs &a, hipStream_t s) {
     static bool attr_set_dev[SC2_MAX_DEVICES] = {};
@@ -293,20 +305,17 @@ int launch_strips(const StripArgs &a, hipStream_t s) {
                                   LDS_BYTES);
         attr_set = true;
     }
-    if (g_cus_strips == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-            n = 256;
-        g_cus_strips = n;
-    }
-    const int wgs = (a.n_strips + WAVES - 1) / WAVES;
-    const int grid = wgs < g_cus_strips ? wgs : g_cus_strips;     // one 8-wave workgroup per CU (148 KB of LDS)
+    const int grid = strips_grid(a.n_strips);
     hipLaunchKernelGGL((gdn96_strips_kernel<MODE, INVERSE>), dim3(grid), dim3(WAVES * 64), LDS_BYTES, s, a);
     SC2_CHECK_LAUNCH();
     return SC2_OK;
 }
 
 }  // namespace
+
+// strips and workgroups of M pixels, for sc2_gdn1_rows_units / _workgroups of gdn512_rows.hip
+long long sc2_gdn96_strips_units(long long M) { return (M + SP - 1) / SP; }
+long long sc2_gdn96_strips_workgroups(long long M) { return strips_grid(sc2_gdn96_strips_units(M)); }
 
 // (called by sc2_gdn1_rows_fwd / _bwd of gdn512_rows.hip for C == 96: one entry point per operation, whatever the channel count)
 int sc2_gdn96_strips(int mode, const void *x, const void *gy, const void *g1, const void *g2, const float *beta, void *out, void *dn,
@@ -322,7 +331,7 @@ int sc2_gdn96_strips(int mode, const void *x, const void *gy, const void *g1, co
     a.dn = static_cast<uint16_t *>(dn);
     a.d_beta = d_beta;
     a.M = (int)M;
-    a.n_strips = (int)((M + SP - 1) / SP);
+    a.n_strips = (int)sc2_gdn96_strips_units(M);
     a.bytes = (unsigned)(M * ROWB);
     if (mode == 0) return inverse ? launch_strips<0, true>(a, s) : launch_strips<0, false>(a, s);
     return inverse ? launch_strips<1, true>(a, s) : launch_strips<1, false>(a, s);

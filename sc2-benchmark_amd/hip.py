@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     'sc2_pmf_to_quantized_cdf',
     'sc2_rans_max_bytes', 'sc2_rans_workspace_bytes', 'sc2_rans_encode_batch', 'sc2_rans_decode_batch', 'sc2_rans_decode_dequantize_batch', 'sc2_rans_decode_dequantize_batch_ev',
     'sc2_mse_partial_len', 'sc2_mse_sum_bf16', 'sc2_mse_grad_bf16', 'sc2_relu_bwd_bf16', 'sc2_relu_bwd_mse_bf16',
-    'sc2_gdn_bwd_pre_blocks', 'sc2_colsum_blocks', 'sc2_gdn_bwd_post_blocks', 'sc2_layout_blocks',
+    'sc2_gdn_bwd_pre_blocks', 'sc2_colsum_blocks', 'sc2_gdn_bwd_post_blocks', 'sc2_layout_blocks', 'sc2_gdn1_rows_units', 'sc2_gdn1_rows_workgroups',
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
     'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_seg_augment_workspace', 'sc2_seg_augment', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
@@ -291,7 +291,8 @@ def lib():
     L.sc2_gdn_bwd_pre.argtypes = [vp, vp, vp, ctypes.c_longlong, i32, i32, vp, vp, vp, vp]
     L.sc2_gdn_bwd_post.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp]
     for name, args in (('sc2_gdn_bwd_pre_blocks', [ctypes.c_longlong, i32]), ('sc2_colsum_blocks', [ctypes.c_longlong, i32]),
-                       ('sc2_gdn_bwd_post_blocks', [ctypes.c_longlong]), ('sc2_layout_blocks', [ctypes.c_longlong])):
+                       ('sc2_gdn_bwd_post_blocks', [ctypes.c_longlong]), ('sc2_layout_blocks', [ctypes.c_longlong]),
+                       ('sc2_gdn1_rows_units', [ctypes.c_longlong, i32]), ('sc2_gdn1_rows_workgroups', [ctypes.c_longlong, i32])):
         getattr(L, name).argtypes = args
         getattr(L, name).restype = ctypes.c_longlong
     L.sc2_eb_forward.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp]
