@@ -876,6 +876,44 @@ typedef struct sc2_roi_levels {
 int sc2_roi_align(sc2_roi_levels lv, int n_levels, int N, int C, int is_bf16, const float *rois, const int32_t *levels, int K, int P,
                   int sampling_ratio, float *out, void *stream);
 
+/* The adjoint of sc2_roi_align with respect to f32 maps: grad_out f32 [K,C,P,P] and the forward call's rois, levels, P and
+ * sampling_ratio -> one f32 NHWC gradient [N,H_l,W_l,C] per level, written through lv.level[l].data (16-byte aligned; H, W and
+ * spatial_scale as in the forward call).  EVERY element of every map is written: zero where no sample lands.  Sample positions and
+ * bilinear weights are the forward's, in f32 by the same expressions; a RoI whose level or image index does not exist contributes
+ * nothing.  RoI coordinates must be finite.
+ * The caller bins the RoIs: order: i32 [K], the RoI indices sorted by bin = level * N + image and ASCENDING within a bin, RoIs without a
+ * valid bin last; bin_off: i32 [n_levels * N + 1], bin b is order[bin_off[b] .. bin_off[b+1]).  Both DEVICE memory.  Every entry is
+ * checked (offsets clamped to 0..K, indices outside 0..K-1 and RoIs that do not belong to the bin are skipped), so malformed bins lose
+ * contributions but never address outside the arrays.
+ * One launch on `stream`: a workgroup per 8 x 8 pixel tile of one (level, image) map gathers that map's RoIs in the order given.  No
+ * atomics: two calls on the same inputs give the same bits.  K == 0 gives all-zero maps. */
+int sc2_roi_align_backward(sc2_roi_levels lv, int n_levels, int N, int C, const float *grad_out, const float *rois, const int32_t *levels,
+                           const int32_t *order, const int32_t *bin_off, int K, int P, int sampling_ratio, void *stream);
+
+#define SC2_MATCH_CHUNK 2048      /* candidates per workgroup of sc2_box_match's first launch: one workspace row per chunk */
+/* torchvision's `Matcher` over `box_iou` for several images in one call, without the [G, A] IoU matrix in memory.
+ * gt: f32 [total_gt,4], cand: f32 [total_cand,4] (x1, y1, x2, y2; both 16-byte aligned); gt_off, cand_off: i32 [n_img + 1] on the DEVICE,
+ * image i owns rows off[i] .. off[i+1]; gt_off_host, cand_off_host: the caller's HOST copies of the same offsets.  The host copies are
+ * checked before anything is launched (first 0, never decreasing, last == the total: SC2_ERR_INVALID_ARG otherwise) and size the
+ * grids; the kernels read the device copies and clamp them to the totals.
+ * matches: i32 [total_cand]; best_iou: f32 [total_cand] or NULL.  IoU in f32, every operation rounded once, as sc2_nms states it
+ * (areas (x2 - x1) * (y2 - y1); w, h clamped at 0; inter / (area_gt + area_cand - inter)).
+ * Per candidate: best_iou = the maximum over its image's gt boxes, taken as a running maximum from -infinity that only a strictly
+ * greater value replaces, in ascending gt index.  Hence (1) a tie goes to the LOWEST gt index and (2) a NaN IoU (0 / 0) never becomes
+ * the maximum; a candidate all of whose IoUs are NaN keeps -infinity and index 0.  matches = -1 if best_iou < low, -2 if
+ * low <= best_iou < high, else the gt index local to the image.
+ * allow_low_quality: a candidate whose IoU with SOME gt box equals that gt box's maximum over all candidates of the image (same
+ * rules: NaN never the maximum) gets its own pre-threshold argmax back -- torchvision's behaviour: the argmax is restored, not the
+ * gt box the candidate is best for.  A per-gt maximum of exactly 0 restores every candidate with IoU 0 to it, as in torchvision.
+ * An image without gt boxes: matches = -1, best_iou = 0, nothing of gt is read.
+ * At most two launches on `stream`: per-gt maxima over chunks of SC2_MATCH_CHUNK candidates into ws (a max-reduction: independent of
+ * order; skipped without allow_low_quality), then the per-candidate pass, which folds the chunks.  No atomics.
+ * ws: sc2_box_match_ws_bytes(total_gt, the longest image's candidate count) bytes, 4-byte aligned (0 if either is <= 0). */
+long long sc2_box_match_ws_bytes(int total_gt, int max_candidates);
+int sc2_box_match(const float *gt, const int32_t *gt_off, const float *cand, const int32_t *cand_off, const int32_t *gt_off_host,
+                  const int32_t *cand_off_host, int n_img, int total_gt, int total_cand, float low, float high, int allow_low_quality,
+                  int32_t *matches, float *best_iou, void *ws, void *stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Segmentation tail (csrc/seg.hip): low-resolution class logits -> labels of the resized map and confusion counts, */
 /* one launch.  tests/ref_seg.py restates it in float64.                                                            */

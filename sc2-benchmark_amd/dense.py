@@ -438,7 +438,7 @@ def faster_rcnn_model(backbone_config, pretrained=True, pretrained_backbone_name
                       backbone_fpn_kwargs=None, num_classes=91, analysis_config=None, start_ckpt_file_path=None, **kwargs):
     """Faster R-CNN with a splittable backbone + FPN (detection/rcnn.py:183-226).  The backbone is built with
     FrozenBatchNorm2d as the reference does; RPN / RoI heads / transform come from torchvision's FasterRCNN where it is
-    importable, else from `detection.FasterRCNN` (inference only)."""
+    importable, else from `detection.FasterRCNN`."""
     from .wrapper import load_classification_model
     backbone_fpn_kwargs = dict(backbone_fpn_kwargs or {})
     backbone_config = dict(backbone_config, kwargs=dict(backbone_config.get('kwargs') or {}, norm_layer='FrozenBatchNorm2d'))

@@ -15,8 +15,16 @@ them independently).  Everything else is small tensor algebra and two small GEMM
 `RCNNTransformWithCompression` (sc2bench/models/detection/transform.py) is the transform of the input-compression baseline: a
 codec between resize and normalise; for plain JPEG on device images it runs on csrc/rcnn_input.hip + csrc/jpeg_image.hip.
 
-Training of the RPN / RoI heads (matcher, samplers, losses) is not built: both modules raise NotImplementedError in
-training mode.
+TRAINING (torchvision's loss path, **[recalled: torchvision 0.15+]** like the rest) is an opt-in: behind `enable_training(model)`
+(which `training.DistillationStage` calls for a `forward_proc: 'forward_batch_target'` student) `FasterRCNN.forward(images,
+targets)` in training mode returns the four-key loss dict (`loss_classifier`, `loss_box_reg`, `loss_objectness`, `loss_rpn_box_reg`).  Two pieces of
+it run on the library's kernels for device tensors: the proposal matcher (`match_boxes` -> `hip.box_match`: `Matcher` over `box_iou`
+for all images of the batch in one call, without the [G, A] IoU matrix) and the backward of multi-level RoIAlign (`_RoIAlignFn` ->
+`hip.roi_align` / `hip.roi_align_backward`, f32 maps only: the bf16 forward stays inference-only).  CPU tensors, and device tensors
+while `hip.host_policy.box_match_hip` / `roi_align_bwd_hip` are off (A/B), take the torch-op definitions (`box_iou` + `Matcher`;
+autograd through `_roi_align_level_torch`); both routes give the same matches.  Box encoding, the balanced sampler, smooth-L1, BCE
+and CE are small tensor algebra on at most a few thousand sampled rows and stay on torch ops.  Not built: the COCO dataset side
+(transforms, aspect-ratio grouping), mask and keypoint heads, a bf16 backward, the random choice among several `min_size` values.
 """
 import math
 from collections import OrderedDict
@@ -46,11 +54,28 @@ def remove_small_boxes(boxes, min_size):
 
 
 class BoxCoder(object):
-    """Box regression deltas <-> boxes (torchvision.models.detection._utils.BoxCoder); only `decode` is needed at inference."""
+    """Box regression deltas <-> boxes (torchvision.models.detection._utils.BoxCoder): `decode` at inference, `encode` for the regression targets in training."""
 
     def __init__(self, weights, bbox_xform_clip=BBOX_XFORM_CLIP):
         self.weights = weights
         self.bbox_xform_clip = bbox_xform_clip
+
+    def encode(self, reference_boxes, proposals):
+        """lists of [k_i,4] per image (the matched gt boxes, the anchors / proposals) -> the list of regression targets [k_i,4]"""
+        boxes_per_image = [len(b) for b in reference_boxes]
+        targets = self.encode_single(torch.cat(list(reference_boxes), dim=0), torch.cat(list(proposals), dim=0))
+        return targets.split(boxes_per_image, 0)
+
+    def encode_single(self, reference_boxes, proposals):
+        """torchvision's `encode_boxes`: dx = wx * (gt_ctr_x - ctr_x) / width, dw = ww * log(gt_width / width); dy, dh likewise"""
+        wx, wy, ww, wh = torch.as_tensor(self.weights, dtype=reference_boxes.dtype, device=reference_boxes.device).unbind(0)
+        px1, py1, px2, py2 = [c.unsqueeze(1) for c in proposals.to(reference_boxes.dtype).unbind(1)]
+        gx1, gy1, gx2, gy2 = [c.unsqueeze(1) for c in reference_boxes.unbind(1)]
+        ex_w, ex_h = px2 - px1, py2 - py1
+        ex_cx, ex_cy = px1 + 0.5 * ex_w, py1 + 0.5 * ex_h
+        gt_w, gt_h = gx2 - gx1, gy2 - gy1
+        gt_cx, gt_cy = gx1 + 0.5 * gt_w, gy1 + 0.5 * gt_h
+        return torch.cat((wx * (gt_cx - ex_cx) / ex_w, wy * (gt_cy - ex_cy) / ex_h, ww * torch.log(gt_w / ex_w), wh * torch.log(gt_h / ex_h)), dim=1)
 
     def decode(self, rel_codes, boxes):
         concat = torch.cat(list(boxes), dim=0)
@@ -71,6 +96,108 @@ class BoxCoder(object):
         pred_ctr_x, pred_ctr_y = dx * widths[:, None] + ctr_x[:, None], dy * heights[:, None] + ctr_y[:, None]
         half_w, half_h = 0.5 * (torch.exp(dw) * widths[:, None]), 0.5 * (torch.exp(dh) * heights[:, None])
         return torch.stack((pred_ctr_x - half_w, pred_ctr_y - half_h, pred_ctr_x + half_w, pred_ctr_y + half_h), dim=2).flatten(1)
+
+
+# ------------------------------------------------------------------------------------------------ matcher, sampler, loss
+def box_iou(boxes1, boxes2):
+    """torchvision.ops.box_iou: [G,4], [A,4] -> [G,A]; every operation its own op (rounded once, as sc2_box_match does):
+    areas (x2 - x1) * (y2 - y1), wh = (min(rb) - max(lt)).clamp(0), inter / (area1 + area2 - inter)"""
+    area1 = (boxes1[:, 2] - boxes1[:, 0]) * (boxes1[:, 3] - boxes1[:, 1])
+    area2 = (boxes2[:, 2] - boxes2[:, 0]) * (boxes2[:, 3] - boxes2[:, 1])
+    wh = (torch.min(boxes1[:, None, 2:], boxes2[:, 2:]) - torch.max(boxes1[:, None, :2], boxes2[:, :2])).clamp(min=0)
+    inter = wh[:, :, 0] * wh[:, :, 1]
+    return inter / (area1[:, None] + area2 - inter)
+
+
+class Matcher(object):
+    """torchvision.models.detection._utils.Matcher over a [G, A] quality matrix -> int64 [A]: the gt index, BELOW_LOW_THRESHOLD where
+    the maximum is < low, BETWEEN_THRESHOLDS where it is >= low and < high.  `allow_low_quality_matches`: every candidate whose
+    quality with some gt box equals that box's maximum over all candidates gets its own argmax back (torchvision's known behaviour:
+    the argmax, not the gt box it is best for).  Stated where torchvision leaves it open, as include/sc2_bottleneck.h does for
+    sc2_box_match: a tie goes to the lowest gt index, and a NaN quality (0 / 0) is never a maximum (a column of NaNs: index 0, below
+    the threshold)."""
+    BELOW_LOW_THRESHOLD = -1
+    BETWEEN_THRESHOLDS = -2
+
+    def __init__(self, high_threshold, low_threshold, allow_low_quality_matches=False):
+        if low_threshold > high_threshold:
+            raise ValueError('Matcher: low_threshold should be <= high_threshold')
+        self.high_threshold, self.low_threshold = high_threshold, low_threshold
+        self.allow_low_quality_matches = allow_low_quality_matches
+
+    def __call__(self, match_quality_matrix):
+        if match_quality_matrix.numel() == 0:
+            if match_quality_matrix.shape[0] == 0:
+                raise ValueError('No ground-truth boxes available for one of the images during training')
+            raise ValueError('No proposal boxes available for one of the images during training')
+        ranked = torch.where(torch.isnan(match_quality_matrix), torch.full_like(match_quality_matrix, float('-inf')), match_quality_matrix)
+        matched_vals, matches = ranked.max(dim=0)
+        all_matches = matches.clone() if self.allow_low_quality_matches else None
+        below = matched_vals < self.low_threshold
+        between = (matched_vals >= self.low_threshold) & (matched_vals < self.high_threshold)
+        matches[below] = self.BELOW_LOW_THRESHOLD
+        matches[between] = self.BETWEEN_THRESHOLDS
+        if self.allow_low_quality_matches:
+            self.set_low_quality_matches_(matches, all_matches, match_quality_matrix)
+        return matches
+
+    def set_low_quality_matches_(self, matches, all_matches, match_quality_matrix):
+        ranked = torch.where(torch.isnan(match_quality_matrix), torch.full_like(match_quality_matrix, float('-inf')), match_quality_matrix)
+        highest_quality_foreach_gt = ranked.max(dim=1)[0]
+        restore = (match_quality_matrix == highest_quality_foreach_gt[:, None]).any(dim=0)      # (a NaN equals nothing)
+        matches[restore] = all_matches[restore]
+
+
+def match_boxes(gt_boxes, boxes, high_threshold, low_threshold, allow_low_quality_matches):
+    """`Matcher(box_iou(gt_boxes[i], boxes[i]))` for every image i -> a list of int64 [A_i]; an image without gt boxes is all
+    BELOW_LOW_THRESHOLD.  Device tensors: ONE call of `hip.box_match` for the batch (no IoU matrix); CPU tensors, or
+    `hip.host_policy.box_match_hip` off: the matrix + `Matcher` per image.  Both give the same indices."""
+    gt_boxes = [g.detach().to(torch.float32).reshape(-1, 4) for g in gt_boxes]
+    boxes = [b.detach().to(torch.float32) for b in boxes]
+    if boxes[0].is_cuda and hip.host_policy.box_match_hip:
+        counts = [int(b.shape[0]) for b in boxes]
+        matches, _ = hip.box_match(torch.cat(gt_boxes).contiguous(), [int(g.shape[0]) for g in gt_boxes], torch.cat(boxes).contiguous(), counts,
+                                   low_threshold, high_threshold, allow_low_quality_matches, want_iou=False)
+        return list(matches.to(torch.int64).split(counts))
+    matcher = Matcher(high_threshold, low_threshold, allow_low_quality_matches)
+    out = []
+    for g, b in zip(gt_boxes, boxes):
+        if g.shape[0] == 0 or b.shape[0] == 0:
+            out.append(torch.full((b.shape[0],), Matcher.BELOW_LOW_THRESHOLD, dtype=torch.int64, device=b.device))
+        else:
+            out.append(matcher(box_iou(g, b)))
+    return out
+
+
+class BalancedPositiveNegativeSampler(object):
+    """torchvision's sampler: per image up to batch_size_per_image * positive_fraction of the positives (label >= 1) and the rest of
+    the batch from the negatives (label == 0), by two `randperm` draws per image on the labels' device from the global generator --
+    positives first, then negatives -> (list of uint8 positive masks, list of uint8 negative masks)."""
+
+    def __init__(self, batch_size_per_image, positive_fraction):
+        self.batch_size_per_image, self.positive_fraction = batch_size_per_image, positive_fraction
+
+    def __call__(self, matched_idxs):
+        pos_idx, neg_idx = [], []
+        for m in matched_idxs:
+            positive, negative = torch.where(m >= 1)[0], torch.where(m == 0)[0]
+            num_pos = min(positive.numel(), int(self.batch_size_per_image * self.positive_fraction))
+            num_neg = min(negative.numel(), self.batch_size_per_image - num_pos)
+            perm1 = torch.randperm(positive.numel(), device=positive.device)[:num_pos]
+            perm2 = torch.randperm(negative.numel(), device=negative.device)[:num_neg]
+            pos_mask, neg_mask = torch.zeros_like(m, dtype=torch.uint8), torch.zeros_like(m, dtype=torch.uint8)
+            pos_mask[positive[perm1]] = 1
+            neg_mask[negative[perm2]] = 1
+            pos_idx.append(pos_mask)
+            neg_idx.append(neg_mask)
+        return pos_idx, neg_idx
+
+
+def smooth_l1_loss(input, target, beta=1.0 / 9, size_average=False):
+    """0.5 * d^2 / beta where |d| < beta, |d| - 0.5 * beta elsewhere, summed (or averaged)"""
+    n = torch.abs(input - target)
+    loss = torch.where(n < beta, 0.5 * n ** 2 / beta, n - 0.5 * beta)
+    return loss.mean() if size_average else loss.sum()
 
 
 # ------------------------------------------------------------------------------------------------ NMS
@@ -164,6 +291,25 @@ def _roi_align_level_torch(feat, rois, scale, P, S, chunk=128):
     return torch.cat(outs, dim=0)
 
 
+class _RoIAlignFn(torch.autograd.Function):
+    """hip.roi_align / hip.roi_align_backward as one differentiable operation over f32 NCHW maps (any memory format); the RoIs get
+    no gradient (torchvision's do not either)."""
+
+    @staticmethod
+    def forward(ctx, rois, levels, scales, P, S, *feats):
+        nhwc = [f.detach().permute(0, 2, 3, 1).contiguous() for f in feats]
+        ctx.save_for_backward(rois, levels)
+        ctx.meta = (tuple(scales), P, S, [tuple(f.shape[1:3]) for f in nhwc], int(feats[0].shape[0]))
+        return hip.roi_align(nhwc, scales, rois, levels, P, S)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        rois, levels = ctx.saved_tensors
+        scales, P, S, sizes, N = ctx.meta
+        grads = hip.roi_align_backward(grad_out.to(torch.float32).contiguous(), sizes, scales, rois, levels, N, S)
+        return (None, None, None, None, None) + tuple(g.permute(0, 3, 1, 2) for g in grads)
+
+
 def multiscale_roi_align(feats, scales, rois, levels, output_size, sampling_ratio):
     """RoIAlign (aligned=False) of rois f32 [K,5] (image index, x1, y1, x2, y2), each from the map `levels[k]` of `feats`
     (NCHW maps of one batch, any memory format; `scales[l]`: image pixels -> pixels of map l) -> f32 [K,C,P,P]."""
@@ -172,7 +318,12 @@ def multiscale_roi_align(feats, scales, rois, levels, output_size, sampling_rati
     if S <= 0:
         raise NotImplementedError('roi_align: the adaptive sampling grid (sampling_ratio <= 0) is not built')
     rois = rois.to(torch.float32)
-    if feats[0].is_cuda and hip.host_policy.roi_align_hip:
+    # f32 maps that ask for a gradient: the kernel pair, or (switch off) autograd through the torch ops below.  bf16 maps keep
+    # the inference kernel whatever they ask for: there is no bf16 backward.
+    wants_grad = torch.is_grad_enabled() and any(f.requires_grad for f in feats) and all(f.dtype == torch.float32 for f in feats)
+    if wants_grad and feats[0].is_cuda and hip.host_policy.roi_align_hip and hip.host_policy.roi_align_bwd_hip and feats[0].shape[1] % 8 == 0:
+        return _RoIAlignFn.apply(rois.detach().contiguous(), levels.to(torch.int32).contiguous(), tuple(float(s) for s in scales), P, S, *feats)
+    if feats[0].is_cuda and hip.host_policy.roi_align_hip and not wants_grad:
         if feats[0].shape[1] % 8:
             raise ValueError('roi_align: {} channels (the kernel takes multiples of 8)'.format(feats[0].shape[1]))
         dtype = torch.bfloat16 if feats[0].dtype == torch.bfloat16 else torch.float32
@@ -358,11 +509,24 @@ def concat_box_prediction_layers(box_cls, box_regression):
     return torch.cat(cls_flat, dim=1).flatten(0, -2), torch.cat(reg_flat, dim=1).reshape(-1, 4)
 
 
-_NO_TRAINING = ('{}: training is not built in this package -- the proposal matcher, the balanced positive / negative samplers '
-                'and the classification / box-regression losses are missing; only the eval forward exists')
+_TRAINING_OFF = ('{}: the training path is off for this module -- the proposal matcher, the balanced positive / negative samplers and '
+                 'the classification / box-regression losses run only behind `detection.enable_training(model)` (a '
+                 "`forward_proc: 'forward_batch_target'` student gets it from `training.DistillationStage`); a module that was only "
+                 'put into train() keeps raising, as it always has')
+
+
+def enable_training(model, enabled=True):
+    """Switch the loss path of every `RegionProposalNetwork` and `RoIHeads` inside `model` on (or off) -> model.  The path is an
+    opt-in per module: without it a module in training mode raises NotImplementedError, the behaviour from before the path was built."""
+    for m in model.modules():
+        if isinstance(m, (RegionProposalNetwork, RoIHeads)):
+            m.training_enabled = bool(enabled)
+    return model
 
 
 class RegionProposalNetwork(nn.Module):
+    training_enabled = False      # see `enable_training`
+
     def __init__(self, anchor_generator, head, fg_iou_thresh=0.7, bg_iou_thresh=0.3, batch_size_per_image=256, positive_fraction=0.5,
                  pre_nms_top_n=None, post_nms_top_n=None, nms_thresh=0.7, score_thresh=0.0):
         super().__init__()
@@ -413,11 +577,42 @@ class RegionProposalNetwork(nn.Module):
             final_scores.append(scores[keep])
         return final_boxes, final_scores
 
+    def assign_targets_to_anchors(self, anchors, targets):
+        """-> (labels f32 [A] per image: 1 matched, 0 background, -1 between the thresholds; the matched gt box of every anchor).
+        Thresholds fg / bg (0.7 / 0.3) with low-quality matches on; an image without gt boxes: all-zero labels and boxes."""
+        gt_boxes = [t['boxes'] for t in targets]
+        matched = match_boxes(gt_boxes, anchors, self.fg_iou_thresh, self.bg_iou_thresh, True)
+        labels, matched_gt_boxes = [], []
+        for anchors_per_image, gt, m in zip(anchors, gt_boxes, matched):
+            if gt.numel() == 0:
+                matched_gt_boxes.append(torch.zeros_like(anchors_per_image))
+                labels.append(torch.zeros((anchors_per_image.shape[0],), dtype=torch.float32, device=anchors_per_image.device))
+                continue
+            matched_gt_boxes.append(gt.to(anchors_per_image.dtype)[m.clamp(min=0)])
+            lab = (m >= 0).to(torch.float32)
+            lab = torch.where(m == Matcher.BELOW_LOW_THRESHOLD, torch.zeros_like(lab), lab)
+            lab = torch.where(m == Matcher.BETWEEN_THRESHOLDS, torch.full_like(lab, -1.0), lab)
+            labels.append(lab)
+        return labels, matched_gt_boxes
+
+    def compute_loss(self, objectness, pred_bbox_deltas, labels, regression_targets):
+        """BCE-with-logits on the sampled anchors; smooth-L1 (beta 1/9) summed over the sampled positives / the number sampled"""
+        sampled_pos, sampled_neg = BalancedPositiveNegativeSampler(self.batch_size_per_image, self.positive_fraction)(labels)
+        sampled_pos = torch.where(torch.cat(sampled_pos, dim=0))[0]
+        sampled_neg = torch.where(torch.cat(sampled_neg, dim=0))[0]
+        sampled = torch.cat([sampled_pos, sampled_neg], dim=0)
+        objectness = objectness.flatten()
+        labels, regression_targets = torch.cat(labels, dim=0), torch.cat(regression_targets, dim=0)
+        box_loss = smooth_l1_loss(pred_bbox_deltas[sampled_pos], regression_targets[sampled_pos], beta=1.0 / 9) / sampled.numel()
+        objectness_loss = F.binary_cross_entropy_with_logits(objectness[sampled], labels[sampled])
+        return objectness_loss, box_loss
+
     def forward(self, images, features, targets=None):
         if self.training:
             if targets is None:
                 raise ValueError('targets should not be None in training mode')
-            raise NotImplementedError(_NO_TRAINING.format('RegionProposalNetwork'))
+            if not self.training_enabled:
+                raise NotImplementedError(_TRAINING_OFF.format('RegionProposalNetwork'))
         features = list(features.values())
         objectness, pred_bbox_deltas = self.head(features)
         anchors = self.anchor_generator(images, features)
@@ -426,7 +621,13 @@ class RegionProposalNetwork(nn.Module):
         objectness, pred_bbox_deltas = concat_box_prediction_layers(objectness, pred_bbox_deltas)
         proposals = self.box_coder.decode(pred_bbox_deltas.detach().float(), anchors).view(num_images, -1, 4)
         boxes, _ = self.filter_proposals(proposals, objectness.float(), images.image_sizes, num_anchors_per_level)
-        return boxes, {}
+        losses = {}
+        if self.training:
+            labels, matched_gt_boxes = self.assign_targets_to_anchors(anchors, targets)
+            regression_targets = self.box_coder.encode(matched_gt_boxes, anchors)
+            loss_objectness, loss_rpn_box_reg = self.compute_loss(objectness.float(), pred_bbox_deltas.float(), labels, regression_targets)
+            losses = {'loss_objectness': loss_objectness, 'loss_rpn_box_reg': loss_rpn_box_reg}
+        return boxes, losses
 
 
 # ------------------------------------------------------------------------------------------------ box head, RoI heads
@@ -455,6 +656,8 @@ class FastRCNNPredictor(nn.Module):
 
 
 class RoIHeads(nn.Module):
+    training_enabled = False      # see `enable_training`
+
     def __init__(self, box_roi_pool, box_head, box_predictor, fg_iou_thresh=0.5, bg_iou_thresh=0.5, batch_size_per_image=512,
                  positive_fraction=0.25, bbox_reg_weights=None, score_thresh=0.05, nms_thresh=0.5, detections_per_img=100):
         super().__init__()
@@ -485,11 +688,77 @@ class RoIHeads(nn.Module):
             all_labels.append(labels[keep])
         return all_boxes, all_scores, all_labels
 
+    @staticmethod
+    def check_targets(targets):
+        if targets is None:
+            raise ValueError('targets should not be None in training mode')
+        if not all('boxes' in t for t in targets):
+            raise ValueError('Every element of targets should have a boxes key')
+        if not all('labels' in t for t in targets):
+            raise ValueError('Every element of targets should have a labels key')
+
+    @staticmethod
+    def add_gt_proposals(proposals, gt_boxes):
+        return [torch.cat((p, g)) for p, g in zip(proposals, gt_boxes)]
+
+    def assign_targets_to_proposals(self, proposals, gt_boxes, gt_labels):
+        """-> (matched gt index clamped at 0, labels int64: the gt label, 0 background, -1 ignored) per image; fg / bg thresholds
+        (0.5 / 0.5) without low-quality matches"""
+        matched = match_boxes(gt_boxes, proposals, self.fg_iou_thresh, self.bg_iou_thresh, False)
+        matched_idxs, labels = [], []
+        for m, labels_in_image in zip(matched, gt_labels):
+            clamped = m.clamp(min=0)
+            if labels_in_image.numel() == 0:
+                lab = torch.zeros_like(clamped)
+            else:
+                lab = labels_in_image[clamped].to(torch.int64)
+                lab = torch.where(m == Matcher.BELOW_LOW_THRESHOLD, torch.zeros_like(lab), lab)
+                lab = torch.where(m == Matcher.BETWEEN_THRESHOLDS, torch.full_like(lab, -1), lab)
+            matched_idxs.append(clamped)
+            labels.append(lab)
+        return matched_idxs, labels
+
+    def subsample(self, labels):
+        sampled_pos, sampled_neg = BalancedPositiveNegativeSampler(self.batch_size_per_image, self.positive_fraction)(labels)
+        return [torch.where(p | n)[0] for p, n in zip(sampled_pos, sampled_neg)]
+
+    def select_training_samples(self, proposals, targets):
+        self.check_targets(targets)
+        dtype = proposals[0].dtype
+        gt_boxes = [t['boxes'].to(dtype).reshape(-1, 4) for t in targets]
+        gt_labels = [t['labels'] for t in targets]
+        proposals = self.add_gt_proposals(proposals, gt_boxes)
+        matched_idxs, labels = self.assign_targets_to_proposals(proposals, gt_boxes, gt_labels)
+        sampled_inds = self.subsample(labels)
+        matched_gt_boxes = []
+        for i, inds in enumerate(sampled_inds):
+            proposals[i], labels[i], matched_idxs[i] = proposals[i][inds], labels[i][inds], matched_idxs[i][inds]
+            gt = gt_boxes[i] if gt_boxes[i].numel() else torch.zeros((1, 4), dtype=dtype, device=proposals[i].device)
+            matched_gt_boxes.append(gt[matched_idxs[i]])
+        regression_targets = self.box_coder.encode(matched_gt_boxes, proposals)
+        return proposals, matched_idxs, labels, regression_targets
+
+    @staticmethod
+    def fastrcnn_loss(class_logits, box_regression, labels, regression_targets):
+        """cross entropy; smooth-L1 (beta 1/9) on the positive rows' own class, summed / the number of sampled RoIs"""
+        labels, regression_targets = torch.cat(labels, dim=0), torch.cat(regression_targets, dim=0)
+        classification_loss = F.cross_entropy(class_logits, labels)
+        pos = torch.where(labels > 0)[0]
+        box_regression = box_regression.reshape(class_logits.shape[0], box_regression.size(-1) // 4, 4)
+        box_loss = smooth_l1_loss(box_regression[pos, labels[pos]], regression_targets[pos], beta=1.0 / 9) / labels.numel()
+        return classification_loss, box_loss
+
     def forward(self, features, proposals, image_shapes, targets=None):
         if self.training:
             if targets is None:
                 raise ValueError('targets should not be None in training mode')
-            raise NotImplementedError(_NO_TRAINING.format('RoIHeads'))
+            if not self.training_enabled:
+                raise NotImplementedError(_TRAINING_OFF.format('RoIHeads'))
+            proposals, _, labels, regression_targets = self.select_training_samples(proposals, targets)
+            box_features = self.box_head(self.box_roi_pool(features, proposals, image_shapes))
+            class_logits, box_regression = self.box_predictor(box_features)
+            loss_classifier, loss_box_reg = self.fastrcnn_loss(class_logits.float(), box_regression.float(), labels, regression_targets)
+            return [], {'loss_classifier': loss_classifier, 'loss_box_reg': loss_box_reg}
         box_features = self.box_head(self.box_roi_pool(features, proposals, image_shapes))
         class_logits, box_regression = self.box_predictor(box_features)
         boxes, scores, labels = self.postprocess_detections(class_logits.float(), box_regression.float(), proposals, image_shapes)
@@ -764,6 +1033,10 @@ class FasterRCNN(nn.Module):
         features = self.backbone(images.tensors)
         if isinstance(features, torch.Tensor):
             features = OrderedDict([('0', features)])
-        proposals, _ = self.rpn(images, features, targets)
-        detections, _ = self.roi_heads(features, proposals, images.image_sizes, targets)
+        proposals, proposal_losses = self.rpn(images, features, targets)
+        detections, detector_losses = self.roi_heads(features, proposals, images.image_sizes, targets)
+        if self.training:      # the four-key loss dict, in torchvision's order
+            losses = dict(detector_losses)
+            losses.update(proposal_losses)
+            return losses
         return self.transform.postprocess(detections, images.image_sizes, original_image_sizes)

@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
     'sc2_gdn_bwd_pre_blocks', 'sc2_colsum_blocks', 'sc2_gdn_bwd_post_blocks', 'sc2_layout_blocks', 'sc2_gdn1_rows_units', 'sc2_gdn1_rows_workgroups',
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
-    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_seg_augment_workspace', 'sc2_seg_augment', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
+    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_roi_align_backward', 'sc2_box_match_ws_bytes', 'sc2_box_match', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_seg_augment_workspace', 'sc2_seg_augment', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
     'sc2_jpeg_max_bytes', 'sc2_jpeg_tensor_codec', 'sc2_jpeg_image_max_bytes', 'sc2_jpeg_image_workspace_bytes', 'sc2_jpeg_image_codec',
     'sc2_rcnn_resize_u8', 'sc2_rcnn_normalize_pad',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
@@ -66,6 +66,8 @@ class ArScanArgs(ctypes.Structure):
 
 NMS_MAX_BOXES = 16384      # SC2_NMS_MAX_BOXES
 ROI_MAX_LEVELS = 5         # SC2_ROI_MAX_LEVELS
+MATCH_CHUNK = 2048         # SC2_MATCH_CHUNK: candidates per workgroup of sc2_box_match's first launch
+MATCH_CAND_PER_WG, MATCH_GT_TILE = 1024, 64     # ... per workgroup of its second launch; gt boxes staged at a time
 SEG_MAX_CLASSES = 64       # SC2_SEG_MAX_CLASSES
 SEG_CE_MEAN, SEG_CE_SUM, SEG_CE_NONE = 0, 1, 2     # SC2_SEG_CE_*
 COCO_THRS, COCO_RECS, COCO_AREAS, COCO_MAXDETS = 10, 101, 4, 3     # SC2_COCO_*
@@ -152,6 +154,8 @@ class HostPolicy(object):
     eval_graph_max_batch = 1   # ... for batches up to this size (the reference evaluates at batch size 1)
     nms_hip = True             # detection.nms / batched_nms of device tensors on sc2_nms (False: the torch-op restatement, A/B)
     roi_align_hip = True       # detection.roi_align / multiscale_roi_align of device tensors on sc2_roi_align (False: torch ops, A/B)
+    box_match_hip = True       # detection.match_boxes (the RPN's and the RoI heads' target assignment in training) of device tensors on sc2_box_match (False: the [G, A] `box_iou` matrix + `Matcher` on torch ops, A/B; tools/det_train_times.py, 6 images x 242 991 anchors x 20 gt boxes, 0.3 / 0.7 with low-quality matches: 0.17 against 2.41 ms, identical matches)
+    roi_align_bwd_hip = True   # the backward of detection.multiscale_roi_align of f32 device maps on sc2_roi_align_backward (False: autograd through the torch-op restatement, forward included, A/B; tools/det_train_times.py, 3 072 RoIs over four maps of 6 images, C = 256, P = 7, S = 2: forward + backward 2.03 against 137.1 ms, the backward launch with its binning 1.64 ms)
     coco_eval_hip = True       # coco_eval.CocoBoxEvaluator.accumulate of device tensors on sc2_coco_match + sc2_coco_accumulate (False: the torch / numpy host path of the same module; tools/coco_eval_times.py)
     jpeg_codec_hip = True      # transforms.PILTensorModule(format='JPEG') of f32 device tensors up to 64 x 64 on sc2_jpeg_tensor_codec (False: PIL per channel group on the host, A/B; tools/jpeg_codec_times.py: 0.36 against 42.7 ms at [1,512,28,28])
     jpeg_image_hip = True      # transforms.PILImageModule(format='JPEG').forward_batch of equal-size RGB / grey PIL images up to 2048 x 2048 on sc2_jpeg_image_codec (False: PIL per image on the host, A/B; tools/jpeg_image_times.py, codec + ToTensor + Normalize to the classifier input: 0.39 against 0.50 ms at [1,3,224,224], 10.4 against 174 ms at [256,3,224,224])
@@ -335,6 +339,10 @@ def lib():
     L.sc2_nms_ws_bytes.restype = i64
     L.sc2_nms.argtypes = [vp, vp, i32, f32, vp, vp, vp, vp]
     L.sc2_roi_align.argtypes = [RoiLevels, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp]
+    L.sc2_roi_align_backward.argtypes = [RoiLevels, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, i32, vp]
+    L.sc2_box_match_ws_bytes.argtypes = [i32, i32]
+    L.sc2_box_match_ws_bytes.restype = i64
+    L.sc2_box_match.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp]
     L.sc2_seg_predict.argtypes = [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, i32, vp, vp, vp, vp]
     L.sc2_seg_ce_ws_bytes.argtypes = [i32, i32, i32]
     L.sc2_seg_ce_ws_bytes.restype = i64
@@ -1250,6 +1258,92 @@ def roi_align(feats_nhwc, scales, rois, levels, output_size, sampling_ratio, out
         _check(lib().sc2_roi_align(lv, len(feats_nhwc), N, C, 1 if f0.dtype == torch.bfloat16 else 0, _ptr(rois), _ptr(levels), K, P,
                                    int(sampling_ratio), _ptr(out), _stream()), 'roi_align')
     return out
+
+
+def roi_align_backward(grad_out, map_sizes, scales, rois, levels, n_images, sampling_ratio, out=None, tag=None):
+    """The adjoint of `roi_align` with respect to f32 maps (include/sc2_bottleneck.h: sc2_roi_align_backward).
+    grad_out: f32 [K,C,P,P] contiguous; map_sizes: (H_l, W_l) per level; scales, rois f32 [K,5], levels i32 [K], sampling_ratio: the
+    forward call's; n_images: N -> a list of f32 [N,H_l,W_l,C] gradients, every element written (zeros where nothing lands), the
+    same bits on every call.  `out`: the caller's list of such tensors to write into.  A RoI whose level or image index does not
+    exist contributes nothing.  The RoIs are binned by (level, image) with torch ops on the device (a stable sort: ascending index
+    within a bin); nothing synchronises."""
+    _dev(grad_out, 'grad_out')
+    map_sizes = [(int(h), int(w)) for h, w in map_sizes]
+    L = len(map_sizes)
+    if not 1 <= L <= ROI_MAX_LEVELS or len(scales) != L:
+        raise ValueError('roi_align_backward: {} maps, {} scales (1..{} of each)'.format(L, len(scales), ROI_MAX_LEVELS))
+    assert grad_out.dtype == torch.float32 and grad_out.dim() == 4 and grad_out.is_contiguous() and grad_out.shape[2] == grad_out.shape[3]
+    K, C, P, N = int(grad_out.shape[0]), int(grad_out.shape[1]), int(grad_out.shape[2]), int(n_images)
+    dev = grad_out.device
+    assert rois.dtype == torch.float32 and rois.shape == (K, 5) and rois.is_contiguous() and rois.device == dev
+    assert levels.dtype == torch.int32 and levels.shape == (K,) and levels.is_contiguous() and levels.device == dev
+    if out is None:
+        out = [torch.empty((N, h, w, C), dtype=torch.float32, device=dev) for h, w in map_sizes]
+    out = list(out)
+    lv = RoiLevels()
+    assert len(out) == L
+    for l, (g, (h, w), sc) in enumerate(zip(out, map_sizes, scales)):
+        assert g.dtype == torch.float32 and g.shape == (N, h, w, C) and g.is_contiguous() and g.device == dev
+        lv.level[l].data, lv.level[l].H, lv.level[l].W, lv.level[l].spatial_scale = g.data_ptr(), h, w, float(sc)
+    n_bins = L * N
+    img = rois[:, 0]
+    valid = (levels >= 0) & (levels < L) & (img >= 0) & (img < N)      # (a NaN image index compares false)
+    key = torch.where(valid, levels.to(torch.int64) * N + img.clamp(0, max(N - 1, 0)).to(torch.int64), torch.full_like(levels, n_bins, dtype=torch.int64))
+    order = torch.sort(key, stable=True)[1].to(torch.int32)
+    bin_off = torch.zeros(n_bins + 2, dtype=torch.int64, device=dev)
+    bin_off[1:] = torch.cumsum(torch.bincount(key, minlength=n_bins + 1), 0)
+    bin_off = bin_off.to(torch.int32)
+    with _timed(tag or 'roi_align_backward'):
+        _check(lib().sc2_roi_align_backward(lv, L, N, C, _ptr(grad_out), _ptr(rois), _ptr(levels), _ptr(order), _ptr(bin_off), K, P,
+                                            int(sampling_ratio), _stream()), 'roi_align_backward')
+    return out
+
+
+def box_match(gt_boxes, gt_counts, boxes, counts, low, high, allow_low_quality, out=None, want_iou=True, tag=None):
+    """torchvision's `Matcher` over `box_iou` for several images in one call, without the IoU matrix (include/sc2_bottleneck.h:
+    sc2_box_match).  gt_boxes: f32 [sum G_i,4]; boxes: f32 [sum A_i,4] (the candidates); gt_counts, counts: the G_i and A_i as Python
+    ints (they become the offsets: increasing by construction; `gt_offsets=` / `offsets=` style lists are what the library checks).
+    -> (matches i32 [sum A_i]: the gt index local to the image, -1 below `low`, -2 between the thresholds; best_iou f32 [sum A_i] or
+    None with want_iou=False).  `out`: (matches, best_iou or None) buffers of the caller to write into.  Ties go to the lowest gt
+    index, a NaN IoU is never the maximum, an image without gt boxes is all -1 / 0."""
+    return box_match_offsets(gt_boxes, _offsets(gt_counts), boxes, _offsets(counts), low, high, allow_low_quality, out=out,
+                             want_iou=want_iou, tag=tag)
+
+
+def _offsets(counts):
+    off = [0]
+    for c in counts:
+        off.append(off[-1] + int(c))
+    return off
+
+
+def box_match_offsets(gt_boxes, gt_offsets, boxes, offsets, low, high, allow_low_quality, out=None, want_iou=True, tag=None):
+    """`box_match` with the two offset lists ([n_img + 1] Python ints each) given as they are: the library refuses lists that do not
+    start at 0, that decrease or that do not end at the row counts (ValueError), before anything is launched."""
+    _dev(boxes, 'boxes')
+    _dev(gt_boxes, 'gt_boxes')
+    assert boxes.dtype == torch.float32 and boxes.dim() == 2 and boxes.shape[1] == 4 and boxes.is_contiguous()
+    assert gt_boxes.dtype == torch.float32 and gt_boxes.dim() == 2 and gt_boxes.shape[1] == 4 and gt_boxes.is_contiguous()
+    assert gt_boxes.device == boxes.device and len(gt_offsets) == len(offsets) >= 1
+    dev, n_img = boxes.device, len(offsets) - 1
+    A, G = int(boxes.shape[0]), int(gt_boxes.shape[0])
+    if out is None:
+        out = (torch.empty(A, dtype=torch.int32, device=dev), torch.empty(A, dtype=torch.float32, device=dev) if want_iou else None)
+    matches, best = out
+    assert matches.dtype == torch.int32 and matches.shape == (A,) and matches.is_contiguous() and matches.device == dev
+    assert best is None or (best.dtype == torch.float32 and best.shape == (A,) and best.is_contiguous() and best.device == dev)
+    if not all(-2 ** 31 <= int(v) < 2 ** 31 for v in list(gt_offsets) + list(offsets)):
+        raise ValueError('box_match: an offset does not fit 32 bits')
+    g_host = (ctypes.c_int32 * (n_img + 1))(*[int(v) for v in gt_offsets])
+    a_host = (ctypes.c_int32 * (n_img + 1))(*[int(v) for v in offsets])
+    both = torch.tensor([int(v) for v in gt_offsets] + [int(v) for v in offsets], dtype=torch.int32).to(dev)
+    longest = max([0] + [int(offsets[i + 1]) - int(offsets[i]) for i in range(n_img)])
+    ws = torch.empty(max(int(lib().sc2_box_match_ws_bytes(G, max(longest, 0))) // 4, 1), dtype=torch.float32, device=dev)
+    with _timed(tag or 'box_match'):
+        _check(lib().sc2_box_match(_ptr(gt_boxes), _ptr(both[:n_img + 1]), _ptr(boxes), _ptr(both[n_img + 1:]), g_host, a_host, n_img, G, A,
+                                   float(low), float(high), 1 if allow_low_quality else 0, _ptr(matches), _ptr(best), _ptr(ws),
+                                   _stream()), 'box_match')
+    return matches, best
 
 
 # --------------------------------------------------------------------------------------------- #

@@ -193,13 +193,47 @@ def poly_lr_scheduler(optimizer, num_iterations, num_epochs, power=0.9):
 LR_SCHEDULERS = {'poly_lr_scheduler': poly_lr_scheduler}     # looked up before torch.optim.lr_scheduler
 
 
-class WeightedSumLoss(nn.Module):
-    """sum_i weight_i * term_i(student_io_dict, teacher_io_dict, targets)."""
+def _to_device(obj, device):
+    """tensors inside lists / tuples / dicts moved to `device`; anything else as it is"""
+    if isinstance(obj, torch.Tensor):
+        return obj.to(device)
+    if isinstance(obj, (list, tuple)):
+        return type(obj)(_to_device(v, device) for v in obj)
+    if isinstance(obj, dict):
+        return {k: _to_device(v, device) for k, v in obj.items()}
+    return obj
 
-    def __init__(self, sub_terms=None, model_term=None, **kwargs):
+
+def extract_model_loss_dict(student_outputs, targets=None, **kwargs):
+    """torchdistill's `extract_model_loss_dict` ([recalled]): the model's training output IS its loss dict"""
+    return student_outputs
+
+
+MODEL_LOSS_EXTRACTORS = {'extract_model_loss_dict': extract_model_loss_dict}
+
+
+class WeightedSumLoss(nn.Module):
+    """sum_i weight_i * term_i(student_io_dict, teacher_io_dict, targets), plus the `model_term`: the losses the student itself
+    returns in training mode (a detector's loss dict), read from student_io_dict['.']['output'] through `func2extract_model_loss`
+    (torchdistill's, [recalled]).  model_term = {'weight': w}: a number multiplies the sum of the dict's values, a
+    dict weights per key (keys it does not name add nothing); absent, or a weight of 0 / None, adds nothing and reads nothing."""
+
+    def __init__(self, sub_terms=None, model_term=None, func2extract_model_loss=None, **kwargs):
         super().__init__()
         self.terms = nn.ModuleDict()
         self.weights = dict()
+        self.model_loss_factor = (model_term or {}).get('weight') if isinstance(model_term, dict) else None
+        if isinstance(self.model_loss_factor, dict):
+            self.model_loss_factor = {k: float(v) for k, v in self.model_loss_factor.items()}
+        elif self.model_loss_factor is not None:
+            self.model_loss_factor = float(self.model_loss_factor)
+        key = func2extract_model_loss or 'extract_model_loss_dict'
+        if callable(key):
+            self.extract_model_loss = key
+        elif key in MODEL_LOSS_EXTRACTORS:
+            self.extract_model_loss = MODEL_LOSS_EXTRACTORS[key]
+        else:
+            raise KeyError('func2extract_model_loss `{}` is not available'.format(key))
         for name, cfg in (sub_terms or {}).items():
             crit_cfg = cfg['criterion']
             key, ckw = crit_cfg['key'], dict(crit_cfg.get('kwargs') or {})
@@ -222,13 +256,28 @@ class WeightedSumLoss(nn.Module):
         total = 0
         for name, term in self.terms.items():
             total = total + self.weights[name] * term(student_io_dict, teacher_io_dict, targets)
-        return total
+        factor = self.model_loss_factor
+        if not factor:
+            return total
+        model_loss_dict = self.extract_model_loss(student_io_dict['.']['output'], targets)
+        if not isinstance(model_loss_dict, dict):
+            raise TypeError('WeightedSumLoss: model_term expects the student to return a dict of losses (a detector in training '
+                            'mode), got {}'.format(type(model_loss_dict).__name__))
+        if isinstance(factor, dict):
+            for key, weight in factor.items():
+                if weight and key in model_loss_dict:
+                    total = total + weight * model_loss_dict[key]
+            return total
+        return total + factor * sum(model_loss_dict.values())
 
 
 def build_criterion(cfg):
     if cfg['key'] != 'WeightedSumLoss':
         raise KeyError('criterion `{}` is not available'.format(cfg['key']))
-    return WeightedSumLoss(**(cfg.get('kwargs') or {}))
+    kwargs = dict(cfg.get('kwargs') or {})
+    if cfg.get('func2extract_model_loss') is not None:      # (the reference's files state it beside `kwargs`)
+        kwargs.setdefault('func2extract_model_loss', cfg['func2extract_model_loss'])
+    return WeightedSumLoss(**kwargs)
 
 
 class DistillationStage(object):
@@ -240,6 +289,10 @@ class DistillationStage(object):
     def __init__(self, teacher, student, stage_config, device, lr_factor=1, head_dtype=None, bucket_mb=25.0):
         self.device = device
         t_cfg, s_cfg = stage_config.get('teacher') or {}, stage_config.get('student') or {}
+        self.t_forward_proc, self.s_forward_proc = t_cfg.get('forward_proc'), s_cfg.get('forward_proc')
+        if self.s_forward_proc == 'forward_batch_target':     # the student is asked for its loss dict: a detector's loss path is an opt-in
+            from .detection import enable_training
+            enable_training(student)
         self.student_full = student
         self.aux_module = student.get_aux_module() if hasattr(student, 'get_aux_module') else None
         freeze(student, s_cfg.get('frozen_modules'))
@@ -430,6 +483,8 @@ class DistillationStage(object):
         from .transforms import DeferredSegBatch
         if isinstance(batch, DeferredSegBatch):     # a planned PASCAL batch: the augmentation runs here, on the stage's device
             batch, targets = batch.materialize(self.device)
+        if 'forward_batch_target' in (self.t_forward_proc, self.s_forward_proc):
+            return self._forward_batch_target(batch, targets)
         side = self._teacher_side_stream(batch)
         if side is None:
             t_out = self._teacher_forward(batch)
@@ -447,6 +502,21 @@ class DistillationStage(object):
         s_out = self._student_forward(batch)
         if side is not None:
             main.wait_stream(side)
+        s_io = self.s_hooks.pop()
+        s_io['.'] = {'output': s_out}
+        return self.criterion(s_io, t_io, targets)
+
+    def _forward_batch_target(self, batch, targets):
+        """`forward_proc: 'forward_batch_target'` (torchdistill's, [recalled]): the model is called with
+        (batch, targets) -- a detector, whose batch is a list of images and whose targets are a list of dicts; both are moved to the
+        stage's device.  The teacher runs without gradients (in eval mode it returns detections and ignores the targets); a
+        model whose own forward_proc is not 'forward_batch_target' is called with the batch alone."""
+        batch, targets = _to_device(batch, self.device), _to_device(targets, self.device)
+        with torch.no_grad():
+            t_out = self.teacher(batch, targets) if self.t_forward_proc == 'forward_batch_target' else self.teacher(batch)
+        t_io = self.t_hooks.pop()
+        t_io['.'] = {'output': t_out}
+        s_out = self.student(batch, targets) if self.s_forward_proc == 'forward_batch_target' else self.student(batch)
         s_io = self.s_hooks.pop()
         s_io['.'] = {'output': s_out}
         return self.criterion(s_io, t_io, targets)
