@@ -1201,6 +1201,41 @@ int sc2_rcnn_normalize_pad(const uint8_t *pixels, int C, int h, int w, const flo
                            void *stream);
 
 /* ------------------------------------------------------------------------------------------ */
+/* The detector's input transform of a planned COCO batch (csrc/det_input.hip): what ToTensor, the loader's horizontal flip   */
+/* and torchvision's GeneralizedRCNNTransform (normalise, bilinear resize, zero-padded batch) do to a list of images, from    */
+/* the packed 8-bit sources in ONE launch on `stream`.  tests/ref_det_input.py restates the arithmetic.  No atomics, no       */
+/* workspace, nothing is copied to the host.                                                                                  */
+/* ------------------------------------------------------------------------------------------ */
+#define SC2_DET_INPUT_MAX_BATCH 64      /* samples of one launch: their descriptor rows travel by value in the kernel arguments */
+#define SC2_DET_INPUT_ROW_INTS 6        /* int32 words of a descriptor row: offset, h, w, oh, ow, flip */
+#define SC2_DET_INPUT_TILE_H 16         /* output rows and columns of a workgroup's tile */
+#define SC2_DET_INPUT_TILE_W 256
+/* buf : u8 [nbytes] on the device, nbytes in 1..2^31-1 (SC2_ERR_UNSUPPORTED beyond), any alignment.
+ * rows: int32 [n][SC2_DET_INPUT_ROW_INTS] ON THE HOST (read before the call returns), n in 1..SC2_DET_INPUT_MAX_BATCH
+ *   (SC2_ERR_UNSUPPORTED otherwise: the caller splits).  Row i: the byte offset of the sample's interleaved [h,w,3] RGB image in buf,
+ *   h, w, the resized size (oh, ow) -- the caller's: what GeneralizedRCNNTransform.resized_size returns --, flip.  EVERY row is checked
+ *   on the host before anything is launched: h, w, oh, ow in 1..SC2_JPEG_IMAGE_MAX_SIDE (SC2_ERR_UNSUPPORTED otherwise);
+ *   0 <= offset and offset + 3*h*w <= nbytes, oh <= Hp, ow <= Wp, flip in {0, 1} (SC2_ERR_INVALID_ARG otherwise).  On an error nothing
+ *   runs and `out` is untouched.
+ * mean, std: 3 floats each ON THE HOST; std[c] != 0 (SC2_ERR_INVALID_ARG).
+ * out : f32 [n,3,Hp,Wp] contiguous, 4-byte aligned, Hp and Wp in 1..4 * SC2_JPEG_IMAGE_MAX_SIDE (SC2_ERR_UNSUPPORTED beyond).  EVERY
+ *   element is written exactly once: the caller clears nothing.  Outside sample i's (oh, ow) +0.0.  Inside, every operation in f32
+ *   and rounded once, nothing contracted:
+ *     nrm[c][b] = ((float(b) / 255) - mean[c]) / std[c]      both divisions IEEE correctly rounded: the host's
+ *                                                            `(to_tensor(u8) - mean) / std`, as a table of 3 x 256 values
+ *     per axis, as aten's upsample_bilinear2d (align_corners=False) when no scale factor is handed down
+ *     (F.interpolate(..., recompute_scale_factor=True)), the same as sc2_rcnn_resize_u8's:
+ *       scale = in / out;  src = max(scale * (d + 0.5) - 0.5, 0);  i0 = min(int(src), in - 1);  i1 = min(i0 + 1, in - 1);
+ *       l1 = src - i0;  l0 = 1 - l1
+ *     v = ly0 * (lx0 * p + lx1 * q) + ly1 * (lx0 * s + lx1 * t)   p, q = nrm[c][.] of row j0 at columns i0, i1; s, t of row j1
+ *     with flip, source column i is read at w - 1 - i (the flip comes before the resize: ToTensor -> flip -> normalise -> resize).
+ *   One workgroup per (sample, SC2_DET_INPUT_TILE_H rows, SC2_DET_INPUT_TILE_W columns) produces the three channels of its tile from
+ *   one set of indices and weights; the table is built per workgroup in LDS (3 KB); a lane produces four adjacent pixels of four rows
+ *   and stores 16 bytes per channel and row where the address allows, else element by element. */
+int sc2_det_input(const uint8_t *buf, long long nbytes, const int32_t *rows, int n, const float *mean, const float *std, float *out,
+                  int Hp, int Wp, void *stream);
+
+/* ------------------------------------------------------------------------------------------ */
 /* Diagnostics (csrc/diag.hip; no product path calls these).                                    */
 /* ------------------------------------------------------------------------------------------ */
 /* The shader clock the chip holds while OTHER kernels run: `n_workgroups` probe waves (one per workgroup; launch >= 8 so that

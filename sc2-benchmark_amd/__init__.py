@@ -34,7 +34,11 @@ from .dense import (DETECTION_MODEL_FUNC_DICT, SEGMENTATION_MODEL_FUNC_DICT, Bas
                     ResizedLogits, SegEvaluator, UpdatableBackboneWithFPN, backbone_with_fpn, deeplabv3_model, deeplabv3_resnet50,
                     faster_rcnn_model, fasterrcnn_resnet50_fpn, seg_cross_entropy, seg_labels)
 
+from . import coco_eval  # noqa: F401
 from .coco_eval import CocoBoxEvaluator, CocoDictDetection, coco_gt_from_dataset  # noqa: F401
+from . import coco_data  # noqa: F401
+from .coco_data import GroupedBatchSampler, coco_dataset, create_aspect_ratio_groups  # noqa: F401
+from .transforms import DeferredDetBatch, DeferredDetSample  # noqa: F401
 from .pipeline import StagePipeline, supports_stages  # noqa: F401
 from . import graphs  # noqa: F401
 

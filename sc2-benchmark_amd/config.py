@@ -8,6 +8,8 @@ into packages that are not installed here (`torchvision`, `torchdistill`) or tha
 * `sc2bench.*`      -> the registries of this package (same keys: layers, backbones, losses, analyzers),
 * `torchvision.datasets.VOCSegmentation` -> this module's class of that name, `custom.transform.*` (the PASCAL pair transforms of
   the reference's task scripts) -> `sc2bench_amd.transforms.CUSTOM_TRANSFORM_DICT`,
+* `coco.dataset.*`, `custom.sampler.*` (the COCO dataset, its transforms and the grouped batch sampler of the reference's task
+  scripts) -> `sc2bench_amd.coco_data`,
 * other `torchvision.datasets.*` -> this module's `ImageFolder` (root/<class>/<image>; a missing directory raises on first
   use unless SC2_SYNTHETIC_DATA=1 opts in to random images),
 * `torchvision.models.resnet.*Weights` -> an inert enum (pretrained weights need the network),
@@ -236,6 +238,10 @@ def resolve(key):
         return VOCSegmentation
     if key.startswith('torchvision.datasets.'):
         return ImageFolder
+    if key.startswith('coco.dataset.') or key.startswith('custom.sampler.'):
+        from . import coco_data
+        if key.split('.')[-1] in coco_data.__all__:      # the restated names only: never a module that file happens to import
+            return getattr(coco_data, key.split('.')[-1])
     if key.startswith('custom.transform.'):
         from . import transforms as tr
         if key.split('.')[-1] in tr.CUSTOM_TRANSFORM_DICT:

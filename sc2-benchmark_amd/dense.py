@@ -418,7 +418,8 @@ class BaseRCNN(_UpdatableDenseModel):
     def forward(self, images, targets=None):
         if self.training and targets is None:
             raise ValueError('targets should not be None in training mode')
-        original_image_sizes = [tuple(img.shape[-2:]) for img in images]
+        from .detection import original_sizes
+        original_image_sizes = original_sizes(images)      # (a planned batch states them: transforms.DeferredDetBatch.sizes)
         images, targets = self.transform(images, targets)
         features = self.backbone(images.tensors)
         if isinstance(features, torch.Tensor):

@@ -35,7 +35,7 @@ from torch import nn
 
 from . import hip
 from .analysis import AnalyzableModule
-from .transforms import AdaptivePad, Compose, PILImageModule, to_pil_image, to_tensor
+from .transforms import AdaptivePad, Compose, DeferredDetBatch, PILImageModule, to_pil_image, to_tensor
 
 BBOX_XFORM_CLIP = math.log(1000.0 / 16)
 
@@ -773,6 +773,13 @@ def resize_boxes(boxes, original_size, new_size):
     return torch.stack((xmin * ratio_w, ymin * ratio_h, xmax * ratio_w, ymax * ratio_h), dim=1)
 
 
+def original_sizes(images):
+    """[(h, w)] of a list of [C,H,W] images or of a planned batch (`transforms.DeferredDetBatch.sizes`)"""
+    if isinstance(images, DeferredDetBatch):
+        return [tuple(size) for size in images.sizes]
+    return [tuple(img.shape[-2:]) for img in images]
+
+
 class GeneralizedRCNNTransform(nn.Module):
     """Normalise, resize so that the shorter side is min_size unless the longer would pass max_size, zero-pad the batch to a
     multiple of `size_divisible`; `postprocess` maps the detections back to each image's own size."""
@@ -822,7 +829,37 @@ class GeneralizedRCNNTransform(nn.Module):
             batched[i, :, :img.shape[1], :img.shape[2]].copy_(img)
         return batched
 
+    def _det_input_plan(self, batch):
+        """True when a planned batch takes the kernel path (`DeferredDetBatch.transformed`: one copy up of the source bytes and one
+        sc2_det_input launch): a HIP device, `hip.host_policy.det_input_hip` on, no fixed size, the resize not skipped, three
+        channels' statistics and every side within the kernel's cap.  Decided before anything is launched."""
+        if batch.device.type != 'cuda' or not hip.host_policy.det_input_hip or self.fixed_size is not None:
+            return False
+        if (self.training and self._skip_resize) or len(batch) == 0 or len(self.image_mean) != 3 or len(self.image_std) != 3:
+            return False
+        if any(float(v) == 0.0 for v in self.image_std) or batch.buf.numel() > 0x7FFFFFFF:
+            return False
+        for h, w in batch.sizes:
+            oh, ow = self.resized_size(h, w)
+            if max(h, w, oh, ow) > hip.JPEG_IMAGE_MAX_SIDE or min(h, w, oh, ow) < 1:
+                return False
+        return True
+
+    def _forward_deferred(self, batch, targets):
+        """a `transforms.DeferredDetBatch` as `images`: the same ImageList and targets as `forward(batch.tensors(device), targets)`"""
+        if not self._det_input_plan(batch):
+            return self.forward(batch.tensors(batch.device), targets)
+        targets = [dict(t) for t in targets] if targets is not None else None
+        batched, image_sizes = batch.transformed(self, batch.device)      # shared with every transform of equal parameters: read-only
+        if targets is not None:
+            for i, (size, new_size) in enumerate(zip(batch.sizes, image_sizes)):
+                if 'boxes' in targets[i]:
+                    targets[i] = dict(targets[i], boxes=resize_boxes(targets[i]['boxes'], size, new_size))
+        return ImageList(batched, list(image_sizes)), targets
+
     def forward(self, images, targets=None):
+        if isinstance(images, DeferredDetBatch):
+            return self._forward_deferred(images, targets)
         images = [img for img in images]
         targets = [dict(t) for t in targets] if targets is not None else None
         for i, image in enumerate(images):
@@ -971,6 +1008,8 @@ class RCNNTransformWithCompression(GeneralizedRCNNTransform, AnalyzableModule):
         return ImageList(batched, [(int(oh), int(ow)) for oh, ow in sizes]), targets
 
     def forward(self, images, targets=None):
+        if isinstance(images, DeferredDetBatch):      # a planned batch: the codec works on the host chain's tensors
+            images = images.tensors(images.device)
         images = [img for img in images]
         targets = [dict(t) for t in targets] if targets is not None else None
         for image in images:
@@ -1028,7 +1067,7 @@ class FasterRCNN(nn.Module):
     def forward(self, images, targets=None):
         if self.training and targets is None:
             raise ValueError('targets should not be None in training mode')
-        original_image_sizes = [tuple(img.shape[-2:]) for img in images]
+        original_image_sizes = original_sizes(images)
         images, targets = self.transform(images, targets)
         features = self.backbone(images.tensors)
         if isinstance(features, torch.Tensor):

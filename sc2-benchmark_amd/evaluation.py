@@ -239,11 +239,15 @@ def _evaluate_detection(model, data_loader, device, evaluator, max_samples, log_
         model.activate_analysis()
     t0 = time.perf_counter()
     seen = 0
+    from .transforms import DeferredDetBatch
     for i, (images, targets) in enumerate(data_loader):
         if max_samples is not None and seen + len(images) > max_samples:
             images, targets = images[:max_samples - seen], targets[:max_samples - seen]
         image_ids = [int(t['image_id']) for t in targets]      # host-side targets: read before anything is moved
-        images = [image.to(device, non_blocking=True) for image in images]
+        if isinstance(images, DeferredDetBatch):      # a planned COCO batch: the detector's transform finishes it, on `device`
+            images = images.to(device)
+        else:
+            images = [image.to(device, non_blocking=True) for image in images]
         outputs = model(images)
         evaluator.update({image_id: output for image_id, output in zip(image_ids, outputs)})
         seen += len(images)
@@ -269,7 +273,9 @@ def _evaluate_detection(model, data_loader, device, evaluator, max_samples, log_
 
 
 def build_data_loader(dataset_dict, loader_config):
-    """`test.test_data_loader` block -> DataLoader (dataset by id, sampler class, kwargs, `collate_fn` by name)."""
+    """`test.test_data_loader` or `train_data_loader` block -> DataLoader (dataset by id, sampler class, kwargs, `collate_fn` by name).
+    `batch_sampler: {key, kwargs}`: the class of that name in `coco_data.BATCH_SAMPLER_DICT`, built as `cls(sampler, **kwargs)`; the
+    DataLoader then gets no `batch_size` (torchdistill's behaviour, [recalled])."""
     from .transforms import COLLATE_FUNC_DICT
     dataset = dataset_dict[loader_config['dataset_id']]
     if isinstance(dataset, dict) and 'coco_gt' in dataset:      # `--json`: a COCO dictionary (or its path) in place of the dataset
@@ -282,6 +288,22 @@ def build_data_loader(dataset_dict, loader_config):
     if sampler_cls is not None and not isinstance(sampler_cls, C.Placeholder):
         sampler = sampler_cls(dataset, **(sampler_cfg.get('kwargs') or {}))
     collate = COLLATE_FUNC_DICT.get(loader_config.get('collate_fn'))      # default_collate_w_pil, pascal_seg_collate_fn, pascal_seg_eval_collate_fn
+    batch_sampler_cfg = loader_config.get('batch_sampler')
+    if batch_sampler_cfg is not None:
+        from .coco_data import BATCH_SAMPLER_DICT
+        key = batch_sampler_cfg.get('key') if isinstance(batch_sampler_cfg, dict) else None
+        if key not in BATCH_SAMPLER_DICT:
+            raise KeyError('batch_sampler `{}` is not available (have {})'.format(key, sorted(BATCH_SAMPLER_DICT)))
+        sampler_kwargs = dict(batch_sampler_cfg.get('kwargs') or {})
+        unresolved = [k for k, v in sampler_kwargs.items() if isinstance(v, C.Placeholder)]
+        if unresolved:
+            raise ValueError('batch_sampler `{}`: kwargs {} are unresolved (a dataset that is not available leaves '
+                             '`custom.sampler.create_aspect_ratio_groups` unresolved)'.format(key, unresolved))
+        if sampler is None:
+            sampler = torch.utils.data.SequentialSampler(dataset)
+        batch_sampler = BATCH_SAMPLER_DICT[key](sampler, **sampler_kwargs)
+        kwargs.pop('batch_size', None)
+        return torch.utils.data.DataLoader(dataset, batch_sampler=batch_sampler, collate_fn=collate, **kwargs)
     kwargs.setdefault('batch_size', 1)
     return torch.utils.data.DataLoader(dataset, sampler=sampler, collate_fn=collate, **kwargs)
 

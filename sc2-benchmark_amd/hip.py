@@ -8,6 +8,7 @@ import collections
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -41,7 +42,7 @@ ABI_SYMBOLS = [
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
     'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_roi_align_backward', 'sc2_box_match_ws_bytes', 'sc2_box_match', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_seg_augment_workspace', 'sc2_seg_augment', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
     'sc2_jpeg_max_bytes', 'sc2_jpeg_tensor_codec', 'sc2_jpeg_image_max_bytes', 'sc2_jpeg_image_workspace_bytes', 'sc2_jpeg_image_codec',
-    'sc2_rcnn_resize_u8', 'sc2_rcnn_normalize_pad',
+    'sc2_rcnn_resize_u8', 'sc2_rcnn_normalize_pad', 'sc2_det_input',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
 ]
 
@@ -81,6 +82,8 @@ SEG_AUGMENT_DESC_INTS, SEG_AUGMENT_ENTRY_INTS = 16, 12      # SC2_SEG_AUGMENT_*
 SEG_AUGMENT_MAX_SIDE, SEG_AUGMENT_MAX_BATCH = 16384, 65535
 SEG_AUGMENT_RATIO, SEG_AUGMENT_BAD = 1, 2
 JPEG_IMAGE_CHUNK_BLOCKS = 128    # SC2_JPEG_IMAGE_CHUNK_BLOCKS
+DET_INPUT_MAX_BATCH, DET_INPUT_ROW_INTS = 64, 6      # SC2_DET_INPUT_*
+DET_INPUT_TILE_H, DET_INPUT_TILE_W = 16, 256
 
 
 class RoiLevel(ctypes.Structure):
@@ -161,6 +164,7 @@ class HostPolicy(object):
     jpeg_image_hip = True      # transforms.PILImageModule(format='JPEG').forward_batch of equal-size RGB / grey PIL images up to 2048 x 2048 on sc2_jpeg_image_codec (False: PIL per image on the host, A/B; tools/jpeg_image_times.py, codec + ToTensor + Normalize to the classifier input: 0.39 against 0.50 ms at [1,3,224,224], 10.4 against 174 ms at [256,3,224,224])
     rcnn_input_hip = True      # detection.RCNNTransformWithCompression (eval, plain JPEG, f32 RGB device images): resize -> codec -> normalise + pad per image on sc2_rcnn_resize_u8 + sc2_jpeg_image_codec + sc2_rcnn_normalize_pad, one read-back per list (False: the reference's loop through Pillow on the host, A/B; tools/rcnn_input_times.py, 480 x 640 -> 800 x 1066 at quality 90: 2.79 against 25.7 ms at one image per call, 16.0 against 88.3 ms at six; the two new kernels alone 0.009 ms each, the codec 2.63 ms)
     seg_augment_hip = True     # transforms.DeferredSegBatch.materialize (the PASCAL CustomCompose chain, planned in the data-loader workers) on sc2_seg_augment: one copy up and two launches per batch (False: Pillow + torch on the host with the recorded draws, A/B; tools/seg_augment_times.py, 16 sources of 375 x 500 -> 513 x 513: 0.38 ms per batch with the copy up and the read-back, the launches alone 0.102 ms, against 86.0 ms through Pillow on one core)
+    det_input_hip = True       # detection.GeneralizedRCNNTransform on a transforms.DeferredDetBatch (the COCO loader's ImageToTensor -> [flip] chain, planned in the data-loader workers) on sc2_det_input: one copy up of the source bytes and one launch per batch; coco_data.CustomCocoDetection plans its samples only while this is on (False: the float32 list of the host chain copied up, then normalise + F.interpolate + pad per image, A/B; tools/det_input_times.py, six 480 x 640 sources -> [6,3,800,1088]: 0.185 against 0.884 ms per batch with the copies up, the launch alone 0.042 ms)
     seg_predict_hip = True     # dense.seg_labels (BaseSegmentationModel.predict, SegEvaluator.update_logits) of device tensors on sc2_seg_predict (False: interpolate + argmax + bincount, A/B)
     seg_loss_hip = True        # dense.seg_cross_entropy (DictLossWrapper over a deferred-resize segmentation student) of device tensors on sc2_seg_ce_forward + sc2_seg_ce_backward (False: F.interpolate + F.cross_entropy + autograd, A/B; tools/seg_loss_times.py, out + aux forward + backward at [8,21,65,65] -> 513 x 513: 1.27 against 2.70 ms with f32 logits, 1.27 against 1.72 ms with bf16, 20 against 707 MB of peak allocation)
 
@@ -362,6 +366,7 @@ def lib():
     L.sc2_jpeg_image_codec.argtypes = [vp, i64, i64, i64, i64, i32, i32, i32, i32, i32, vp, vp, vp, i64, vp, i64, vp]
     L.sc2_rcnn_resize_u8.argtypes = [vp, i64, i64, i64, i32, i32, i32, vp, i32, i32, vp, vp]
     L.sc2_rcnn_normalize_pad.argtypes = [vp, i32, i32, i32, vp, vp, vp, i32, i32, vp]
+    L.sc2_det_input.argtypes = [vp, i64, vp, i32, vp, vp, vp, i32, i32, vp]
     L.sc2_seg_augment_workspace.argtypes = [i32, i32, i32]
     L.sc2_seg_augment_workspace.restype = i64
     L.sc2_seg_augment.argtypes = [vp, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
@@ -1617,6 +1622,43 @@ def rcnn_normalize_pad(pixels_u8, mean, std, out_slot, tag=None):
     with _timed(tag or 'rcnn_normalize_pad'):
         _check(lib().sc2_rcnn_normalize_pad(_ptr(pixels_u8), C, h, w, fm, fs, _ptr(out_slot.detach()), Hp, Wp, _stream()), 'rcnn_normalize_pad')
     return out_slot
+
+
+def det_input(buf, rows, mean, std, out, tag=None):
+    """The detector's input transform of a planned batch (include/sc2_bottleneck.h: sc2_det_input).  buf: flat contiguous uint8 device
+    tensor holding the interleaved [h,w,3] sources; rows: integers [n, DET_INPUT_ROW_INTS] on the host -- (byte offset, h, w, oh, ow,
+    flip) per sample, checked by the library on the host before anything is launched (a bad row raises Sc2Error and `out` is
+    untouched); mean, std: three numbers each; out: a contiguous float32 [n,3,Hp,Wp] device tensor, every element of which is written
+    (+0.0 outside a sample's (oh, ow)).  One launch per DET_INPUT_MAX_BATCH samples.  -> out."""
+    _dev(buf, 'det_input: buf')
+    _dev(out, 'det_input: out')
+    if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
+        raise Sc2Error('det_input: a flat contiguous uint8 buffer is required, got {} {}'.format(buf.dtype, tuple(buf.shape)))
+    table = np.ascontiguousarray(np.asarray(rows.numpy() if isinstance(rows, torch.Tensor) else rows, dtype=np.int64))
+    if table.ndim != 2 or table.shape[0] < 1 or table.shape[1] != DET_INPUT_ROW_INTS:
+        raise Sc2Error('det_input: a descriptor table [n >= 1, {}] is required, got {}'.format(DET_INPUT_ROW_INTS, table.shape))
+    if np.abs(table).max() > 0x7FFFFFFF:
+        raise Sc2Error('det_input: a descriptor field beyond int32')
+    table = table.astype(np.int32)
+    n = int(table.shape[0])
+    if out.dtype != torch.float32 or out.dim() != 4 or out.shape[0] != n or out.shape[1] != 3 or not out.is_contiguous() or \
+            out.device != buf.device:
+        raise Sc2Error('det_input: out must be a contiguous float32 [{},3,Hp,Wp] tensor on {}, got {} {}'.format(
+            n, buf.device, out.dtype, tuple(out.shape)))
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3:
+        raise Sc2Error('det_input: three mean and three std values are required')
+    Hp, Wp = int(out.shape[2]), int(out.shape[3])
+    fm, fs = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    dst = out.detach()
+    with _timed(tag or 'det_input'):
+        for i0 in range(0, n, DET_INPUT_MAX_BATCH):
+            part = np.ascontiguousarray(table[i0:i0 + DET_INPUT_MAX_BATCH])
+            rc = lib().sc2_det_input(_ptr(buf), int(buf.numel()), ctypes.c_void_p(part.ctypes.data), int(part.shape[0]), fm, fs,
+                                     _ptr(dst[i0:i0 + DET_INPUT_MAX_BATCH]), Hp, Wp, _stream())
+            if rc != 0:
+                raise Sc2Error('det_input failed (code {}): {}'.format(rc, last_error()))
+    return out
 
 
 # --------------------------------------------------------------------------------------------- #

@@ -197,6 +197,9 @@ def _to_device(obj, device):
     """tensors inside lists / tuples / dicts moved to `device`; anything else as it is"""
     if isinstance(obj, torch.Tensor):
         return obj.to(device)
+    from .transforms import DeferredDetBatch
+    if isinstance(obj, DeferredDetBatch):      # a planned COCO batch: the detector's transform finishes it, on `device`
+        return obj.to(device)
     if isinstance(obj, (list, tuple)):
         return type(obj)(_to_device(v, device) for v in obj)
     if isinstance(obj, dict):

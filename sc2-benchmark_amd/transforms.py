@@ -20,6 +20,9 @@ image; `config.resolve` maps `torchvision.transforms.<Name>` here).
   `CustomCompose.plan` records the draws of the train / evaluation chain in a `DeferredSegSample`; the collate functions pack those
   into a `DeferredSegBatch`, whose `materialize(device)` runs the whole chain on the library's kernel (csrc/seg_augment.hip,
   `hip.host_policy.seg_augment_hip`) with the host chain's tensors bit for bit, or on the host without a device.
+* `DeferredDetSample` / `DeferredDetBatch` -- the planned form of a COCO sample and batch (`coco_data.Compose.plan`, `coco_collate_fn`):
+  source bytes and the drawn flip; `detection.GeneralizedRCNNTransform` finishes the batch on the device by one copy up and one
+  launch (csrc/det_input.hip, `hip.host_policy.det_input_hip`), `tensors(device)` gives the host chain's float32 list bit for bit.
 * `SimpleQuantizer` / `SimpleDequantizer` -- misc.py:181-231, the 8-bit affine quantizer of the CR+BQ baseline, with
   torchdistill's `QuantizedTensor` / `quantize_tensor` / `dequantize_tensor` (tensor_util) restated here.  On a device tensor the
   8-bit form runs on the library's kernels (csrc/bq.hip), on a CPU tensor on torch ops; both give the same bits.
@@ -446,7 +449,13 @@ def pascal_seg_eval_collate_fn(batch):
 @register_collate_func
 def coco_collate_fn(batch):
     """(image, target dict) pairs of COCO 2017 -> (images as a tuple, targets as a tuple): detection batches are lists, never padded
-    (every `configs/coco2017/**` loader names it)."""
+    (every `configs/coco2017/**` loader names it).  Pairs whose first item is a `DeferredDetSample` -> (one `DeferredDetBatch`, targets
+    as a tuple); a batch that mixes planned and transformed samples raises TypeError."""
+    firsts = [item[0] for item in batch]
+    if any(isinstance(f, DeferredDetSample) for f in firsts):
+        if not all(isinstance(f, DeferredDetSample) for f in firsts):
+            raise TypeError('a batch mixes planned and transformed samples')
+        return DeferredDetBatch(firsts), tuple(item[1] for item in batch)
     return tuple(zip(*batch))
 
 
@@ -974,6 +983,126 @@ def _collate_deferred(batch, with_supp):
     if not all(isinstance(f, DeferredSegSample) for f in firsts):
         raise TypeError('a batch mixes planned and transformed samples')
     return DeferredSegBatch(firsts, extra=(tuple(item[2] for item in batch),) if with_supp else ())
+
+
+class DeferredDetSample(object):
+    """What `coco_data.Compose.plan` hands out in place of the float image: the source bytes as numpy uint8 [h,w,3] and the drawn
+    `flip`, so that a data-loader worker converts nothing.  `.shape` is the (3, h, w) of the tensor it stands for; `host()` is that
+    tensor: `to_tensor` and the flip."""
+    __slots__ = ('image', 'flip')
+
+    def __init__(self, image, flip):
+        assert image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] == 3, 'DeferredDetSample: uint8 [h,w,3] is required'
+        self.image, self.flip = image, bool(flip)
+
+    def __getstate__(self):
+        return {k: getattr(self, k) for k in self.__slots__}
+
+    def __setstate__(self, state):
+        for k, v in state.items():
+            setattr(self, k, v)
+
+    @property
+    def shape(self):
+        return (3, int(self.image.shape[0]), int(self.image.shape[1]))
+
+    def host(self):
+        image = to_tensor(self.image)
+        return image.flip(-1) if self.flip else image
+
+
+class DeferredDetBatch(object):
+    """A batch of `DeferredDetSample`s as `coco_collate_fn` packs it: `buf`, one flat CPU uint8 tensor with every image back to back;
+    `sizes`, the (h, w) of each -- what a consumer reads in place of `img.shape[-2:]`; `flips`; `offsets`, each image's byte offset in
+    `buf`.  `to(device)` only records where the batch is wanted.  `tensors(device)` gives the list of float32 images of the host chain,
+    bit for bit the unplanned samples; `transformed(transform, device)` gives the padded batch of a `detection.GeneralizedRCNNTransform`
+    and its image sizes by one copy up of `buf` and one sc2_det_input launch, cached per (device, min_size, max_size, mean, std,
+    size_divisible): a teacher and a student whose transforms agree share one copy and one launch, and neither may write into the
+    tensor; on a device that is not a HIP device it raises.  A slice shares the buffer and its copy on the device.  `release()` drops
+    the copies and caches.  `launches` counts the launches of the process (for the tests and the tools)."""
+    launches = 0
+
+    def __init__(self, samples, _parts=None):
+        if _parts is not None:
+            self.buf, self.sizes, self.flips, self.offsets = _parts
+        else:
+            assert len(samples) >= 1 and all(isinstance(s, DeferredDetSample) for s in samples)
+            chunks = [np.ascontiguousarray(s.image).reshape(-1) for s in samples]
+            self.buf = torch.from_numpy(np.concatenate(chunks))
+            self.sizes = [tuple(s.shape[-2:]) for s in samples]
+            self.flips = [s.flip for s in samples]
+            self.offsets = [int(v) for v in np.cumsum([0] + [c.size for c in chunks[:-1]])]
+        self.device = torch.device('cpu')
+        self._on_device = dict()      # device -> the copy of buf there (shared with the slices of this batch)
+        self._cache = dict()          # transform parameters -> (padded batch, image sizes)
+        self._lists = dict()          # device -> the float32 list of `tensors`
+
+    def __len__(self):
+        return len(self.sizes)
+
+    def __getitem__(self, index):
+        """a slice: the batch of those samples over the same buffer; an integer: that `DeferredDetSample`, as a view of `buf`"""
+        if isinstance(index, slice):
+            part = DeferredDetBatch(None, _parts=(self.buf, self.sizes[index], self.flips[index], self.offsets[index]))
+            part.device, part._on_device = self.device, self._on_device      # (one buffer: one copy up for all its slices)
+            return part
+        (h, w), off = self.sizes[index], self.offsets[index]
+        return DeferredDetSample(self.buf.numpy()[off:off + 3 * h * w].reshape(h, w, 3), self.flips[index])
+
+    def to(self, device, **kwargs):
+        self.device = torch.device(device)
+        return self
+
+    def pin_memory(self):
+        self.buf = self.buf.pin_memory()
+        return self
+
+    def release(self):
+        """drops the device copies of `buf` and every cached result (the next `tensors` / `transformed` starts from the host bytes)"""
+        self._on_device.clear()
+        self._cache.clear()
+        self._lists.clear()
+
+    def tensors(self, device=None):
+        """the float32 [3,h,w] images of the host chain on `device`, converted once per device: a NEW list of the SAME tensors on every
+        call, which a teacher and a student share -- nobody writes into them"""
+        device = torch.device(self.device if device is None else device)
+        images = self._lists.get(device)
+        if images is None:
+            host = self._lists.get(torch.device('cpu'))
+            if host is None:
+                host = self._lists[torch.device('cpu')] = [self[i].host() for i in range(len(self))]
+            images = self._lists[device] = host if device.type == 'cpu' else [image.to(device, non_blocking=True) for image in host]
+        return list(images)
+
+    def transformed(self, transform, device=None):
+        """-> (f32 [n,3,Hp,Wp] on `device`, [(oh, ow)]): what `transform.forward(self.tensors(device))` puts into its ImageList"""
+        from . import hip
+        device = torch.device(self.device if device is None else device)
+        if device.type != 'cuda':
+            raise hip.Sc2Error('DeferredDetBatch.transformed: {} is not a HIP device (sc2_det_input has no CPU fallback); call the '
+                               'transform itself on the batch, or on `tensors(device)`'.format(device))
+        mean, std = tuple(float(v) for v in transform.image_mean), tuple(float(v) for v in transform.image_std)
+        key = (device, tuple(transform.min_size), transform.max_size, mean, std, transform.size_divisible)
+        hit = self._cache.get(key)
+        if hit is not None:
+            return hit
+        image_sizes = [tuple(int(v) for v in transform.resized_size(h, w)) for h, w in self.sizes]
+        stride = float(transform.size_divisible)
+        max_h = int(math.ceil(max(s[0] for s in image_sizes) / stride) * stride)
+        max_w = int(math.ceil(max(s[1] for s in image_sizes) / stride) * stride)
+        rows = [(off, h, w, oh, ow, int(flip)) for off, (h, w), (oh, ow), flip in zip(self.offsets, self.sizes, image_sizes, self.flips)]
+        with torch.cuda.device(device):         # (the launch goes to the current device's current stream)
+            buf = self._on_device.get(device)
+            if buf is None:
+                buf = self._on_device[device] = self.buf.to(device, non_blocking=True)
+            batched = torch.empty((len(self), 3, max_h, max_w), dtype=torch.float32, device=device)      # every element is written
+            hip.det_input(buf, rows, mean, std, batched)
+            # (the kernel reads `buf` on the current stream: the allocator must not hand its block out before it has run)
+            buf.record_stream(torch.cuda.current_stream(device))
+        DeferredDetBatch.launches += -(-len(self) // hip.DET_INPUT_MAX_BATCH)
+        self._cache[key] = (batched, image_sizes)
+        return batched, image_sizes
 
 
 def get_transform(name):
