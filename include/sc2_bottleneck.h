@@ -1024,6 +1024,43 @@ long long sc2_seg_augment_workspace(int n, int oh, int ow);
 int sc2_seg_augment(const uint8_t *buf, long long nbytes, const int32_t *desc, int n, int oh, int ow, const float *mean,
                     const float *std, float *images, long long *targets, void *ws, int32_t *status, void *stream);
 
+/* Classification input (csrc/cls_input.hip): the ImageNet chains of a whole batch -- RandomResizedCrop -> RandomHorizontalFlip ->
+ * ToTensor -> Normalize, or Resize -> CenterCrop -> ToTensor -> Normalize -- from source bytes straight to the f32 batch.  A sample is a
+ * STORED BOX of a full image, resampled with the full image's coefficients (Pillow's ImagingResample, bilinear, exactly the arithmetic
+ * stated above for sc2_seg_augment), flipped, and shown through an oh x ow window.  tests/ref_cls_input.py restates it; the result
+ * equals the host chain (Pillow + torch) bit for bit.
+ * buf    : nbytes (1 .. 2^31-1) of device memory holding every sample's stored box (h*w*3 bytes, RGB, HWC, rows dense: pitch 3*w).
+ * desc   : int32 [n, SC2_CLS_INPUT_DESC_INTS] on the device, one row per sample:
+ *            [0] offset of the stored box in buf   [1] h  [2] w (the stored box)   [3] full_h  [4] full_w (the axis lengths the
+ *            coefficients see)   [5] row0  [6] col0 (where the stored box sits inside the full image)   [7] nh  [8] nw (resized)
+ *            [9] flip (0 / 1)   [10] top  [11] left (origin of the window in the resized, flipped image)   [12..15] unused
+ *          Training: the box is the crop itself -- full = (h, w), row0 = col0 = 0, (nh, nw) = (oh, ow), top = left = 0 -- so the
+ *          resample clamps at the crop's edges as `img.crop(...).resize(...)` does.  Evaluation: full is the whole image, (nh, nw)
+ *          Resize's size, (top, left) CenterCrop's origin, and the box need hold only the rows and columns the window's taps read.
+ * Output pixel (y, x) of sample i is resized row top + y and resized column left + x, or nw - 1 - (left + x) when flipped, as
+ * (float(p) / 255.0f - mean[c]) / std[c] with two correctly rounded f32 divisions.  An axis with full == resized is the identity pass:
+ * the one coefficient 2^22 on the pixel itself, which is Pillow's skipped pass byte for byte and reads no neighbour.
+ * mean, std : three f32 each, HOST memory (std != 0).
+ * images : f32 [n,3,oh,ow], contiguous; every element of an accepted sample is written.
+ * status : int32 [n], written for every sample: 0, or
+ *            SC2_CLS_INPUT_BAD    sides outside 1 .. SC2_SEG_AUGMENT_MAX_SIDE, a box outside buf or outside the full image, a window outside
+ *                                 the resized image, a flip that is not 0 / 1;
+ *            SC2_CLS_INPUT_RATIO  an axis shrinks by more than 4 (full > 4 * resized: more than nine taps);
+ *            SC2_CLS_INPUT_TAP    a tap of the window lies outside the stored box.
+ *          Such a sample's slot is left unwritten and no address is formed from it.  The caller redoes the batch on the host.
+ * ONE launch on `stream`, one workgroup per 16 x 64 output tile: the tile's 64 column and 16 row entries are computed in the
+ * workgroup's prologue into LDS, so there is no table in memory: sc2_cls_input_workspace is 0 for every batch the entry takes (-1 for
+ * sizes it refuses: n outside 1 .. SC2_CLS_INPUT_MAX_BATCH, a side outside 1 .. SC2_SEG_AUGMENT_MAX_SIDE).  No atomics, no host
+ * synchronisation. */
+#define SC2_CLS_INPUT_DESC_INTS 16
+#define SC2_CLS_INPUT_MAX_BATCH 65535
+#define SC2_CLS_INPUT_RATIO 1
+#define SC2_CLS_INPUT_BAD 2
+#define SC2_CLS_INPUT_TAP 3
+long long sc2_cls_input_workspace(int n, int oh, int ow);
+int sc2_cls_input(const uint8_t *buf, long long nbytes, const int32_t *desc, int n, int oh, int ow, const float *mean, const float *std,
+                  float *images, int32_t *status, void *stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* COCO box AP (csrc/coco.hip): COCOeval's `bbox` protocol with its default parameters, written from the published     */
 /* protocol.  tests/ref_coco.py restates it as a sequential float64 loop; both kernels reproduce that bit for bit.    */

@@ -74,12 +74,17 @@ class ImageFolder(torch.utils.data.Dataset):
     """`torchvision.datasets.ImageFolder(root, transform)`: root/<class>/<image>, classes sorted by name, label = class
     index, images opened with PIL and converted to RGB.  The directory is scanned on first use, so a config whose
     dataset directory does not exist still PARSES; using such a dataset raises, unless SC2_SYNTHETIC_DATA=1 opts in to
-    `SyntheticImageFolder` (random pixels, random labels -- never silently)."""
+    `SyntheticImageFolder` (random pixels, random labels -- never silently).  With `plan_samples` set -- `evaluation.build_data_loader`
+    sets it on the dataset of a loader it gives `transforms.cls_collate_fn`; a loader with any other collate function, and `dataset[i]`
+    by hand, keep getting tensors -- an item whose `transform` can plan it (`transforms.Compose.plan`: the two ImageNet chains) while
+    `hip.host_policy.cls_input_hip` is on is (`DeferredClsSample`, label) instead: source bytes and the drawn parameters;
+    `cls_collate_fn` and `DeferredClsBatch.materialize` finish it, on the device where there is one."""
 
-    def __init__(self, root=None, transform=None, target_transform=None, **kwargs):
+    def __init__(self, root=None, transform=None, target_transform=None, plan_samples=False, **kwargs):
         self.root = None if root is None else os.path.expanduser(str(root))
         self.transform = transform
         self.target_transform = target_transform
+        self.plan_samples = bool(plan_samples)
         self.kwargs = kwargs
         self._samples = None
         self._synthetic = None
@@ -122,7 +127,12 @@ class ImageFolder(torch.utils.data.Dataset):
         with open(path, 'rb') as f:
             img = Image.open(f).convert('RGB')
         if self.transform is not None and not isinstance(self.transform, Placeholder):
-            img = self.transform(img)
+            plan = getattr(self.transform, 'plan', None) if self.plan_samples else None
+            deferred = None
+            if plan is not None:
+                from . import hip
+                deferred = plan(img) if hip.host_policy.cls_input_hip else None
+            img = self.transform(img) if deferred is None else deferred
         if self.target_transform is not None and not isinstance(self.target_transform, Placeholder):
             target = self.target_transform(target)
         return img, target

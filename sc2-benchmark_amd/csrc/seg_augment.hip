@@ -8,6 +8,7 @@
 // include/sc2_bottleneck.h states the contract; tests/ref_pil_resize.py restates the two resizes.
 // Plain kernels: every index checked against its array before use, no atomics, no workgroup waits for another.
 #include "sc2_common.h"
+#include "pil_resample.h"      // pil_coeffs, pil_pixel: shared with cls_input.hip
 
 #pragma clang fp contract(off)   // int() truncates and the sums are ordered: a fused multiply-add in `center` moves xmin for some sizes
 
@@ -15,8 +16,8 @@ namespace {
 
 constexpr int SA_DESC = SC2_SEG_AUGMENT_DESC_INTS;       // int32 words of a descriptor row
 constexpr int SA_ENTRY = SC2_SEG_AUGMENT_ENTRY_INTS;     // int32 words of a table entry: first, count, 9 coefficients, nearest index
-constexpr int SA_TAPS = 9;                               // ksize at filterscale 4
-constexpr int SA_BITS = 22;                              // Pillow's PRECISION_BITS for 8-bit channels
+constexpr int SA_TAPS = PIL_TAPS;                        // ksize at filterscale 4
+constexpr int SA_BITS = PIL_BITS;                        // Pillow's PRECISION_BITS for 8-bit channels
 constexpr int SA_TH = 16, SA_TW = 64;                    // output rows and columns of a tile
 constexpr int SA_THREADS = 256;
 constexpr int SA_ROWS = 4 * SA_TH + SA_TAPS;             // source rows a band can need: (TH - 1) * 4 + 2 * 4 + 1 and some
@@ -62,36 +63,6 @@ struct TableArgs {
     int OH, OW, blocks;      // blocks: workgroups along x that compute coefficients; one more walks the nearest sums
 };
 
-// Pillow's precompute_coeffs + normalize_coeffs_8bpc for output index xx of an axis n_in -> n_out with the bilinear filter.
-__device__ __forceinline__ void sa_coeffs(int n_in, int n_out, int xx, int32_t *e) {
-    const double scale = (double)n_in / (double)n_out;
-    const double fs = scale < 1.0 ? 1.0 : scale;
-    const double support = fs, ss = 1.0 / fs;
-    const double center = ((double)xx + 0.5) * scale;
-    int xmin = (int)(center - support + 0.5);
-    if (xmin < 0) xmin = 0;
-    int xmax = (int)(center + support + 0.5);
-    if (xmax > n_in) xmax = n_in;
-    xmax -= xmin;
-    if (xmax > SA_TAPS) xmax = SA_TAPS;      // (cannot happen at filterscale <= 4: 2 * support + 1 <= 9)
-    if (xmax < 0) xmax = 0;
-    double wt[SA_TAPS];
-    double ww = 0.0;
-#pragma unroll
-    for (int x = 0; x < SA_TAPS; ++x) {
-        const double v = fabs(((double)(x + xmin) - center + 0.5) * ss);
-        wt[x] = (x < xmax && v < 1.0) ? 1.0 - v : 0.0;
-        if (x < xmax) ww += wt[x];
-    }
-    e[0] = xmin;
-    e[1] = xmax;
-#pragma unroll
-    for (int x = 0; x < SA_TAPS; ++x) {
-        const double p = ww != 0.0 ? wt[x] / ww : wt[x];
-        e[2 + x] = x < xmax ? (int)(0.5 + p * (double)(1 << SA_BITS)) : 0;
-    }
-}
-
 __global__ __launch_bounds__(SA_THREADS) void seg_augment_tables_kernel(const TableArgs a) {
     const int i = blockIdx.z, axis = blockIdx.y;      // axis 0: columns, 1: rows
     const Desc s = sa_desc(a.desc, i);
@@ -109,7 +80,7 @@ __global__ __launch_bounds__(SA_THREADS) void seg_augment_tables_kernel(const Ta
         const int r = origin + o;                    // position in the padded, flipped, resized image
         int32_t e[SA_ENTRY];
         if (o < ext && r < n_out) {
-            sa_coeffs(n_in, n_out, flip ? n_out - 1 - r : r, e);
+            pil_coeffs(n_in, n_out, flip ? n_out - 1 - r : r, e);
         } else {
 #pragma unroll
             for (int k = 0; k < SA_ENTRY; ++k) e[k] = 0;
@@ -136,17 +107,6 @@ __global__ __launch_bounds__(SA_THREADS) void seg_augment_tables_kernel(const Ta
         }
         xo += step;
     }
-}
-
-// The three bytes of the pixel at byte offset `off` of an image of `bytes` bytes, R in the low byte: one unaligned four-byte load where
-// the byte behind the pixel is still the image's (every pixel but the last), three byte loads otherwise.
-__device__ __forceinline__ uint32_t sa_pixel(const uint8_t *img, size_t off, size_t bytes) {
-    if (off + 4 <= bytes) {
-        uint32_t v;
-        __builtin_memcpy(&v, img + off, 4);
-        return v;
-    }
-    return (uint32_t)img[off] | (uint32_t)img[off + 1] << 8 | (uint32_t)img[off + 2] << 16;
 }
 
 struct TileArgs {
@@ -192,7 +152,7 @@ __global__ __launch_bounds__(SA_THREADS) void seg_augment_tile_kernel(const Tile
 #pragma unroll
                 for (int t = 0; t < SA_TAPS; ++t) {
                     if (t < count) {
-                        const uint32_t p = sa_pixel(img, ((size_t)sr * s.w + min(max(first + t, 0), s.w - 1)) * 3, img_bytes);
+                        const uint32_t p = pil_pixel(img, ((size_t)sr * s.w + min(max(first + t, 0), s.w - 1)) * 3, img_bytes);
                         acc0 += (int)(p & 0xFFu) * k[t];
                         acc1 += (int)((p >> 8) & 0xFFu) * k[t];
                         acc2 += (int)((p >> 16) & 0xFFu) * k[t];

@@ -64,6 +64,7 @@ def _evaluate_pipelined(model, data_loader, device, max_samples, pipeline_kwargs
     launch on its own HIP stream, top-1 / top-5 hits are counted on the device behind each back stage -- the host reads
     two numbers at the end instead of two per batch.  -> (correct@1, correct@5, samples) as floats."""
     from .pipeline import StagePipeline
+    from .transforms import DeferredClsBatch
     pipe = StagePipeline(model, device, **(pipeline_kwargs or {}))
     # one row of hit counters per back stream: back stage j runs on back stream j % len(back_streams), and two streams adding
     # into the same two addresses would race
@@ -78,7 +79,9 @@ def _evaluate_pipelined(model, data_loader, device, max_samples, pipeline_kwargs
                 return
             targets[i] = target.to(device, non_blocking=True)
             seen[0] += len(image)
-            yield image.to(device, non_blocking=True)
+            # (a planned batch -- transforms.DeferredClsBatch -- is finished here, on the caller's stream like the copy it replaces: the
+            #  front stage's wait on that stream orders its launch before the encoder)
+            yield image.materialize(device) if isinstance(image, DeferredClsBatch) else image.to(device, non_blocking=True)
 
     def on_output(step, output, nbytes, status):
         # called inside the back stream's context.  The labels were copied on the caller's stream (ordered before this point
@@ -126,7 +129,10 @@ def evaluate(model, data_loader, device, max_samples=None, log_freq=1000, title=
         c1, c5, seen = _evaluate_pipelined(model, data_loader, device, max_samples, pipeline_kwargs)
         acc1.total, acc1.count = 100.0 * c1, seen       # (Meter: sum of percent x batch size, and the sample count)
         acc5.total, acc5.count = 100.0 * c5, seen
+    from .transforms import DeferredClsBatch
     for i, (image, target) in enumerate(() if pipelined else data_loader):
+        if isinstance(image, DeferredClsBatch):     # a planned ImageNet batch: crop, resize, ToTensor and Normalize run here, on `device`
+            image = image.materialize(device)
         if isinstance(image, torch.Tensor):
             image = image.to(device, non_blocking=True)
         if isinstance(target, torch.Tensor):
@@ -288,6 +294,9 @@ def build_data_loader(dataset_dict, loader_config):
     if sampler_cls is not None and not isinstance(sampler_cls, C.Placeholder):
         sampler = sampler_cls(dataset, **(sampler_cfg.get('kwargs') or {}))
     collate = COLLATE_FUNC_DICT.get(loader_config.get('collate_fn'))      # default_collate_w_pil, pascal_seg_collate_fn, pascal_seg_eval_collate_fn
+    if loader_config.get('collate_fn') is None and isinstance(dataset, C.ImageFolder):
+        collate = COLLATE_FUNC_DICT['cls_collate_fn']      # default_collate, but for the samples an ImageFolder plans ...
+        dataset.plan_samples = True                         # ... which it does for this collate function only
     batch_sampler_cfg = loader_config.get('batch_sampler')
     if batch_sampler_cfg is not None:
         from .coco_data import BATCH_SAMPLER_DICT

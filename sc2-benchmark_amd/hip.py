@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     'sc2_gdn_bwd_pre_blocks', 'sc2_colsum_blocks', 'sc2_gdn_bwd_post_blocks', 'sc2_layout_blocks', 'sc2_gdn1_rows_units', 'sc2_gdn1_rows_workgroups',
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
-    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_roi_align_backward', 'sc2_box_match_ws_bytes', 'sc2_box_match', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_seg_augment_workspace', 'sc2_seg_augment', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
+    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_roi_align_backward', 'sc2_box_match_ws_bytes', 'sc2_box_match', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_seg_augment_workspace', 'sc2_seg_augment', 'sc2_cls_input_workspace', 'sc2_cls_input', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
     'sc2_jpeg_max_bytes', 'sc2_jpeg_tensor_codec', 'sc2_jpeg_image_max_bytes', 'sc2_jpeg_image_workspace_bytes', 'sc2_jpeg_image_codec',
     'sc2_rcnn_resize_u8', 'sc2_rcnn_normalize_pad', 'sc2_det_input',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
@@ -81,6 +81,8 @@ JPEG_IMAGE_MAX_SIDE = 2048       # SC2_JPEG_IMAGE_MAX_SIDE
 SEG_AUGMENT_DESC_INTS, SEG_AUGMENT_ENTRY_INTS = 16, 12      # SC2_SEG_AUGMENT_*
 SEG_AUGMENT_MAX_SIDE, SEG_AUGMENT_MAX_BATCH = 16384, 65535
 SEG_AUGMENT_RATIO, SEG_AUGMENT_BAD = 1, 2
+CLS_INPUT_DESC_INTS, CLS_INPUT_MAX_BATCH = 16, 65535       # SC2_CLS_INPUT_*
+CLS_INPUT_RATIO, CLS_INPUT_BAD, CLS_INPUT_TAP = 1, 2, 3
 JPEG_IMAGE_CHUNK_BLOCKS = 128    # SC2_JPEG_IMAGE_CHUNK_BLOCKS
 DET_INPUT_MAX_BATCH, DET_INPUT_ROW_INTS = 64, 6      # SC2_DET_INPUT_*
 DET_INPUT_TILE_H, DET_INPUT_TILE_W = 16, 256
@@ -165,6 +167,7 @@ class HostPolicy(object):
     rcnn_input_hip = True      # detection.RCNNTransformWithCompression (eval, plain JPEG, f32 RGB device images): resize -> codec -> normalise + pad per image on sc2_rcnn_resize_u8 + sc2_jpeg_image_codec + sc2_rcnn_normalize_pad, one read-back per list (False: the reference's loop through Pillow on the host, A/B; tools/rcnn_input_times.py, 480 x 640 -> 800 x 1066 at quality 90: 2.79 against 25.7 ms at one image per call, 16.0 against 88.3 ms at six; the two new kernels alone 0.009 ms each, the codec 2.63 ms)
     seg_augment_hip = True     # transforms.DeferredSegBatch.materialize (the PASCAL CustomCompose chain, planned in the data-loader workers) on sc2_seg_augment: one copy up and two launches per batch (False: Pillow + torch on the host with the recorded draws, A/B; tools/seg_augment_times.py, 16 sources of 375 x 500 -> 513 x 513: 0.38 ms per batch with the copy up and the read-back, the launches alone 0.102 ms, against 86.0 ms through Pillow on one core)
     det_input_hip = True       # detection.GeneralizedRCNNTransform on a transforms.DeferredDetBatch (the COCO loader's ImageToTensor -> [flip] chain, planned in the data-loader workers) on sc2_det_input: one copy up of the source bytes and one launch per batch; coco_data.CustomCocoDetection plans its samples only while this is on (False: the float32 list of the host chain copied up, then normalise + F.interpolate + pad per image, A/B; tools/det_input_times.py, six 480 x 640 sources -> [6,3,800,1088]: 0.185 against 0.884 ms per batch with the copies up, the launch alone 0.042 ms)
+    cls_input_hip = True       # transforms.DeferredClsBatch.materialize (the ImageNet train / eval chains of config.ImageFolder, planned in the data-loader workers) on sc2_cls_input: one copy up of the stored boxes and one launch per batch; config.ImageFolder plans its samples only while this is on (False: Pillow + ToTensor + Normalize per image in the worker and a float32 batch copied up, A/B; tools/cls_input_times.py, 256 decoded sources of 375 x 500 -> [256,3,224,224], one core: the worker's plan + pack 26.3 ms and materialize 3.6 ms with the copy up and the read-back against 271.5 ms per batch in the eval form, 21.6 + 2.9 against 182.9 ms in the train form; the launch alone 0.159 / 0.144 ms)
     seg_predict_hip = True     # dense.seg_labels (BaseSegmentationModel.predict, SegEvaluator.update_logits) of device tensors on sc2_seg_predict (False: interpolate + argmax + bincount, A/B)
     seg_loss_hip = True        # dense.seg_cross_entropy (DictLossWrapper over a deferred-resize segmentation student) of device tensors on sc2_seg_ce_forward + sc2_seg_ce_backward (False: F.interpolate + F.cross_entropy + autograd, A/B; tools/seg_loss_times.py, out + aux forward + backward at [8,21,65,65] -> 513 x 513: 1.27 against 2.70 ms with f32 logits, 1.27 against 1.72 ms with bf16, 20 against 707 MB of peak allocation)
 
@@ -370,6 +373,9 @@ def lib():
     L.sc2_seg_augment_workspace.argtypes = [i32, i32, i32]
     L.sc2_seg_augment_workspace.restype = i64
     L.sc2_seg_augment.argtypes = [vp, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.sc2_cls_input_workspace.argtypes = [i32, i32, i32]
+    L.sc2_cls_input_workspace.restype = i64
+    L.sc2_cls_input.argtypes = [vp, i64, vp, i32, i32, i32, vp, vp, vp, vp, vp]
     L.sc2_rans_host_tables_create.argtypes = [vp, i32, i32, vp, vp, ctypes.POINTER(vp)]
     L.sc2_rans_host_tables_destroy.argtypes = [vp]
     L.sc2_rans_host_tables_destroy.restype = None
@@ -1755,6 +1761,93 @@ def seg_augment(buf, desc, size, mean, std, images_out=None, targets_out=None, r
         _check(lib().sc2_seg_augment(_ptr(buf), int(buf.numel()), _ptr(d_desc), n, oh, ow, fm, fs, _ptr(images), _ptr(targets), _ptr(ws),
                                      _ptr(status), _stream()), 'seg_augment')
     return SegAugment(images, targets, status, ws if return_workspace else None)
+
+
+# --------------------------------------------------------------------------------------------- #
+# classification input: the ImageNet train / eval chains of a batch from stored boxes of its sources (csrc/cls_input.hip)
+# --------------------------------------------------------------------------------------------- #
+CLS_INPUT_FIELDS = ('offset', 'h', 'w', 'full_h', 'full_w', 'row0', 'col0', 'nh', 'nw', 'flip', 'top', 'left')
+ClsInput = collections.namedtuple('ClsInput', ['images', 'status'])
+
+
+def cls_input_desc(**fields):
+    """One descriptor row (int32 [CLS_INPUT_DESC_INTS]) from CLS_INPUT_FIELDS by name.  offset, h, w, nh, nw are required; the rest
+    default to the train form: full_h / full_w = h / w, row0 = col0 = 0, flip = 0, top = left = 0."""
+    import numpy as np
+    for name, default in (('full_h', fields.get('h')), ('full_w', fields.get('w')), ('row0', 0), ('col0', 0), ('flip', 0), ('top', 0),
+                          ('left', 0)):
+        fields.setdefault(name, default)
+    row = np.zeros(CLS_INPUT_DESC_INTS, dtype=np.int32)
+    for k, name in enumerate(CLS_INPUT_FIELDS):
+        row[k] = int(fields.pop(name))
+    assert not fields, 'cls_input_desc: unknown fields {}'.format(sorted(fields))
+    return row
+
+
+def cls_input_check(desc, nbytes, oh, ow):
+    """Refuses a malformed descriptor table on the host, before any launch (ValueError naming the sample and the field): sides below 1
+    or above SEG_AUGMENT_MAX_SIDE, a stored box outside the buffer or outside the full image, a flip that is not 0 / 1, a window outside
+    the resized image.  A ratio above 4 and a tap outside the stored box are the kernel's to flag (its status word): they are well
+    formed.  desc: integer array [n, CLS_INPUT_DESC_INTS]."""
+    import numpy as np
+    desc = np.asarray(desc)
+    if desc.ndim != 2 or desc.shape[1] != CLS_INPUT_DESC_INTS or desc.shape[0] < 1 or desc.shape[0] > CLS_INPUT_MAX_BATCH:
+        raise ValueError('cls_input: a descriptor table [1..{}, {}] is required, got {}'.format(
+            CLS_INPUT_MAX_BATCH, CLS_INPUT_DESC_INTS, desc.shape))
+    if not (1 <= oh <= SEG_AUGMENT_MAX_SIDE and 1 <= ow <= SEG_AUGMENT_MAX_SIDE):
+        raise ValueError('cls_input: a {} x {} output slot (sides 1..{})'.format(oh, ow, SEG_AUGMENT_MAX_SIDE))
+    if not 1 <= nbytes <= 0x7FFFFFFF:
+        raise ValueError('cls_input: a source buffer of {} bytes (1..2^31-1)'.format(nbytes))
+    for i, row in enumerate(desc.tolist()):
+        f = dict(zip(CLS_INPUT_FIELDS, row))
+
+        def refuse(name, why):
+            raise ValueError('cls_input: sample {}: {} = {}: {}'.format(i, name, f[name], why))
+        for name in ('h', 'w', 'full_h', 'full_w', 'nh', 'nw'):
+            if not 1 <= f[name] <= SEG_AUGMENT_MAX_SIDE:
+                refuse(name, 'sides are 1..{}'.format(SEG_AUGMENT_MAX_SIDE))
+        if f['offset'] < 0 or f['offset'] + 3 * f['h'] * f['w'] > nbytes:
+            refuse('offset', 'the stored box lies outside the buffer of {} bytes'.format(nbytes))
+        for name, side, full in (('row0', 'h', 'full_h'), ('col0', 'w', 'full_w')):
+            if f[name] < 0 or f[name] + f[side] > f[full]:
+                refuse(name, 'the stored box of {} lies outside the full image of {}'.format(f[side], f[full]))
+        if f['flip'] not in (0, 1):
+            refuse('flip', '0 or 1')
+        for name, ext, resized in (('top', oh, 'nh'), ('left', ow, 'nw')):
+            if f[name] < 0 or f[name] + ext > f[resized]:
+                refuse(name, 'the window of {} lies outside the resized image of {}'.format(ext, f[resized]))
+    return desc
+
+
+def cls_input(buf, desc, size, mean, std, images_out=None, tag=None):
+    """The classification input chain of a batch on the device (include/sc2_bottleneck.h: sc2_cls_input).  buf: uint8 device tensor
+    holding the stored boxes; desc: integer array / CPU tensor [n, CLS_INPUT_DESC_INTS] (rows from `cls_input_desc`), checked by
+    `cls_input_check` before anything is launched; size: (oh, ow); mean, std: three numbers each.  images_out f32 [n,3,oh,ow]: a
+    caller's contiguous tensor to write into.
+    -> ClsInput(images, status int32 [n] on the device): nothing is read back; a sample whose status is not 0 (CLS_INPUT_RATIO: an
+    axis shrinks by more than 4; CLS_INPUT_TAP: a tap outside its stored box) has its slot unwritten."""
+    import numpy as np
+    _dev(buf, 'cls_input: buf')
+    if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
+        raise Sc2Error('cls_input: a flat contiguous uint8 buffer is required, got {} {}'.format(buf.dtype, tuple(buf.shape)))
+    oh, ow = int(size[0]), int(size[1])
+    table = np.ascontiguousarray(desc.numpy() if isinstance(desc, torch.Tensor) else desc)
+    cls_input_check(table, int(buf.numel()), oh, ow)
+    n, dev = int(table.shape[0]), buf.device
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != 3 or len(std) != 3 or any(v == 0.0 for v in std):
+        raise ValueError('cls_input: three mean and three non-zero std values are required')
+    d_desc = torch.from_numpy(table.astype(np.int32)).to(dev, non_blocking=True)
+    images = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=dev) if images_out is None else _dev(images_out, 'cls_input: images_out')
+    if images.dtype != torch.float32 or tuple(images.shape) != (n, 3, oh, ow) or not images.is_contiguous() or images.device != dev:
+        raise Sc2Error('cls_input: images_out must be a contiguous float32 [{},3,{},{}] tensor on {}'.format(n, oh, ow, dev))
+    assert int(lib().sc2_cls_input_workspace(n, oh, ow)) == 0      # one launch, tables in LDS: nothing to allocate
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    fm, fs = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+    with _timed(tag or 'cls_input'):
+        _check(lib().sc2_cls_input(_ptr(buf), int(buf.numel()), _ptr(d_desc), n, oh, ow, fm, fs, _ptr(images), _ptr(status), _stream()),
+               'cls_input')
+    return ClsInput(images, status)
 
 
 # --------------------------------------------------------------------------------------------- #

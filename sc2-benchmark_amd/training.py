@@ -197,8 +197,8 @@ def _to_device(obj, device):
     """tensors inside lists / tuples / dicts moved to `device`; anything else as it is"""
     if isinstance(obj, torch.Tensor):
         return obj.to(device)
-    from .transforms import DeferredDetBatch
-    if isinstance(obj, DeferredDetBatch):      # a planned COCO batch: the detector's transform finishes it, on `device`
+    from .transforms import DeferredClsBatch, DeferredDetBatch
+    if isinstance(obj, (DeferredClsBatch, DeferredDetBatch)):      # a planned batch: its consumer finishes it, on `device`
         return obj.to(device)
     if isinstance(obj, (list, tuple)):
         return type(obj)(_to_device(v, device) for v in obj)
@@ -483,9 +483,11 @@ class DistillationStage(object):
             return self.teacher(tb)
 
     def forward_process(self, batch, targets=None):
-        from .transforms import DeferredSegBatch
+        from .transforms import DeferredClsBatch, DeferredSegBatch
         if isinstance(batch, DeferredSegBatch):     # a planned PASCAL batch: the augmentation runs here, on the stage's device
             batch, targets = batch.materialize(self.device)
+        if isinstance(batch, DeferredClsBatch):     # a planned ImageNet batch likewise
+            batch = batch.materialize(self.device)
         if 'forward_batch_target' in (self.t_forward_proc, self.s_forward_proc):
             return self._forward_batch_target(batch, targets)
         side = self._teacher_side_stream(batch)

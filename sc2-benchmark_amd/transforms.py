@@ -20,6 +20,9 @@ image; `config.resolve` maps `torchvision.transforms.<Name>` here).
   `CustomCompose.plan` records the draws of the train / evaluation chain in a `DeferredSegSample`; the collate functions pack those
   into a `DeferredSegBatch`, whose `materialize(device)` runs the whole chain on the library's kernel (csrc/seg_augment.hip,
   `hip.host_policy.seg_augment_hip`) with the host chain's tensors bit for bit, or on the host without a device.
+* `DeferredClsSample` / `DeferredClsBatch` -- the planned form of an ImageNet sample and batch (`Compose.plan`, `cls_collate_fn`): the box
+  of source bytes the chain's output depends on and the drawn crop / flip; `materialize(device)` finishes the batch by one copy up and
+  one launch (csrc/cls_input.hip, `hip.host_policy.cls_input_hip`) with the host chain's tensors bit for bit, or on the host.
 * `DeferredDetSample` / `DeferredDetBatch` -- the planned form of a COCO sample and batch (`coco_data.Compose.plan`, `coco_collate_fn`):
   source bytes and the drawn flip; `detection.GeneralizedRCNNTransform` finishes the batch on the device by one copy up and one
   launch (csrc/det_input.hip, `hip.host_policy.det_input_hip`), `tensors(device)` gives the host chain's float32 list bit for bit.
@@ -146,6 +149,62 @@ class Compose(object):
     def __repr__(self):
         return 'Compose({})'.format(self.transforms)
 
+    def _cls_chain(self):
+        """('train', crop, flip, normalize) for RandomResizedCrop -> RandomHorizontalFlip -> ToTensor -> Normalize, ('eval', resize,
+        crop, normalize) for Resize -> CenterCrop -> ToTensor -> Normalize -- the two chains of configs/ilsvrc2012/** -- bilinear, with
+        three-value mean / std and a Resize size that is an int or (h, w); else None."""
+        ts = list(self.transforms)
+        if len(ts) != 4 or type(ts[2]) is not ToTensor or type(ts[3]) is not Normalize or len(ts[3].mean) != 3 or len(ts[3].std) != 3:
+            return None
+        if any(float(v) == 0.0 for v in ts[3].std):
+            return None
+        if type(ts[0]) is RandomResizedCrop and type(ts[1]) is RandomHorizontalFlip:
+            size = ts[0].size
+            if ts[0].resize.interpolation != INTERPOLATION['bilinear'] or len(size) != 2 or not all(isinstance(v, int) and v >= 1 for v in size):
+                return None
+            return 'train', ts[0], ts[1], ts[3]
+        if type(ts[0]) is Resize and type(ts[1]) is CenterCrop:
+            size = ts[0].size
+            pair = isinstance(size, (list, tuple)) and len(size) == 2 and all(isinstance(v, int) for v in size)
+            if ts[0].interpolation != INTERPOLATION['bilinear'] or not ((isinstance(size, int) and not isinstance(size, bool)) or pair):
+                return None
+            if len(ts[1].size) != 2 or not all(isinstance(v, int) and v >= 1 for v in ts[1].size):
+                return None
+            return 'eval', ts[0], ts[1], ts[3]
+        return None
+
+    def plan(self, img):
+        """One of the two ImageNet chains (`_cls_chain`) on an 8-bit RGB PIL image: draws what `__call__` would draw, in its order, and
+        returns the `DeferredClsSample` -- the box of source bytes the chain's output depends on and the parameters, no pixel resampled
+        (but for a sample beyond sc2_cls_input's ratio cap, which is finished here, by Pillow).  Any other chain or input, or a centre
+        crop larger than the resized image (which pads): None, and nothing drawn."""
+        chain = self._cls_chain()
+        if chain is None or not _is_pil(img) or img.mode != 'RGB' or min(img.size) < 1:
+            return None
+        w, h = img.size
+        if chain[0] == 'train':
+            _, crop, flip, normalize = chain
+            oh, ow = crop.size
+            top, left, ch, cw = crop.draw(h, w)
+            flipped = flip.draw()
+            if ch > 4 * oh or cw > 4 * ow:       # beyond the kernel's nine taps: Pillow, here
+                done = img.crop((left, top, left + cw, top + ch)).resize((ow, oh), INTERPOLATION['bilinear'])
+                return DeferredClsSample.identity(_hflip(done) if flipped else done, normalize.mean, normalize.std)
+            box = np.asarray(img.crop((left, top, left + cw, top + ch)))
+            return DeferredClsSample(box, ch, cw, 0, 0, oh, ow, flipped, 0, 0, oh, ow, normalize.mean, normalize.std)
+        _, resize, crop, normalize = chain
+        oh, ow = crop.size
+        nh, nw = _resized_hw(h, w, resize.size if isinstance(resize.size, int) else list(resize.size))
+        if oh > nh or ow > nw:
+            return None
+        top, left = int(round((nh - oh) / 2.0)), int(round((nw - ow) / 2.0))
+        if h > 4 * nh or w > 4 * nw:
+            done = img.resize((nw, nh), INTERPOLATION['bilinear']).crop((left, top, left + ow, top + oh))
+            return DeferredClsSample.identity(done, normalize.mean, normalize.std)
+        (r0, r1), (c0, c1) = pil_tap_span(h, nh, top, oh), pil_tap_span(w, nw, left, ow)
+        box = np.asarray(img.crop((c0, r0, c1, r1)))
+        return DeferredClsSample(box, h, w, r0, c0, nh, nw, False, top, left, oh, ow, normalize.mean, normalize.std)
+
 
 INTERPOLATION = {'nearest': 0, 'lanczos': 1, 'bilinear': 2, 'bicubic': 3, 'box': 4, 'hamming': 5}
 
@@ -233,8 +292,12 @@ class RandomHorizontalFlip(nn.Module):
         super().__init__()
         self.p = p
 
+    def draw(self):
+        """True when the image is flipped: the one number `forward` draws"""
+        return not random.random() >= self.p
+
     def forward(self, img):
-        if random.random() >= self.p:
+        if not self.draw():
             return img
         if _is_pil(img):
             from PIL import Image
@@ -250,8 +313,8 @@ class RandomResizedCrop(nn.Module):
         self.scale, self.ratio = scale, ratio
         self.resize = Resize(self.size, interpolation if interpolation is not None else 'bilinear')
 
-    def forward(self, img):
-        h, w = _size_hw(img)
+    def draw(self, h, w):
+        """-> (top, left, ch, cw), the crop box of an h x w image: the numbers `forward` draws, in its order"""
         area = h * w
         log_ratio = (math.log(self.ratio[0]), math.log(self.ratio[1]))
         top = left = 0
@@ -270,6 +333,10 @@ class RandomResizedCrop(nn.Module):
             elif in_ratio > max(self.ratio):
                 ch, cw = h, int(round(h * max(self.ratio)))
             top, left = (h - ch) // 2, (w - cw) // 2
+        return top, left, ch, cw
+
+    def forward(self, img):
+        top, left, ch, cw = self.draw(*_size_hw(img))
         img = img.crop((left, top, left + cw, top + ch)) if _is_pil(img) else img[..., top:top + ch, left:left + cw]
         return self.resize(img)
 
@@ -983,6 +1050,160 @@ def _collate_deferred(batch, with_supp):
     if not all(isinstance(f, DeferredSegSample) for f in firsts):
         raise TypeError('a batch mixes planned and transformed samples')
     return DeferredSegBatch(firsts, extra=(tuple(item[2] for item in batch),) if with_supp else ())
+
+
+def pil_tap_bounds(n_in, n_out, xx):
+    """(first, count) of the source indices Pillow's bilinear resample of an axis n_in -> n_out reads for output index xx: float64,
+    every operation rounded once (tests/ref_pil_resize.py proves the rule against Pillow).  An axis of equal lengths is the pass
+    Pillow skips: the pixel itself."""
+    if n_in == n_out:
+        return xx, 1
+    scale = n_in / n_out
+    support = max(scale, 1.0)
+    center = (xx + 0.5) * scale
+    first = max(int(center - support + 0.5), 0)
+    return first, min(int(center + support + 0.5), n_in) - first
+
+
+def pil_tap_span(n_in, n_out, origin, length):
+    """[lo, hi): the source indices the outputs origin .. origin + length - 1 read (the bounds do not decrease with the index)"""
+    last = pil_tap_bounds(n_in, n_out, origin + length - 1)
+    return pil_tap_bounds(n_in, n_out, origin)[0], last[0] + last[1]
+
+
+class DeferredClsSample(object):
+    """What `Compose.plan` hands out in place of the transformed image: `image`, uint8 [h,w,3], a box of the source at (row0, col0) of
+    a full_h x full_w image -- the only bytes the output depends on -- and the parameters: (nh, nw) the resized size of the FULL image,
+    flip, (top, left) the origin of the out_h x out_w window in the resized, flipped image, mean / std.  Train form: the box is the
+    drawn crop and full = its size (Pillow clamps at the crop's edges).  Evaluation form: full is the whole image and the box the rows
+    and columns the window's taps read.  A data-loader worker neither resamples nor opens the device."""
+    __slots__ = ('image', 'full_h', 'full_w', 'row0', 'col0', 'nh', 'nw', 'flip', 'top', 'left', 'out_h', 'out_w', 'mean', 'std')
+
+    def __init__(self, image, full_h, full_w, row0, col0, nh, nw, flip, top, left, out_h, out_w, mean, std):
+        assert image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] == 3, 'DeferredClsSample: uint8 [h,w,3] is required'
+        self.image = image
+        self.full_h, self.full_w, self.row0, self.col0 = int(full_h), int(full_w), int(row0), int(col0)
+        self.nh, self.nw, self.flip, self.top, self.left = int(nh), int(nw), bool(flip), int(top), int(left)
+        self.out_h, self.out_w = int(out_h), int(out_w)
+        self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
+
+    @classmethod
+    def identity(cls, window, mean, std):
+        """The sample of a finished 8-bit window (PIL RGB or uint8 [h,w,3]): nothing is left to resample, flip or crop."""
+        window = np.asarray(window)
+        h, w = window.shape[:2]
+        return cls(window, h, w, 0, 0, h, w, False, 0, 0, h, w, mean, std)
+
+    def __getstate__(self):
+        return {k: getattr(self, k) for k in self.__slots__}
+
+    def __setstate__(self, state):
+        for k, v in state.items():
+            setattr(self, k, v)
+
+    def host(self):
+        """The tensor `Compose.__call__` returns for these draws: Pillow and torch on the host.  A box smaller than its full image is
+        laid into a canvas of that size first: no tap of the window reads the canvas outside the box."""
+        from PIL import Image
+        h, w = self.image.shape[:2]
+        if (h, w) == (self.full_h, self.full_w):
+            image = Image.fromarray(np.ascontiguousarray(self.image))
+        else:
+            canvas = np.zeros((self.full_h, self.full_w, 3), np.uint8)
+            canvas[self.row0:self.row0 + h, self.col0:self.col0 + w] = self.image
+            image = Image.fromarray(canvas)
+        if (self.nh, self.nw) != (self.full_h, self.full_w):
+            image = image.resize((self.nw, self.nh), INTERPOLATION['bilinear'])
+        if self.flip:
+            image = _hflip(image)
+        if (self.top, self.left, self.out_h, self.out_w) != (0, 0, self.nh, self.nw):
+            image = _crop(image, self.top, self.left, self.out_h, self.out_w)
+        return Normalize(self.mean, self.std)(to_tensor(image))
+
+
+class DeferredClsBatch(object):
+    """A batch of `DeferredClsSample`s as `cls_collate_fn` packs it: `buf`, one flat CPU uint8 tensor with every stored box back to
+    back; `desc`, the int32 descriptor table of `hip.cls_input` [n, 16]; `size`, the (height, width) every sample ends at; mean / std.
+    `to(device)` only records where the batch is wanted.  `materialize(device)` gives the float32 [n,3,H,W] batch the host transforms
+    and `default_collate` would have given, bit for bit -- on a HIP device with `hip.host_policy.cls_input_hip` on by one copy up of
+    `buf`, one sc2_cls_input launch and one read-back of the status words, otherwise (or when a status word is set) by the host
+    transforms with the recorded draws."""
+    fallbacks = 0       # batches a status word sent back to the host path (process-wide, for the tests and the tools)
+
+    def __init__(self, samples):
+        assert len(samples) >= 1 and all(isinstance(s, DeferredClsSample) for s in samples)
+        first = samples[0]
+        if any((s.mean, s.std) != (first.mean, first.std) for s in samples):
+            raise ValueError('DeferredClsBatch: samples of different normalisations')
+        if any((s.out_h, s.out_w) != (first.out_h, first.out_w) for s in samples):
+            raise ValueError('DeferredClsBatch: samples of different output sizes')
+        from . import hip
+        self.mean, self.std, self.size = first.mean, first.std, (first.out_h, first.out_w)
+        self.device = torch.device('cpu')
+        rows, chunks, offset = [], [], 0
+        for s in samples:
+            box = np.ascontiguousarray(s.image).reshape(-1)
+            rows.append(hip.cls_input_desc(offset=offset, h=s.image.shape[0], w=s.image.shape[1], full_h=s.full_h, full_w=s.full_w,
+                                           row0=s.row0, col0=s.col0, nh=s.nh, nw=s.nw, flip=int(s.flip), top=s.top, left=s.left))
+            chunks.append(box)
+            offset += box.size
+        self.buf = torch.from_numpy(np.concatenate(chunks))
+        self.desc = torch.from_numpy(np.stack(rows))
+
+    def __len__(self):
+        return int(self.desc.shape[0])
+
+    def samples(self):
+        """The `DeferredClsSample`s again, as views of `buf`."""
+        out, buf = [], self.buf.numpy()
+        for row in self.desc.tolist():
+            off, h, w, fh, fw, row0, col0, nh, nw, flip, top, left = row[:12]
+            out.append(DeferredClsSample(buf[off:off + 3 * h * w].reshape(h, w, 3), fh, fw, row0, col0, nh, nw, flip, top, left,
+                                         self.size[0], self.size[1], self.mean, self.std))
+        return out
+
+    def to(self, device, **kwargs):
+        self.device = torch.device(device)
+        return self
+
+    def pin_memory(self):
+        self.buf = self.buf.pin_memory()
+        return self
+
+    def materialize_host(self, device=None):
+        images = torch.stack([s.host() for s in self.samples()])
+        return images if device is None else images.to(device, non_blocking=True)
+
+    def materialize(self, device=None):
+        """-> images f32 [n,3,H,W] on `device` (default: where `to` sent the batch)"""
+        from . import hip
+        device = torch.device(self.device if device is None else device)
+        if device.type != 'cuda' or not hip.host_policy.cls_input_hip:
+            return self.materialize_host(device)
+        with torch.cuda.device(device):         # (the launch goes to the current device's current stream)
+            buf = self.buf.to(device, non_blocking=True)
+            res = hip.cls_input(buf, self.desc, self.size, self.mean, self.std)
+            # (the kernel reads `buf` on the current stream: the allocator must not hand its block out before it has run)
+            buf.record_stream(torch.cuda.current_stream(device))
+            flagged = bool(res.status.cpu().any())      # the one read-back of a batch: a descriptor the kernel's own checks refuse
+        if flagged:
+            DeferredClsBatch.fallbacks += 1
+            return self.materialize_host(device)
+        return res.images
+
+
+@register_collate_func
+def cls_collate_fn(batch):
+    """The collate function of the classification loaders (`evaluation.build_data_loader` gives it to a `config.ImageFolder` that names
+    none): planned samples -- (`DeferredClsSample`, label) -- become (`DeferredClsBatch`, LongTensor of labels); anything else goes
+    through `torch.utils.data.default_collate`, unchanged."""
+    from torch.utils.data import default_collate
+    planned = [isinstance(item, (tuple, list)) and len(item) == 2 and isinstance(item[0], DeferredClsSample) for item in batch]
+    if not any(planned):
+        return default_collate(batch)
+    if not all(planned):
+        raise TypeError('a batch mixes planned and transformed samples')
+    return DeferredClsBatch([item[0] for item in batch]), default_collate([item[1] for item in batch])
 
 
 class DeferredDetSample(object):
