@@ -8,8 +8,9 @@
 // Only the output window is computed; neither the resized image nor the intermediate of Pillow's two passes exists in memory.
 // include/sc2_bottleneck.h states the contract; tests/ref_cls_input.py restates it.
 // Plain kernel: every index checked against the stored box before use, no atomics, no workgroup waits for another.
-#include "sc2_common.h"
-#include "pil_resample.h"      // pil_coeffs, pil_pixel: shared with seg_augment.hip
+// Shared through input_common.h with seg_augment.hip: pil_coeffs, the two passes of a pixel (pil_hpass, pil_vpass) and the tile; with
+// det_input.hip as well: the pixel load and the entry's checks (InputNorm).  Its own: the identity entry of an axis of equal lengths.
+#include "input_common.h"
 
 #pragma clang fp contract(off)
 
@@ -17,9 +18,6 @@ namespace {
 
 constexpr int CI_DESC = SC2_CLS_INPUT_DESC_INTS;         // int32 words of a descriptor row
 constexpr int CI_ENTRY = 2 + PIL_TAPS;                   // int32 words of a table entry: first, count, 9 coefficients
-constexpr int CI_TH = 16, CI_TW = 64;                    // output rows and columns of a tile
-constexpr int CI_THREADS = 256;
-constexpr int CI_ROWS = 4 * CI_TH + PIL_TAPS;            // source rows a band can need: (TH - 1) * 4 + 2 * 4 + 1 and some
 constexpr int CI_MAX_SIDE = SC2_SEG_AUGMENT_MAX_SIDE;
 
 struct Desc {
@@ -69,14 +67,14 @@ struct Args {
     float *images;
     int32_t *status;
     long long nbytes;
-    float mean[3], std[3];
+    InputNorm norm;
     int OH, OW;
 };
 
-__global__ __launch_bounds__(CI_THREADS) void cls_input_kernel(const Args a) {
-    __shared__ uint32_t hbuf[CI_ROWS * CI_TW];            // [source row][tile column]: the horizontal pass's 8-bit output, R | G << 8 | B << 16
-    __shared__ int32_t ctab[CI_TW * CI_ENTRY];            // the tile's column entries, in full-image coordinates
-    __shared__ int32_t rtab[CI_TH * CI_ENTRY];            // ... and its row entries
+__global__ __launch_bounds__(PIL_THREADS) void cls_input_kernel(const Args a) {
+    __shared__ uint32_t hbuf[PIL_ROWS * PIL_TW];          // [source row][tile column]: the horizontal pass's 8-bit output, R | G << 8 | B << 16
+    __shared__ int32_t ctab[PIL_TW * CI_ENTRY];           // the tile's column entries, in full-image coordinates
+    __shared__ int32_t rtab[PIL_TH * CI_ENTRY];           // ... and its row entries
     __shared__ int32_t span[4];                           // the WINDOW's first and last source column and row (last: one past)
     const int i = blockIdx.z;
     const Desc s = ci_desc(a.desc, i);
@@ -86,10 +84,10 @@ __global__ __launch_bounds__(CI_THREADS) void cls_input_kernel(const Args a) {
         if (reports) a.status[i] = fields;
         return;
     }
-    const int y0 = blockIdx.y * CI_TH, x0 = blockIdx.x * CI_TW;
-    const int yv = min(y0 + CI_TH, a.OH), xv = min(x0 + CI_TW, a.OW);      // the tile's rows [y0, yv) and columns [x0, xv)
+    const int y0 = blockIdx.y * PIL_TH, x0 = blockIdx.x * PIL_TW;
+    const int yv = min(y0 + PIL_TH, a.OH), xv = min(x0 + PIL_TW, a.OW);      // the tile's rows [y0, yv) and columns [x0, xv)
     const int tid = threadIdx.x;
-    if (tid < CI_TW) {
+    if (tid < PIL_TW) {
         int32_t e[CI_ENTRY];
         if (x0 + tid < xv) {
             const int c = s.left + x0 + tid;              // position in the flipped, resized image
@@ -100,8 +98,8 @@ __global__ __launch_bounds__(CI_THREADS) void cls_input_kernel(const Args a) {
         }
 #pragma unroll
         for (int k = 0; k < CI_ENTRY; ++k) ctab[tid * CI_ENTRY + k] = e[k];
-    } else if (tid < CI_TW + CI_TH) {
-        const int r = tid - CI_TW;
+    } else if (tid < PIL_TW + PIL_TH) {
+        const int r = tid - PIL_TW;
         int32_t e[CI_ENTRY];
         if (y0 + r < yv) {
             ci_entry(s.fh, s.nh, s.top + y0 + r, e);
@@ -111,10 +109,10 @@ __global__ __launch_bounds__(CI_THREADS) void cls_input_kernel(const Args a) {
         }
 #pragma unroll
         for (int k = 0; k < CI_ENTRY; ++k) rtab[r * CI_ENTRY + k] = e[k];
-    } else if (tid < CI_TW + CI_TH + 4) {
+    } else if (tid < PIL_TW + PIL_TH + 4) {
         // The bounds do not decrease with the resized index, so the window's taps lie between `first` of its lowest index and
         // `first + count` of its highest: every workgroup of the sample reaches the same verdict from these four entries.
-        const int q = tid - CI_TW - CI_TH;                // 0: first column, 1: past the last column, 2: first row, 3: past the last row
+        const int q = tid - PIL_TW - PIL_TH;              // 0: first column, 1: past the last column, 2: first row, 3: past the last row
         const int lo = q < 2 ? (s.flip ? s.nw - s.left - a.OW : s.left) : s.top;
         const int hi = lo + (q < 2 ? a.OW : a.OH) - 1;
         int32_t e[CI_ENTRY];
@@ -125,12 +123,12 @@ __global__ __launch_bounds__(CI_THREADS) void cls_input_kernel(const Args a) {
     const bool taps = span[0] >= s.col0 && span[1] <= s.col0 + s.w && span[2] >= s.row0 && span[3] <= s.row0 + s.h;
     if (reports) a.status[i] = taps ? 0 : SC2_CLS_INPUT_TAP;
     if (!taps) return;                                    // (uniform)
-    const int lx = tid & (CI_TW - 1), ly = tid / CI_TW;   // a wave owns a row, its lanes the columns
+    const int lx = tid & (PIL_TW - 1), ly = tid / PIL_TW; // a wave owns a row, its lanes the columns
     const int x = x0 + lx;
     // the band's source rows run from its first row's bounds to its last row's (full-image coordinates)
     const int r_first = rtab[0];
     const int32_t *el = rtab + (yv - 1 - y0) * CI_ENTRY;
-    const int r_count = min(el[0] + el[1] - r_first, CI_ROWS);
+    const int r_count = min(el[0] + el[1] - r_first, PIL_ROWS);
     if (x < xv) {
         const int32_t *e = ctab + lx * CI_ENTRY;
         const int first = e[0] - s.col0, count = e[1];    // stored-box coordinates from here on
@@ -139,46 +137,23 @@ __global__ __launch_bounds__(CI_THREADS) void cls_input_kernel(const Args a) {
         for (int t = 0; t < PIL_TAPS; ++t) k[t] = e[2 + t];
         const uint8_t *img = a.buf + s.off;
         const size_t img_bytes = (size_t)s.h * s.w * 3;
-        for (int r = ly; r < r_count; r += CI_THREADS / CI_TW) {
+        for (int r = ly; r < r_count; r += PIL_THREADS / PIL_TW) {
             const int sr = min(max(r_first + r - s.row0, 0), s.h - 1);
-            int acc0 = 1 << (PIL_BITS - 1), acc1 = acc0, acc2 = acc0;
-#pragma unroll
-            for (int t = 0; t < PIL_TAPS; ++t) {
-                if (t < count) {
-                    const uint32_t p = pil_pixel(img, ((size_t)sr * s.w + min(max(first + t, 0), s.w - 1)) * 3, img_bytes);
-                    acc0 += (int)(p & 0xFFu) * k[t];
-                    acc1 += (int)((p >> 8) & 0xFFu) * k[t];
-                    acc2 += (int)((p >> 16) & 0xFFu) * k[t];
-                }
-            }
-            hbuf[r * CI_TW + lx] = (uint32_t)min(max(acc0 >> PIL_BITS, 0), 255) | (uint32_t)min(max(acc1 >> PIL_BITS, 0), 255) << 8 |
-                                   (uint32_t)min(max(acc2 >> PIL_BITS, 0), 255) << 16;
+            hbuf[r * PIL_TW + lx] = pil_hpass(img, img_bytes, s.w, sr, first, count, k);
         }
     }
     __syncthreads();
     if (x >= xv) return;
     const size_t plane = (size_t)a.OH * a.OW;
     float *out = a.images + (size_t)i * 3 * plane;
-    for (int y = y0 + ly; y < yv; y += CI_THREADS / CI_TW) {
+    for (int y = y0 + ly; y < yv; y += PIL_THREADS / PIL_TW) {
         const int32_t *e = rtab + (y - y0) * CI_ENTRY;
-        const int first = e[0] - r_first, count = e[1];
-        int acc0 = 1 << (PIL_BITS - 1), acc1 = acc0, acc2 = acc0;
-#pragma unroll
-        for (int t = 0; t < PIL_TAPS; ++t) {
-            if (t < count) {
-                const int kt = e[2 + t];
-                const uint32_t p = hbuf[min(max(first + t, 0), CI_ROWS - 1) * CI_TW + lx];
-                acc0 += (int)(p & 0xFFu) * kt;
-                acc1 += (int)((p >> 8) & 0xFFu) * kt;
-                acc2 += (int)((p >> 16) & 0xFFu) * kt;
-            }
-        }
-        const float p0 = (float)min(max(acc0 >> PIL_BITS, 0), 255), p1 = (float)min(max(acc1 >> PIL_BITS, 0), 255),
-                    p2 = (float)min(max(acc2 >> PIL_BITS, 0), 255);
+        float v0, v1, v2;
+        pil_vpass<PIL_ROWS, PIL_TW>(hbuf, lx, e, e[0] - r_first, a.norm.mean, a.norm.std, v0, v1, v2);
         const size_t o = (size_t)y * a.OW + x;
-        out[o] = __fdiv_rn(__fdiv_rn(p0, 255.0f) - a.mean[0], a.std[0]);
-        out[plane + o] = __fdiv_rn(__fdiv_rn(p1, 255.0f) - a.mean[1], a.std[1]);
-        out[2 * plane + o] = __fdiv_rn(__fdiv_rn(p2, 255.0f) - a.mean[2], a.std[2]);
+        out[o] = v0;
+        out[plane + o] = v1;
+        out[2 * plane + o] = v2;
     }
 }
 
@@ -196,21 +171,14 @@ extern "C" int sc2_cls_input(const uint8_t *buf, long long nbytes, const int32_t
                              const float *std, float *images, int32_t *status, void *stream) {
     SC2_REQUIRE(ci_sizes_ok(n, oh, ow), SC2_ERR_UNSUPPORTED, "cls_input: %d samples of %dx%d (1..%d samples, sides 1..%d)", n, oh, ow,
                 SC2_CLS_INPUT_MAX_BATCH, CI_MAX_SIDE);
-    SC2_REQUIRE(nbytes >= 1 && nbytes <= 0x7FFFFFFFLL, SC2_ERR_UNSUPPORTED, "cls_input: a source buffer of %lld bytes (1..2^31-1)", nbytes);
-    SC2_REQUIRE(buf && desc && mean && std && images && status, SC2_ERR_INVALID_ARG, "cls_input: null pointer");
-    SC2_REQUIRE(((reinterpret_cast<uintptr_t>(desc) | reinterpret_cast<uintptr_t>(images) | reinterpret_cast<uintptr_t>(status)) & 3u) == 0,
-                SC2_ERR_INVALID_ARG, "cls_input: misaligned pointer");
-    for (int c = 0; c < 3; ++c)
-        SC2_REQUIRE(std[c] != 0.0f, SC2_ERR_INVALID_ARG, "cls_input: std[%d] is zero", c);
+    const uintptr_t words = reinterpret_cast<uintptr_t>(desc) | reinterpret_cast<uintptr_t>(images) | reinterpret_cast<uintptr_t>(status);
     Args a;
+    const int rc = a.norm.take("cls_input", nbytes, buf && desc && mean && std && images && status, (words & 3u) == 0, mean, std);
+    if (rc != SC2_OK) return rc;
     a.buf = buf; a.desc = desc; a.images = images; a.status = status; a.nbytes = nbytes;
-    for (int c = 0; c < 3; ++c) {
-        a.mean[c] = mean[c];
-        a.std[c] = std[c];
-    }
     a.OH = oh; a.OW = ow;
-    const dim3 grid((unsigned)((ow + CI_TW - 1) / CI_TW), (unsigned)((oh + CI_TH - 1) / CI_TH), (unsigned)n);
-    hipLaunchKernelGGL(cls_input_kernel, grid, dim3(CI_THREADS), 0, static_cast<hipStream_t>(stream), a);
+    const dim3 grid((unsigned)((ow + PIL_TW - 1) / PIL_TW), (unsigned)((oh + PIL_TH - 1) / PIL_TH), (unsigned)n);
+    hipLaunchKernelGGL(cls_input_kernel, grid, dim3(PIL_THREADS), 0, static_cast<hipStream_t>(stream), a);
     SC2_CHECK_LAUNCH();
     return SC2_OK;
 }

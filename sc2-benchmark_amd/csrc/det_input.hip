@@ -6,7 +6,9 @@
 // interleaved, so one set of indices and weights serves three planes.  The 3 x 256 table of normalised byte values is built once per
 // workgroup in LDS.  include/sc2_bottleneck.h states the contract; tests/ref_det_input.py restates the arithmetic.
 // Plain kernel: every index checked against its array before use, no atomics, no workgroup waits for another.
-#include "sc2_common.h"
+// Shared through input_common.h with rcnn_input.hip: aten's bilinear axis (aten_axis); with seg_augment.hip and cls_input.hip: the
+// pixel load (pil_pixel, here over int offsets) and the entry's checks (InputNorm).
+#include "input_common.h"
 
 #pragma clang fp contract(off)   // every product, sum and quotient rounded once, as the host's operator-by-operator arithmetic
 
@@ -31,7 +33,7 @@ struct DetArgs {
     const uint8_t *buf;
     float *out;
     long long nbytes;
-    float mean[3], std[3];
+    InputNorm norm;
     int n, Hp, Wp;
     DetRow row[SC2_DET_INPUT_MAX_BATCH];
 };
@@ -45,31 +47,11 @@ __host__ __device__ inline int di_row_status(const DetRow &s, long long nbytes, 
     return 0;
 }
 
-// aten's upsample_bilinear2d index and weight of output index d (align_corners=False, no given scale factor), in f32: `ri_axis` of
-// rcnn_input.hip
-__device__ __forceinline__ void di_axis(int d, float scale, int in, int &i0, int &i1, float &l1) {
-    const float src = fmaxf(scale * ((float)d + 0.5f) - 0.5f, 0.0f);
-    i0 = min((int)src, in - 1);
-    i1 = min(i0 + 1, in - 1);
-    l1 = src - (float)i0;
-}
-
-// The three bytes of the pixel at byte offset `off` of an image of `bytes` bytes, R in the low byte: one unaligned four-byte load where
-// the byte behind the pixel is still the image's (every pixel but the last), three byte loads otherwise.
-__device__ __forceinline__ uint32_t di_pixel(const uint8_t *img, int off, int bytes) {
-    if (off + 4 <= bytes) {
-        uint32_t v;
-        __builtin_memcpy(&v, img + off, 4);
-        return v;
-    }
-    return (uint32_t)img[off] | (uint32_t)img[off + 1] << 8 | (uint32_t)img[off + 2] << 16;
-}
-
 __global__ __launch_bounds__(DI_LANES * DI_WAVES) void det_input_kernel(const DetArgs a) {
     __shared__ float nrm[3 * 256];      // [channel][byte]: ((b / 255) - mean) / std
     const int tid = threadIdx.y * DI_LANES + threadIdx.x;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) nrm[c * 256 + tid] = __fdiv_rn(__fdiv_rn((float)tid, 255.0f) - a.mean[c], a.std[c]);
+    for (int c = 0; c < 3; ++c) nrm[c * 256 + tid] = __fdiv_rn(__fdiv_rn((float)tid, 255.0f) - a.norm.mean[c], a.norm.std[c]);
     __syncthreads();
     const int i = blockIdx.z;
     const int x0 = blockIdx.x * DI_TW + threadIdx.x * DI_PX;
@@ -89,7 +71,7 @@ __global__ __launch_bounds__(DI_LANES * DI_WAVES) void det_input_kernel(const De
 #pragma unroll
         for (int j = 0; j < DI_PX; ++j) {
             int i0, i1;
-            di_axis(min(x0 + j, ow - 1), scale_x, w, i0, i1, lx[j]);      // (a column beyond the image repeats the last one: not stored)
+            aten_axis(min(x0 + j, ow - 1), scale_x, w, i0, i1, lx[j]);      // (a column beyond the image repeats the last one: not stored)
             xa[j] = 3 * (s.flip ? w - 1 - i0 : i0);
             xb[j] = 3 * (s.flip ? w - 1 - i1 : i1);
         }
@@ -115,14 +97,14 @@ __global__ __launch_bounds__(DI_LANES * DI_WAVES) void det_input_kernel(const De
         if (live && y < oh) {
             int j0, j1;
             float ly1;
-            di_axis(y, scale_y, h, j0, j1, ly1);
+            aten_axis(y, scale_y, h, j0, j1, ly1);
             const float ly0 = 1.0f - ly1;
             const int r0 = j0 * w * 3, r1 = j1 * w * 3;
 #pragma unroll
             for (int j = 0; j < DI_PX; ++j) {
                 if (x0 + j < ow) {
-                    const uint32_t p = di_pixel(img, r0 + xa[j], img_bytes), q = di_pixel(img, r0 + xb[j], img_bytes),
-                                   u = di_pixel(img, r1 + xa[j], img_bytes), t = di_pixel(img, r1 + xb[j], img_bytes);
+                    const uint32_t p = pil_pixel(img, r0 + xa[j], img_bytes), q = pil_pixel(img, r0 + xb[j], img_bytes),
+                                   u = pil_pixel(img, r1 + xa[j], img_bytes), t = pil_pixel(img, r1 + xb[j], img_bytes);
                     const float lx1 = lx[j], lx0 = 1.0f - lx1;
 #pragma unroll
                     for (int c = 0; c < 3; ++c) {
@@ -158,12 +140,10 @@ extern "C" int sc2_det_input(const uint8_t *buf, long long nbytes, const int32_t
                 SC2_DET_INPUT_MAX_BATCH);
     SC2_REQUIRE(Hp >= 1 && Wp >= 1 && Hp <= DI_MAX_PAD_SIDE && Wp <= DI_MAX_PAD_SIDE, SC2_ERR_UNSUPPORTED,
                 "det_input: a %dx%d batch (sides 1..%d)", Hp, Wp, DI_MAX_PAD_SIDE);
-    SC2_REQUIRE(nbytes >= 1 && nbytes <= 0x7FFFFFFFLL, SC2_ERR_UNSUPPORTED, "det_input: a source buffer of %lld bytes (1..2^31-1)", nbytes);
-    SC2_REQUIRE(buf && rows && mean && std && out, SC2_ERR_INVALID_ARG, "det_input: null pointer");
-    SC2_REQUIRE((reinterpret_cast<uintptr_t>(out) & 3u) == 0, SC2_ERR_INVALID_ARG, "det_input: misaligned pointer");
-    for (int c = 0; c < 3; ++c)
-        SC2_REQUIRE(std[c] != 0.0f, SC2_ERR_INVALID_ARG, "det_input: std[%d] is zero", c);
     DetArgs a;
+    const int rc = a.norm.take("det_input", nbytes, buf && rows && mean && std && out, (reinterpret_cast<uintptr_t>(out) & 3u) == 0, mean,
+                               std);
+    if (rc != SC2_OK) return rc;
     for (int i = 0; i < SC2_DET_INPUT_MAX_BATCH; ++i) {
         DetRow &s = a.row[i];
         if (i < n) {
@@ -177,10 +157,6 @@ extern "C" int sc2_det_input(const uint8_t *buf, long long nbytes, const int32_t
         }
     }
     a.buf = buf; a.out = out; a.nbytes = nbytes;
-    for (int c = 0; c < 3; ++c) {
-        a.mean[c] = mean[c];
-        a.std[c] = std[c];
-    }
     a.n = n; a.Hp = Hp; a.Wp = Wp;
     const dim3 grid((unsigned)((Wp + DI_TW - 1) / DI_TW), (unsigned)((Hp + DI_TH - 1) / DI_TH), (unsigned)n);
     hipLaunchKernelGGL(det_input_kernel, grid, dim3(DI_LANES, DI_WAVES), 0, static_cast<hipStream_t>(stream), a);

@@ -5,7 +5,8 @@
 //   sc2_rcnn_normalize_pad u8 [C,h,w] (the codec's recon) -> one f32 slot [C,Hp,Wp] of the batch tensor, every element written
 // include/sc2_bottleneck.h states the contract; tests/ref_rcnn_input.py restates it.
 // Plain kernels: every index checked against its array before use, no LDS, no atomics, no workgroup waits for another.
-#include "sc2_common.h"
+// Shared through input_common.h with det_input.hip: aten's bilinear axis (aten_axis).
+#include "input_common.h"
 
 #pragma clang fp contract(off)   // every product, sum and quotient rounded once, as the host's operator-by-operator arithmetic
 
@@ -26,14 +27,6 @@ struct ResizeArgs {
     int C, H, W, oh, ow;
 };
 
-// aten's upsample_bilinear2d index and weight of output index d (align_corners=False, no given scale factor), in f32
-__device__ __forceinline__ void ri_axis(int d, float scale, int in, int &i0, int &i1, float &l1) {
-    const float src = fmaxf(scale * ((float)d + 0.5f) - 0.5f, 0.0f);
-    i0 = min((int)src, in - 1);
-    i1 = min(i0 + 1, in - 1);
-    l1 = src - (float)i0;
-}
-
 __device__ __forceinline__ bool ri_in_unit(float v) { return v >= 0.0f && v <= 1.0f; }      // false for NaN
 
 __global__ __launch_bounds__(RI_LANES * RI_WAVES) void rcnn_resize_u8_kernel(const ResizeArgs a) {
@@ -46,7 +39,7 @@ __global__ __launch_bounds__(RI_LANES * RI_WAVES) void rcnn_resize_u8_kernel(con
 #pragma unroll
     for (int j = 0; j < RI_PX; ++j) {
         int i0, i1;
-        ri_axis(min(x0 + j, a.ow - 1), scale_x, a.W, i0, i1, lx[j]);      // (a column beyond the row repeats the last one: not stored)
+        aten_axis(min(x0 + j, a.ow - 1), scale_x, a.W, i0, i1, lx[j]);      // (a column beyond the row repeats the last one: not stored)
         xa[j] = i0 * a.sw;
         xb[j] = i1 * a.sw;
     }
@@ -58,7 +51,7 @@ __global__ __launch_bounds__(RI_LANES * RI_WAVES) void rcnn_resize_u8_kernel(con
         if (y >= a.oh) break;
         int j0, j1;
         float ly1;
-        ri_axis(y, scale_y, a.H, j0, j1, ly1);
+        aten_axis(y, scale_y, a.H, j0, j1, ly1);
         const float ly0 = 1.0f - ly1;
         const float *row0 = plane + j0 * a.sh, *row1 = plane + j1 * a.sh;
         uint32_t packed = 0;

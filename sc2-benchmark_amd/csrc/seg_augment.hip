@@ -7,8 +7,10 @@
 // Only the output window is computed; neither the resized image nor the intermediate of Pillow's two passes exists in memory.
 // include/sc2_bottleneck.h states the contract; tests/ref_pil_resize.py restates the two resizes.
 // Plain kernels: every index checked against its array before use, no atomics, no workgroup waits for another.
-#include "sc2_common.h"
-#include "pil_resample.h"      // pil_coeffs, pil_pixel: shared with cls_input.hip
+// Shared through input_common.h with cls_input.hip: pil_coeffs, the two passes of a pixel (pil_hpass, pil_vpass) and the tile; with
+// det_input.hip as well: the pixel load and the entry's checks (InputNorm).  Their own: every axis goes through pil_coeffs, and an
+// entry's last word is the nearest resize's index.
+#include "input_common.h"
 
 #pragma clang fp contract(off)   // int() truncates and the sums are ordered: a fused multiply-add in `center` moves xmin for some sizes
 
@@ -16,11 +18,6 @@ namespace {
 
 constexpr int SA_DESC = SC2_SEG_AUGMENT_DESC_INTS;       // int32 words of a descriptor row
 constexpr int SA_ENTRY = SC2_SEG_AUGMENT_ENTRY_INTS;     // int32 words of a table entry: first, count, 9 coefficients, nearest index
-constexpr int SA_TAPS = PIL_TAPS;                        // ksize at filterscale 4
-constexpr int SA_BITS = PIL_BITS;                        // Pillow's PRECISION_BITS for 8-bit channels
-constexpr int SA_TH = 16, SA_TW = 64;                    // output rows and columns of a tile
-constexpr int SA_THREADS = 256;
-constexpr int SA_ROWS = 4 * SA_TH + SA_TAPS;             // source rows a band can need: (TH - 1) * 4 + 2 * 4 + 1 and some
 constexpr int SA_MAX_SIDE = SC2_SEG_AUGMENT_MAX_SIDE;
 
 struct Desc {
@@ -63,7 +60,7 @@ struct TableArgs {
     int OH, OW, blocks;      // blocks: workgroups along x that compute coefficients; one more walks the nearest sums
 };
 
-__global__ __launch_bounds__(SA_THREADS) void seg_augment_tables_kernel(const TableArgs a) {
+__global__ __launch_bounds__(PIL_THREADS) void seg_augment_tables_kernel(const TableArgs a) {
     const int i = blockIdx.z, axis = blockIdx.y;      // axis 0: columns, 1: rows
     const Desc s = sa_desc(a.desc, i);
     const int st = sa_status(s, a.nbytes, a.OH, a.OW);
@@ -75,7 +72,7 @@ __global__ __launch_bounds__(SA_THREADS) void seg_augment_tables_kernel(const Ta
     const int origin = axis == 0 ? s.left : s.top, ext = axis == 0 ? s.ew : s.eh;
     const bool flip = axis == 0 && s.flip != 0;
     if ((int)blockIdx.x < a.blocks) {
-        const int o = blockIdx.x * SA_THREADS + threadIdx.x;
+        const int o = blockIdx.x * PIL_THREADS + threadIdx.x;
         if (o >= len) return;
         const int r = origin + o;                    // position in the padded, flipped, resized image
         int32_t e[SA_ENTRY];
@@ -116,50 +113,39 @@ struct TileArgs {
     float *images;
     long long *targets;
     long long nbytes;
-    float mean[3], std[3];
+    InputNorm norm;
     int OH, OW;
 };
 
-__global__ __launch_bounds__(SA_THREADS) void seg_augment_tile_kernel(const TileArgs a) {
-    __shared__ uint32_t hbuf[SA_ROWS * SA_TW];      // [source row][tile column]: the horizontal pass's 8-bit output, R | G << 8 | B << 16
+__global__ __launch_bounds__(PIL_THREADS) void seg_augment_tile_kernel(const TileArgs a) {
+    __shared__ uint32_t hbuf[PIL_ROWS * PIL_TW];      // [source row][tile column]: the horizontal pass's 8-bit output, R | G << 8 | B << 16
     const int i = blockIdx.z;
     const Desc s = sa_desc(a.desc, i);
     if (sa_status(s, a.nbytes, a.OH, a.OW) != 0) return;      // (wave-uniform: the whole workgroup leaves)
-    const int y0 = blockIdx.y * SA_TH, x0 = blockIdx.x * SA_TW;
+    const int y0 = blockIdx.y * PIL_TH, x0 = blockIdx.x * PIL_TW;
     const int32_t *cols = static_cast<const int32_t *>(a.ws) + (size_t)i * (a.OH + a.OW) * SA_ENTRY;
     const int32_t *rows = cols + (size_t)a.OW * SA_ENTRY;
     // the part of the tile that shows resized pixels: rows [y0, yv), columns [x0, xv)
-    const int yv = min(min(y0 + SA_TH, s.eh), s.nh - s.top), xv = min(min(x0 + SA_TW, s.ew), s.nw - s.left);
-    const int lx = threadIdx.x & (SA_TW - 1), ly = threadIdx.x / SA_TW;      // a wave owns a row, its lanes the columns
+    const int yv = min(min(y0 + PIL_TH, s.eh), s.nh - s.top), xv = min(min(x0 + PIL_TW, s.ew), s.nw - s.left);
+    const int lx = threadIdx.x & (PIL_TW - 1), ly = threadIdx.x / PIL_TW;      // a wave owns a row, its lanes the columns
     const int x = x0 + lx;
     int r_first = 0, r_count = 0;
     if (yv > y0 && xv > x0) {
         // the bounds do not decrease with the output index, so the band's source rows run from its first row's to its last row's
         const int32_t *ef = rows + (size_t)y0 * SA_ENTRY, *el = rows + (size_t)(yv - 1) * SA_ENTRY;
         r_first = ef[0];
-        r_count = min(el[0] + el[1] - r_first, SA_ROWS);
+        r_count = min(el[0] + el[1] - r_first, PIL_ROWS);
         if (x < xv) {
             const int32_t *e = cols + (size_t)x * SA_ENTRY;
             const int first = e[0], count = e[1];
-            int k[SA_TAPS];
+            int k[PIL_TAPS];
 #pragma unroll
-            for (int t = 0; t < SA_TAPS; ++t) k[t] = e[2 + t];
+            for (int t = 0; t < PIL_TAPS; ++t) k[t] = e[2 + t];
             const uint8_t *img = a.buf + s.img;
             const size_t img_bytes = (size_t)s.h * s.w * 3;
-            for (int r = ly; r < r_count; r += SA_THREADS / SA_TW) {
+            for (int r = ly; r < r_count; r += PIL_THREADS / PIL_TW) {
                 const int sr = min(max(r_first + r, 0), s.h - 1);
-                int acc0 = 1 << (SA_BITS - 1), acc1 = acc0, acc2 = acc0;
-#pragma unroll
-                for (int t = 0; t < SA_TAPS; ++t) {
-                    if (t < count) {
-                        const uint32_t p = pil_pixel(img, ((size_t)sr * s.w + min(max(first + t, 0), s.w - 1)) * 3, img_bytes);
-                        acc0 += (int)(p & 0xFFu) * k[t];
-                        acc1 += (int)((p >> 8) & 0xFFu) * k[t];
-                        acc2 += (int)((p >> 16) & 0xFFu) * k[t];
-                    }
-                }
-                hbuf[r * SA_TW + lx] = (uint32_t)min(max(acc0 >> SA_BITS, 0), 255) | (uint32_t)min(max(acc1 >> SA_BITS, 0), 255) << 8 |
-                                       (uint32_t)min(max(acc2 >> SA_BITS, 0), 255) << 16;
+                hbuf[r * PIL_TW + lx] = pil_hpass(img, img_bytes, s.w, sr, first, count, k);
             }
         }
     }
@@ -170,34 +156,18 @@ __global__ __launch_bounds__(SA_THREADS) void seg_augment_tile_kernel(const Tile
     long long *tgt = a.targets + (size_t)i * plane;
     const uint8_t *mask = a.buf + s.mask;
     const int mcol = x < xv ? min(max(cols[(size_t)x * SA_ENTRY + SA_ENTRY - 1], 0), s.w - 1) : 0;
-    for (int y = y0 + ly; y < min(y0 + SA_TH, a.OH); y += SA_THREADS / SA_TW) {
+    for (int y = y0 + ly; y < min(y0 + PIL_TH, a.OH); y += PIL_THREADS / PIL_TW) {
         float v0, v1, v2;
         long long label = 255;
         if (y >= s.eh || x >= s.ew) {                 // outside the sample's extent: the collator's fill
             v0 = v1 = v2 = 0.0f;
         } else if (y >= yv || x >= xv) {              // pad_if_smaller's area: a zero pixel, normalised
-            v0 = __fdiv_rn(0.0f - a.mean[0], a.std[0]);
-            v1 = __fdiv_rn(0.0f - a.mean[1], a.std[1]);
-            v2 = __fdiv_rn(0.0f - a.mean[2], a.std[2]);
+            v0 = __fdiv_rn(0.0f - a.norm.mean[0], a.norm.std[0]);
+            v1 = __fdiv_rn(0.0f - a.norm.mean[1], a.norm.std[1]);
+            v2 = __fdiv_rn(0.0f - a.norm.mean[2], a.norm.std[2]);
         } else {
             const int32_t *e = rows + (size_t)y * SA_ENTRY;
-            const int first = e[0] - r_first, count = e[1];
-            int acc0 = 1 << (SA_BITS - 1), acc1 = acc0, acc2 = acc0;
-#pragma unroll
-            for (int t = 0; t < SA_TAPS; ++t) {
-                if (t < count) {
-                    const int kt = e[2 + t];
-                    const uint32_t p = hbuf[min(max(first + t, 0), SA_ROWS - 1) * SA_TW + lx];
-                    acc0 += (int)(p & 0xFFu) * kt;
-                    acc1 += (int)((p >> 8) & 0xFFu) * kt;
-                    acc2 += (int)((p >> 16) & 0xFFu) * kt;
-                }
-            }
-            const float p0 = (float)min(max(acc0 >> SA_BITS, 0), 255), p1 = (float)min(max(acc1 >> SA_BITS, 0), 255),
-                        p2 = (float)min(max(acc2 >> SA_BITS, 0), 255);
-            v0 = __fdiv_rn(__fdiv_rn(p0, 255.0f) - a.mean[0], a.std[0]);
-            v1 = __fdiv_rn(__fdiv_rn(p1, 255.0f) - a.mean[1], a.std[1]);
-            v2 = __fdiv_rn(__fdiv_rn(p2, 255.0f) - a.mean[2], a.std[2]);
+            pil_vpass<PIL_ROWS, PIL_TW>(hbuf, lx, e, e[0] - r_first, a.norm.mean, a.norm.std, v0, v1, v2);
             const int mrow = min(max(e[SA_ENTRY - 1], 0), s.h - 1);
             label = (long long)mask[(size_t)mrow * s.w + mcol];
         }
@@ -224,28 +194,22 @@ extern "C" int sc2_seg_augment(const uint8_t *buf, long long nbytes, const int32
                                const float *std, float *images, long long *targets, void *ws, int32_t *status, void *stream) {
     SC2_REQUIRE(sa_sizes_ok(n, oh, ow), SC2_ERR_UNSUPPORTED, "seg_augment: %d samples of %dx%d (1..%d samples, sides 1..%d)", n, oh, ow,
                 SC2_SEG_AUGMENT_MAX_BATCH, SA_MAX_SIDE);
-    SC2_REQUIRE(nbytes >= 1 && nbytes <= 0x7FFFFFFFLL, SC2_ERR_UNSUPPORTED, "seg_augment: a source buffer of %lld bytes (1..2^31-1)", nbytes);
-    SC2_REQUIRE(buf && desc && mean && std && images && targets && ws && status, SC2_ERR_INVALID_ARG, "seg_augment: null pointer");
-    SC2_REQUIRE(((reinterpret_cast<uintptr_t>(desc) | reinterpret_cast<uintptr_t>(images) | reinterpret_cast<uintptr_t>(ws) |
-                  reinterpret_cast<uintptr_t>(status)) & 3u) == 0 && (reinterpret_cast<uintptr_t>(targets) & 7u) == 0,
-                SC2_ERR_INVALID_ARG, "seg_augment: misaligned pointer");
-    for (int c = 0; c < 3; ++c)
-        SC2_REQUIRE(std[c] != 0.0f, SC2_ERR_INVALID_ARG, "seg_augment: std[%d] is zero", c);
+    const uintptr_t words = reinterpret_cast<uintptr_t>(desc) | reinterpret_cast<uintptr_t>(images) | reinterpret_cast<uintptr_t>(ws) |
+                            reinterpret_cast<uintptr_t>(status);
+    TileArgs a;
+    const int rc = a.norm.take("seg_augment", nbytes, buf && desc && mean && std && images && targets && ws && status,
+                               (words & 3u) == 0 && (reinterpret_cast<uintptr_t>(targets) & 7u) == 0, mean, std);
+    if (rc != SC2_OK) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     TableArgs t;
     t.desc = desc; t.ws = ws; t.status = status; t.nbytes = nbytes; t.OH = oh; t.OW = ow;
-    t.blocks = ((oh > ow ? oh : ow) + SA_THREADS - 1) / SA_THREADS;
-    hipLaunchKernelGGL(seg_augment_tables_kernel, dim3((unsigned)t.blocks + 1, 2, (unsigned)n), dim3(SA_THREADS), 0, s, t);
+    t.blocks = ((oh > ow ? oh : ow) + PIL_THREADS - 1) / PIL_THREADS;
+    hipLaunchKernelGGL(seg_augment_tables_kernel, dim3((unsigned)t.blocks + 1, 2, (unsigned)n), dim3(PIL_THREADS), 0, s, t);
     SC2_CHECK_LAUNCH();
-    TileArgs a;
     a.buf = buf; a.desc = desc; a.ws = ws; a.images = images; a.targets = targets; a.nbytes = nbytes;
-    for (int c = 0; c < 3; ++c) {
-        a.mean[c] = mean[c];
-        a.std[c] = std[c];
-    }
     a.OH = oh; a.OW = ow;
-    const dim3 grid((unsigned)((ow + SA_TW - 1) / SA_TW), (unsigned)((oh + SA_TH - 1) / SA_TH), (unsigned)n);
-    hipLaunchKernelGGL(seg_augment_tile_kernel, grid, dim3(SA_THREADS), 0, s, a);
+    const dim3 grid((unsigned)((ow + PIL_TW - 1) / PIL_TW), (unsigned)((oh + PIL_TH - 1) / PIL_TH), (unsigned)n);
+    hipLaunchKernelGGL(seg_augment_tile_kernel, grid, dim3(PIL_THREADS), 0, s, a);
     SC2_CHECK_LAUNCH();
     return SC2_OK;
 }

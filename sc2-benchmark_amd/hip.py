@@ -1630,16 +1630,83 @@ def rcnn_normalize_pad(pixels_u8, mean, std, out_slot, tag=None):
     return out_slot
 
 
+class _InputCall(object):
+    """What det_input, seg_augment and cls_input repeat around their call: the flat uint8 source buffer on the device, mean / std as
+    two `c_float * 3`, and an output tensor (the caller's, checked; or a new one)."""
+    def __init__(self, who, buf):
+        _dev(buf, who + ': buf')
+        if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
+            raise Sc2Error('{}: a flat contiguous uint8 buffer is required, got {} {}'.format(who, buf.dtype, tuple(buf.shape)))
+        self.who, self.buf, self.nbytes, self.dev = who, buf, int(buf.numel()), buf.device
+
+    def norm(self, mean, std, error, non_zero):
+        """-> (mean, std) as `c_float * 3`; `error` is what anything else raises; non_zero: a zero std is refused here, too"""
+        mean, std = [float(v) for v in mean], [float(v) for v in std]
+        if len(mean) != 3 or len(std) != 3 or (non_zero and any(v == 0.0 for v in std)):
+            raise error('{}: three mean and three {}std values are required'.format(self.who, 'non-zero ' if non_zero else ''))
+        return (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
+
+    def out(self, t, name, dtype, shape):
+        """t (None: a new one) as the contiguous tensor of that dtype and shape on the buffer's device; a name in `shape`: any size"""
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=self.dev)
+        _dev(t, '{}: {}'.format(self.who, name))
+        fits = t.dim() == len(shape) and all(isinstance(want, str) or int(have) == want for have, want in zip(t.shape, shape))
+        if t.dtype != dtype or not fits or not t.is_contiguous() or t.device != self.dev:
+            raise Sc2Error('{}: {} must be a contiguous {} [{}] tensor on {}, got {} {}'.format(
+                self.who, name, str(dtype).split('.')[-1], ','.join(str(v) for v in shape), self.dev, t.dtype, tuple(t.shape)))
+        return t
+
+
+class _DescTable(collections.namedtuple('_DescTable', ['who', 'fields', 'defaults', 'width', 'max_batch'])):
+    """The descriptor table of an input kernel as its `*_desc` / `*_check` pair declares it: `who` for the messages, the names of a row's
+    leading words, `defaults` (the fields given -> (name, value) of those that may be left out), a row's int32 words, the most rows."""
+    def row(self, fields):
+        for name, value in self.defaults(fields):
+            fields.setdefault(name, value)
+        row = np.zeros(self.width, dtype=np.int32)
+        row[:len(self.fields)] = [int(fields.pop(name)) for name in self.fields]
+        assert not fields, '{}_desc: unknown fields {}'.format(self.who, sorted(fields))
+        return row
+
+    def rows(self, desc, nbytes, oh, ow):
+        """The front of a check: the table's shape, the output slot and the buffer's size; then a `_DescRow` per row for the rules."""
+        desc = np.asarray(desc)
+        if desc.ndim != 2 or desc.shape[1] != self.width or desc.shape[0] < 1 or desc.shape[0] > self.max_batch:
+            raise ValueError('{}: a descriptor table [1..{}, {}] is required, got {}'.format(self.who, self.max_batch, self.width, desc.shape))
+        if not (1 <= oh <= SEG_AUGMENT_MAX_SIDE and 1 <= ow <= SEG_AUGMENT_MAX_SIDE):
+            raise ValueError('{}: a {} x {} output slot (sides 1..{})'.format(self.who, oh, ow, SEG_AUGMENT_MAX_SIDE))
+        if not 1 <= nbytes <= 0x7FFFFFFF:
+            raise ValueError('{}: a source buffer of {} bytes (1..2^31-1)'.format(self.who, nbytes))
+        return [_DescRow(self.who, i, dict(zip(self.fields, row)), nbytes) for i, row in enumerate(desc.tolist())]
+
+
+class _DescRow(collections.namedtuple('_DescRow', ['who', 'i', 'f', 'nbytes'])):
+    """Row i of a `_DescTable` under check: `f`, its fields by name, and the rules the tables share"""
+    def refuse(self, name, why):
+        raise ValueError('{}: sample {}: {} = {}: {}'.format(self.who, self.i, name, self.f[name], why))
+
+    def sides(self, *names):
+        for name in names:
+            if not 1 <= self.f[name] <= SEG_AUGMENT_MAX_SIDE:
+                self.refuse(name, 'sides are 1..{}'.format(SEG_AUGMENT_MAX_SIDE))
+
+    def inside(self, name, k, what):      # the k * h * w bytes at offset `name`
+        if self.f[name] < 0 or self.f[name] + k * self.f['h'] * self.f['w'] > self.nbytes:
+            self.refuse(name, 'the {} lies outside the buffer of {} bytes'.format(what, self.nbytes))
+
+    def flip(self):
+        if self.f['flip'] not in (0, 1):
+            self.refuse('flip', '0 or 1')
+
+
 def det_input(buf, rows, mean, std, out, tag=None):
     """The detector's input transform of a planned batch (include/sc2_bottleneck.h: sc2_det_input).  buf: flat contiguous uint8 device
     tensor holding the interleaved [h,w,3] sources; rows: integers [n, DET_INPUT_ROW_INTS] on the host -- (byte offset, h, w, oh, ow,
     flip) per sample, checked by the library on the host before anything is launched (a bad row raises Sc2Error and `out` is
     untouched); mean, std: three numbers each; out: a contiguous float32 [n,3,Hp,Wp] device tensor, every element of which is written
     (+0.0 outside a sample's (oh, ow)).  One launch per DET_INPUT_MAX_BATCH samples.  -> out."""
-    _dev(buf, 'det_input: buf')
-    _dev(out, 'det_input: out')
-    if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
-        raise Sc2Error('det_input: a flat contiguous uint8 buffer is required, got {} {}'.format(buf.dtype, tuple(buf.shape)))
+    call = _InputCall('det_input', buf)
     table = np.ascontiguousarray(np.asarray(rows.numpy() if isinstance(rows, torch.Tensor) else rows, dtype=np.int64))
     if table.ndim != 2 or table.shape[0] < 1 or table.shape[1] != DET_INPUT_ROW_INTS:
         raise Sc2Error('det_input: a descriptor table [n >= 1, {}] is required, got {}'.format(DET_INPUT_ROW_INTS, table.shape))
@@ -1647,20 +1714,13 @@ def det_input(buf, rows, mean, std, out, tag=None):
         raise Sc2Error('det_input: a descriptor field beyond int32')
     table = table.astype(np.int32)
     n = int(table.shape[0])
-    if out.dtype != torch.float32 or out.dim() != 4 or out.shape[0] != n or out.shape[1] != 3 or not out.is_contiguous() or \
-            out.device != buf.device:
-        raise Sc2Error('det_input: out must be a contiguous float32 [{},3,Hp,Wp] tensor on {}, got {} {}'.format(
-            n, buf.device, out.dtype, tuple(out.shape)))
-    mean, std = [float(v) for v in mean], [float(v) for v in std]
-    if len(mean) != 3 or len(std) != 3:
-        raise Sc2Error('det_input: three mean and three std values are required')
+    dst = call.out(out, 'out', torch.float32, (n, 3, 'Hp', 'Wp')).detach()
+    fm, fs = call.norm(mean, std, Sc2Error, non_zero=False)      # (a zero std is the library's to refuse)
     Hp, Wp = int(out.shape[2]), int(out.shape[3])
-    fm, fs = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
-    dst = out.detach()
     with _timed(tag or 'det_input'):
         for i0 in range(0, n, DET_INPUT_MAX_BATCH):
             part = np.ascontiguousarray(table[i0:i0 + DET_INPUT_MAX_BATCH])
-            rc = lib().sc2_det_input(_ptr(buf), int(buf.numel()), ctypes.c_void_p(part.ctypes.data), int(part.shape[0]), fm, fs,
+            rc = lib().sc2_det_input(_ptr(buf), call.nbytes, ctypes.c_void_p(part.ctypes.data), int(part.shape[0]), fm, fs,
                                      _ptr(dst[i0:i0 + DET_INPUT_MAX_BATCH]), Hp, Wp, _stream())
             if rc != 0:
                 raise Sc2Error('det_input failed (code {}): {}'.format(rc, last_error()))
@@ -1672,58 +1732,36 @@ def det_input(buf, rows, mean, std, out, tag=None):
 # --------------------------------------------------------------------------------------------- #
 SEG_AUGMENT_FIELDS = ('image_offset', 'mask_offset', 'h', 'w', 'nh', 'nw', 'flip', 'top', 'left', 'ext_h', 'ext_w', 'pad_h', 'pad_w')
 SegAugment = collections.namedtuple('SegAugment', ['images', 'targets', 'status', 'workspace'])
+_SEG_AUGMENT_TABLE = _DescTable('seg_augment', SEG_AUGMENT_FIELDS, lambda f: (
+    ('pad_h', max(f['nh'], f['top'] + f['ext_h'])), ('pad_w', max(f['nw'], f['left'] + f['ext_w']))), SEG_AUGMENT_DESC_INTS, SEG_AUGMENT_MAX_BATCH)
 
 
 def seg_augment_desc(**fields):
     """One descriptor row (int32 [SEG_AUGMENT_DESC_INTS]) from SEG_AUGMENT_FIELDS by name; pad_h / pad_w (the padded size, which only
     `seg_augment_check` reads) default to max(nh, top + ext_h) / max(nw, left + ext_w)."""
-    import numpy as np
-    fields.setdefault('pad_h', max(fields['nh'], fields['top'] + fields['ext_h']))
-    fields.setdefault('pad_w', max(fields['nw'], fields['left'] + fields['ext_w']))
-    row = np.zeros(SEG_AUGMENT_DESC_INTS, dtype=np.int32)
-    for k, name in enumerate(SEG_AUGMENT_FIELDS):
-        row[k] = int(fields.pop(name))
-    assert not fields, 'seg_augment_desc: unknown fields {}'.format(sorted(fields))
-    return row
+    return _SEG_AUGMENT_TABLE.row(fields)
 
 
 def seg_augment_check(desc, nbytes, oh, ow):
     """Refuses a malformed descriptor table on the host, before any launch (ValueError naming the sample and the field): sides below
     1 or above SEG_AUGMENT_MAX_SIDE, offsets outside the buffer, a flip that is not 0 / 1, an extent outside its slot, a padded size
     smaller than the resized one, a window outside the padded image.  desc: integer array [n, SEG_AUGMENT_DESC_INTS]."""
-    import numpy as np
-    desc = np.asarray(desc)
-    if desc.ndim != 2 or desc.shape[1] != SEG_AUGMENT_DESC_INTS or desc.shape[0] < 1 or desc.shape[0] > SEG_AUGMENT_MAX_BATCH:
-        raise ValueError('seg_augment: a descriptor table [1..{}, {}] is required, got {}'.format(
-            SEG_AUGMENT_MAX_BATCH, SEG_AUGMENT_DESC_INTS, desc.shape))
-    if not (1 <= oh <= SEG_AUGMENT_MAX_SIDE and 1 <= ow <= SEG_AUGMENT_MAX_SIDE):
-        raise ValueError('seg_augment: a {} x {} output slot (sides 1..{})'.format(oh, ow, SEG_AUGMENT_MAX_SIDE))
-    if not 1 <= nbytes <= 0x7FFFFFFF:
-        raise ValueError('seg_augment: a source buffer of {} bytes (1..2^31-1)'.format(nbytes))
-    for i, row in enumerate(desc.tolist()):
-        f = dict(zip(SEG_AUGMENT_FIELDS, row))
-
-        def refuse(name, why):
-            raise ValueError('seg_augment: sample {}: {} = {}: {}'.format(i, name, f[name], why))
-        for name in ('h', 'w', 'nh', 'nw'):
-            if not 1 <= f[name] <= SEG_AUGMENT_MAX_SIDE:
-                refuse(name, 'sides are 1..{}'.format(SEG_AUGMENT_MAX_SIDE))
-        if f['image_offset'] < 0 or f['image_offset'] + 3 * f['h'] * f['w'] > nbytes:
-            refuse('image_offset', 'the image lies outside the buffer of {} bytes'.format(nbytes))
-        if f['mask_offset'] < 0 or f['mask_offset'] + f['h'] * f['w'] > nbytes:
-            refuse('mask_offset', 'the mask lies outside the buffer of {} bytes'.format(nbytes))
-        if f['flip'] not in (0, 1):
-            refuse('flip', '0 or 1')
+    for r in _SEG_AUGMENT_TABLE.rows(desc, nbytes, oh, ow):
+        f = r.f
+        r.sides('h', 'w', 'nh', 'nw')
+        r.inside('image_offset', 3, 'image')
+        r.inside('mask_offset', 1, 'mask')
+        r.flip()
         for name, limit in (('ext_h', oh), ('ext_w', ow)):
             if not 1 <= f[name] <= limit:
-                refuse(name, 'the extent is 1..{}'.format(limit))
+                r.refuse(name, 'the extent is 1..{}'.format(limit))
         for name, resized in (('pad_h', 'nh'), ('pad_w', 'nw')):
             if f[name] < f[resized] or f[name] > SEG_AUGMENT_MAX_SIDE:
-                refuse(name, 'the padded size is {}..{}'.format(f[resized], SEG_AUGMENT_MAX_SIDE))
+                r.refuse(name, 'the padded size is {}..{}'.format(f[resized], SEG_AUGMENT_MAX_SIDE))
         for name, ext, padded in (('top', 'ext_h', 'pad_h'), ('left', 'ext_w', 'pad_w')):
             if f[name] < 0 or f[name] + f[ext] > f[padded]:
-                refuse(name, 'the window of {} lies outside the padded image of {}'.format(f[ext], f[padded]))
-    return desc
+                r.refuse(name, 'the window of {} lies outside the padded image of {}'.format(f[ext], f[padded]))
+    return np.asarray(desc)
 
 
 def seg_augment(buf, desc, size, mean, std, images_out=None, targets_out=None, return_workspace=False, tag=None):
@@ -1734,31 +1772,21 @@ def seg_augment(buf, desc, size, mean, std, images_out=None, targets_out=None, r
     -> SegAugment(images, targets, status int32 [n] on the device, workspace): nothing is read back; a sample whose status is not 0
     (SEG_AUGMENT_RATIO: an axis shrinks by more than 4) has unspecified outputs.  `workspace` (tests) is the int32 table
     [n, ow + oh, SEG_AUGMENT_ENTRY_INTS] when asked for, else None."""
-    import numpy as np
-    _dev(buf, 'seg_augment: buf')
-    if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
-        raise Sc2Error('seg_augment: a flat contiguous uint8 buffer is required, got {} {}'.format(buf.dtype, tuple(buf.shape)))
+    call = _InputCall('seg_augment', buf)
     oh, ow = int(size[0]), int(size[1])
     table = np.ascontiguousarray(desc.numpy() if isinstance(desc, torch.Tensor) else desc)
-    seg_augment_check(table, int(buf.numel()), oh, ow)
-    n, dev = int(table.shape[0]), buf.device
-    mean, std = [float(v) for v in mean], [float(v) for v in std]
-    if len(mean) != 3 or len(std) != 3 or any(v == 0.0 for v in std):
-        raise ValueError('seg_augment: three mean and three non-zero std values are required')
+    seg_augment_check(table, call.nbytes, oh, ow)
+    n, dev = int(table.shape[0]), call.dev
+    fm, fs = call.norm(mean, std, ValueError, non_zero=True)
     d_desc = torch.from_numpy(table.astype(np.int32)).to(dev, non_blocking=True)
-    images = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=dev) if images_out is None else _dev(images_out, 'seg_augment: images_out')
-    targets = torch.empty((n, oh, ow), dtype=torch.int64, device=dev) if targets_out is None else _dev(targets_out, 'seg_augment: targets_out')
-    if images.dtype != torch.float32 or tuple(images.shape) != (n, 3, oh, ow) or not images.is_contiguous() or images.device != dev:
-        raise Sc2Error('seg_augment: images_out must be a contiguous float32 [{},3,{},{}] tensor on {}'.format(n, oh, ow, dev))
-    if targets.dtype != torch.int64 or tuple(targets.shape) != (n, oh, ow) or not targets.is_contiguous() or targets.device != dev:
-        raise Sc2Error('seg_augment: targets_out must be a contiguous int64 [{},{},{}] tensor on {}'.format(n, oh, ow, dev))
+    images = call.out(images_out, 'images_out', torch.float32, (n, 3, oh, ow))
+    targets = call.out(targets_out, 'targets_out', torch.int64, (n, oh, ow))
     ws_bytes = int(lib().sc2_seg_augment_workspace(n, oh, ow))
     assert ws_bytes == n * (oh + ow) * SEG_AUGMENT_ENTRY_INTS * 4
     ws = torch.empty((n, ow + oh, SEG_AUGMENT_ENTRY_INTS), dtype=torch.int32, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
-    fm, fs = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
     with _timed(tag or 'seg_augment'):
-        _check(lib().sc2_seg_augment(_ptr(buf), int(buf.numel()), _ptr(d_desc), n, oh, ow, fm, fs, _ptr(images), _ptr(targets), _ptr(ws),
+        _check(lib().sc2_seg_augment(_ptr(buf), call.nbytes, _ptr(d_desc), n, oh, ow, fm, fs, _ptr(images), _ptr(targets), _ptr(ws),
                                      _ptr(status), _stream()), 'seg_augment')
     return SegAugment(images, targets, status, ws if return_workspace else None)
 
@@ -1768,20 +1796,15 @@ def seg_augment(buf, desc, size, mean, std, images_out=None, targets_out=None, r
 # --------------------------------------------------------------------------------------------- #
 CLS_INPUT_FIELDS = ('offset', 'h', 'w', 'full_h', 'full_w', 'row0', 'col0', 'nh', 'nw', 'flip', 'top', 'left')
 ClsInput = collections.namedtuple('ClsInput', ['images', 'status'])
+_CLS_INPUT_TABLE = _DescTable('cls_input', CLS_INPUT_FIELDS, lambda f: (
+    ('full_h', f.get('h')), ('full_w', f.get('w')), ('row0', 0), ('col0', 0), ('flip', 0), ('top', 0), ('left', 0)), CLS_INPUT_DESC_INTS,
+                              CLS_INPUT_MAX_BATCH)
 
 
 def cls_input_desc(**fields):
     """One descriptor row (int32 [CLS_INPUT_DESC_INTS]) from CLS_INPUT_FIELDS by name.  offset, h, w, nh, nw are required; the rest
     default to the train form: full_h / full_w = h / w, row0 = col0 = 0, flip = 0, top = left = 0."""
-    import numpy as np
-    for name, default in (('full_h', fields.get('h')), ('full_w', fields.get('w')), ('row0', 0), ('col0', 0), ('flip', 0), ('top', 0),
-                          ('left', 0)):
-        fields.setdefault(name, default)
-    row = np.zeros(CLS_INPUT_DESC_INTS, dtype=np.int32)
-    for k, name in enumerate(CLS_INPUT_FIELDS):
-        row[k] = int(fields.pop(name))
-    assert not fields, 'cls_input_desc: unknown fields {}'.format(sorted(fields))
-    return row
+    return _CLS_INPUT_TABLE.row(fields)
 
 
 def cls_input_check(desc, nbytes, oh, ow):
@@ -1789,34 +1812,18 @@ def cls_input_check(desc, nbytes, oh, ow):
     or above SEG_AUGMENT_MAX_SIDE, a stored box outside the buffer or outside the full image, a flip that is not 0 / 1, a window outside
     the resized image.  A ratio above 4 and a tap outside the stored box are the kernel's to flag (its status word): they are well
     formed.  desc: integer array [n, CLS_INPUT_DESC_INTS]."""
-    import numpy as np
-    desc = np.asarray(desc)
-    if desc.ndim != 2 or desc.shape[1] != CLS_INPUT_DESC_INTS or desc.shape[0] < 1 or desc.shape[0] > CLS_INPUT_MAX_BATCH:
-        raise ValueError('cls_input: a descriptor table [1..{}, {}] is required, got {}'.format(
-            CLS_INPUT_MAX_BATCH, CLS_INPUT_DESC_INTS, desc.shape))
-    if not (1 <= oh <= SEG_AUGMENT_MAX_SIDE and 1 <= ow <= SEG_AUGMENT_MAX_SIDE):
-        raise ValueError('cls_input: a {} x {} output slot (sides 1..{})'.format(oh, ow, SEG_AUGMENT_MAX_SIDE))
-    if not 1 <= nbytes <= 0x7FFFFFFF:
-        raise ValueError('cls_input: a source buffer of {} bytes (1..2^31-1)'.format(nbytes))
-    for i, row in enumerate(desc.tolist()):
-        f = dict(zip(CLS_INPUT_FIELDS, row))
-
-        def refuse(name, why):
-            raise ValueError('cls_input: sample {}: {} = {}: {}'.format(i, name, f[name], why))
-        for name in ('h', 'w', 'full_h', 'full_w', 'nh', 'nw'):
-            if not 1 <= f[name] <= SEG_AUGMENT_MAX_SIDE:
-                refuse(name, 'sides are 1..{}'.format(SEG_AUGMENT_MAX_SIDE))
-        if f['offset'] < 0 or f['offset'] + 3 * f['h'] * f['w'] > nbytes:
-            refuse('offset', 'the stored box lies outside the buffer of {} bytes'.format(nbytes))
+    for r in _CLS_INPUT_TABLE.rows(desc, nbytes, oh, ow):
+        f = r.f
+        r.sides('h', 'w', 'full_h', 'full_w', 'nh', 'nw')
+        r.inside('offset', 3, 'stored box')
         for name, side, full in (('row0', 'h', 'full_h'), ('col0', 'w', 'full_w')):
             if f[name] < 0 or f[name] + f[side] > f[full]:
-                refuse(name, 'the stored box of {} lies outside the full image of {}'.format(f[side], f[full]))
-        if f['flip'] not in (0, 1):
-            refuse('flip', '0 or 1')
+                r.refuse(name, 'the stored box of {} lies outside the full image of {}'.format(f[side], f[full]))
+        r.flip()
         for name, ext, resized in (('top', oh, 'nh'), ('left', ow, 'nw')):
             if f[name] < 0 or f[name] + ext > f[resized]:
-                refuse(name, 'the window of {} lies outside the resized image of {}'.format(ext, f[resized]))
-    return desc
+                r.refuse(name, 'the window of {} lies outside the resized image of {}'.format(ext, f[resized]))
+    return np.asarray(desc)
 
 
 def cls_input(buf, desc, size, mean, std, images_out=None, tag=None):
@@ -1826,27 +1833,18 @@ def cls_input(buf, desc, size, mean, std, images_out=None, tag=None):
     caller's contiguous tensor to write into.
     -> ClsInput(images, status int32 [n] on the device): nothing is read back; a sample whose status is not 0 (CLS_INPUT_RATIO: an
     axis shrinks by more than 4; CLS_INPUT_TAP: a tap outside its stored box) has its slot unwritten."""
-    import numpy as np
-    _dev(buf, 'cls_input: buf')
-    if buf.dtype != torch.uint8 or buf.dim() != 1 or not buf.is_contiguous():
-        raise Sc2Error('cls_input: a flat contiguous uint8 buffer is required, got {} {}'.format(buf.dtype, tuple(buf.shape)))
+    call = _InputCall('cls_input', buf)
     oh, ow = int(size[0]), int(size[1])
     table = np.ascontiguousarray(desc.numpy() if isinstance(desc, torch.Tensor) else desc)
-    cls_input_check(table, int(buf.numel()), oh, ow)
-    n, dev = int(table.shape[0]), buf.device
-    mean, std = [float(v) for v in mean], [float(v) for v in std]
-    if len(mean) != 3 or len(std) != 3 or any(v == 0.0 for v in std):
-        raise ValueError('cls_input: three mean and three non-zero std values are required')
+    cls_input_check(table, call.nbytes, oh, ow)
+    n, dev = int(table.shape[0]), call.dev
+    fm, fs = call.norm(mean, std, ValueError, non_zero=True)
     d_desc = torch.from_numpy(table.astype(np.int32)).to(dev, non_blocking=True)
-    images = torch.empty((n, 3, oh, ow), dtype=torch.float32, device=dev) if images_out is None else _dev(images_out, 'cls_input: images_out')
-    if images.dtype != torch.float32 or tuple(images.shape) != (n, 3, oh, ow) or not images.is_contiguous() or images.device != dev:
-        raise Sc2Error('cls_input: images_out must be a contiguous float32 [{},3,{},{}] tensor on {}'.format(n, oh, ow, dev))
+    images = call.out(images_out, 'images_out', torch.float32, (n, 3, oh, ow))
     assert int(lib().sc2_cls_input_workspace(n, oh, ow)) == 0      # one launch, tables in LDS: nothing to allocate
     status = torch.empty(n, dtype=torch.int32, device=dev)
-    fm, fs = (ctypes.c_float * 3)(*mean), (ctypes.c_float * 3)(*std)
     with _timed(tag or 'cls_input'):
-        _check(lib().sc2_cls_input(_ptr(buf), int(buf.numel()), _ptr(d_desc), n, oh, ow, fm, fs, _ptr(images), _ptr(status), _stream()),
-               'cls_input')
+        _check(lib().sc2_cls_input(_ptr(buf), call.nbytes, _ptr(d_desc), n, oh, ow, fm, fs, _ptr(images), _ptr(status), _stream()), 'cls_input')
     return ClsInput(images, status)
 
 

@@ -887,7 +887,56 @@ class CustomNormalize(object):
         return self._normalize(image), target
 
 
-class DeferredSegSample(object):
+class _PlannedSample(object):
+    """A planned sample pickles as the dict of its slots (a data-loader worker sends it to the main process)."""
+    __slots__ = ()
+
+    def __getstate__(self):
+        return {k: getattr(self, k) for k in self.__slots__}
+
+    def __setstate__(self, state):
+        for k, v in state.items():
+            setattr(self, k, v)
+
+
+def _pack_planned(samples, parts_of, row_of):
+    """(buf, desc) of a planned batch: the byte arrays `parts_of(sample)` of every sample back to back in one flat CPU uint8 tensor,
+    and the stacked descriptor rows `row_of(sample, offset)`, offset being where the sample's bytes start"""
+    rows, chunks, offset = [], [], 0
+    for s in samples:
+        parts = [np.ascontiguousarray(p).reshape(-1) for p in parts_of(s)]
+        rows.append(row_of(s, offset))
+        chunks += parts
+        offset += sum(p.size for p in parts)
+    return torch.from_numpy(np.concatenate(chunks)), torch.from_numpy(np.stack(rows))
+
+
+def _launch_on_copy(host_buf, device, copies, launch):
+    """-> launch(buf), buf being the copy of `host_buf` on the HIP device (made here unless `copies`, device -> copy, has it)"""
+    with torch.cuda.device(device):         # (the launches go to the current device's current stream)
+        buf = copies.get(device)
+        if buf is None:
+            buf = copies[device] = host_buf.to(device, non_blocking=True)
+        out = launch(buf)
+        # (the kernels read `buf` on the current stream: the allocator must not hand its block out before they have run)
+        buf.record_stream(torch.cuda.current_stream(device))
+    return out
+
+
+def _planned_on_device(cls, batch, device, enabled, launch):
+    """The device path of `materialize` of a planned batch: one copy up of `batch.buf`, `launch(buf)`, one read-back of the status
+    words.  -> what `launch` returned; None where the host path is to be taken: no HIP device, the switch off, or a status word set
+    (a sample the kernels' own checks refuse), which `cls.fallbacks` counts."""
+    if device.type != 'cuda' or not enabled:
+        return None
+    res = _launch_on_copy(batch.buf, device, dict(), launch)
+    if bool(res.status.cpu().any()):
+        cls.fallbacks += 1
+        return None
+    return res
+
+
+class DeferredSegSample(_PlannedSample):
     """What `CustomCompose.plan` hands out in place of the transformed pair: the source bytes and every drawn parameter, as numpy, so
     that a data-loader worker neither resizes nor opens the device.  image uint8 [h,w,3], mask uint8 [h,w]; (nh, nw) the resized
     size, flip, (top, left) the crop's origin in the padded, flipped, resized image, (out_h, out_w) the size of the finished
@@ -899,13 +948,6 @@ class DeferredSegSample(object):
         self.nh, self.nw, self.flip, self.top, self.left = int(nh), int(nw), bool(flip), int(top), int(left)
         self.out_h, self.out_w, self.pad_h, self.pad_w = int(out_h), int(out_w), int(pad_h), int(pad_w)
         self.mean, self.std = tuple(float(v) for v in mean), tuple(float(v) for v in std)
-
-    def __getstate__(self):
-        return {k: getattr(self, k) for k in self.__slots__}
-
-    def __setstate__(self, state):
-        for k, v in state.items():
-            setattr(self, k, v)
 
     def host(self):
         """The pair `CustomCompose.__call__` returns for these draws: Pillow and torch on the host."""
@@ -989,17 +1031,9 @@ class DeferredSegBatch(object):
         self.mean, self.std = samples[0].mean, samples[0].std
         self.size = (max(s.out_h for s in samples), max(s.out_w for s in samples))
         self.extra = tuple(extra)
-        rows, chunks, offset = [], [], 0
-        for s in samples:
-            img, mask = np.ascontiguousarray(s.image).reshape(-1), np.ascontiguousarray(s.mask).reshape(-1)
-            h, w = s.mask.shape
-            rows.append(hip.seg_augment_desc(image_offset=offset, mask_offset=offset + img.size, h=h, w=w, nh=s.nh, nw=s.nw,
-                                             flip=int(s.flip), top=s.top, left=s.left, ext_h=s.out_h, ext_w=s.out_w, pad_h=s.pad_h,
-                                             pad_w=s.pad_w))
-            chunks += [img, mask]
-            offset += img.size + mask.size
-        self.buf = torch.from_numpy(np.concatenate(chunks))
-        self.desc = torch.from_numpy(np.stack(rows))
+        self.buf, self.desc = _pack_planned(samples, lambda s: (s.image, s.mask), lambda s, offset: hip.seg_augment_desc(
+            image_offset=offset, mask_offset=offset + s.image.size, h=s.mask.shape[0], w=s.mask.shape[1], nh=s.nh, nw=s.nw, flip=int(s.flip),
+            top=s.top, left=s.left, ext_h=s.out_h, ext_w=s.out_w, pad_h=s.pad_h, pad_w=s.pad_w))
 
     def __len__(self):
         return int(self.desc.shape[0])
@@ -1024,18 +1058,9 @@ class DeferredSegBatch(object):
         """-> (images f32 [n,3,H,W], targets int64 [n,H,W]) on `device`."""
         from . import hip
         device = torch.device('cpu' if device is None else device)
-        if device.type != 'cuda' or not hip.host_policy.seg_augment_hip:
-            return self.materialize_host(device)
-        with torch.cuda.device(device):         # (the launches go to the current device's current stream)
-            buf = self.buf.to(device, non_blocking=True)
-            res = hip.seg_augment(buf, self.desc, self.size, self.mean, self.std)
-            # (the kernels read `buf` on the current stream: the allocator must not hand its block out before they have run)
-            buf.record_stream(torch.cuda.current_stream(device))
-            flagged = bool(res.status.cpu().any())      # the one read-back of a batch: a sample beyond the kernels' ratio cap
-        if flagged:
-            DeferredSegBatch.fallbacks += 1
-            return self.materialize_host(device)
-        return res.images, res.targets
+        res = _planned_on_device(DeferredSegBatch, self, device, hip.host_policy.seg_augment_hip,
+                                 lambda buf: hip.seg_augment(buf, self.desc, self.size, self.mean, self.std))
+        return self.materialize_host(device) if res is None else (res.images, res.targets)
 
     def pin_memory(self):
         self.buf = self.buf.pin_memory()
@@ -1071,7 +1096,7 @@ def pil_tap_span(n_in, n_out, origin, length):
     return pil_tap_bounds(n_in, n_out, origin)[0], last[0] + last[1]
 
 
-class DeferredClsSample(object):
+class DeferredClsSample(_PlannedSample):
     """What `Compose.plan` hands out in place of the transformed image: `image`, uint8 [h,w,3], a box of the source at (row0, col0) of
     a full_h x full_w image -- the only bytes the output depends on -- and the parameters: (nh, nw) the resized size of the FULL image,
     flip, (top, left) the origin of the out_h x out_w window in the resized, flipped image, mean / std.  Train form: the box is the
@@ -1093,13 +1118,6 @@ class DeferredClsSample(object):
         window = np.asarray(window)
         h, w = window.shape[:2]
         return cls(window, h, w, 0, 0, h, w, False, 0, 0, h, w, mean, std)
-
-    def __getstate__(self):
-        return {k: getattr(self, k) for k in self.__slots__}
-
-    def __setstate__(self, state):
-        for k, v in state.items():
-            setattr(self, k, v)
 
     def host(self):
         """The tensor `Compose.__call__` returns for these draws: Pillow and torch on the host.  A box smaller than its full image is
@@ -1140,15 +1158,9 @@ class DeferredClsBatch(object):
         from . import hip
         self.mean, self.std, self.size = first.mean, first.std, (first.out_h, first.out_w)
         self.device = torch.device('cpu')
-        rows, chunks, offset = [], [], 0
-        for s in samples:
-            box = np.ascontiguousarray(s.image).reshape(-1)
-            rows.append(hip.cls_input_desc(offset=offset, h=s.image.shape[0], w=s.image.shape[1], full_h=s.full_h, full_w=s.full_w,
-                                           row0=s.row0, col0=s.col0, nh=s.nh, nw=s.nw, flip=int(s.flip), top=s.top, left=s.left))
-            chunks.append(box)
-            offset += box.size
-        self.buf = torch.from_numpy(np.concatenate(chunks))
-        self.desc = torch.from_numpy(np.stack(rows))
+        self.buf, self.desc = _pack_planned(samples, lambda s: (s.image,), lambda s, offset: hip.cls_input_desc(
+            offset=offset, h=s.image.shape[0], w=s.image.shape[1], full_h=s.full_h, full_w=s.full_w, row0=s.row0, col0=s.col0, nh=s.nh,
+            nw=s.nw, flip=int(s.flip), top=s.top, left=s.left))
 
     def __len__(self):
         return int(self.desc.shape[0])
@@ -1178,18 +1190,9 @@ class DeferredClsBatch(object):
         """-> images f32 [n,3,H,W] on `device` (default: where `to` sent the batch)"""
         from . import hip
         device = torch.device(self.device if device is None else device)
-        if device.type != 'cuda' or not hip.host_policy.cls_input_hip:
-            return self.materialize_host(device)
-        with torch.cuda.device(device):         # (the launch goes to the current device's current stream)
-            buf = self.buf.to(device, non_blocking=True)
-            res = hip.cls_input(buf, self.desc, self.size, self.mean, self.std)
-            # (the kernel reads `buf` on the current stream: the allocator must not hand its block out before it has run)
-            buf.record_stream(torch.cuda.current_stream(device))
-            flagged = bool(res.status.cpu().any())      # the one read-back of a batch: a descriptor the kernel's own checks refuse
-        if flagged:
-            DeferredClsBatch.fallbacks += 1
-            return self.materialize_host(device)
-        return res.images
+        res = _planned_on_device(DeferredClsBatch, self, device, hip.host_policy.cls_input_hip,
+                                 lambda buf: hip.cls_input(buf, self.desc, self.size, self.mean, self.std))
+        return self.materialize_host(device) if res is None else res.images
 
 
 @register_collate_func
@@ -1206,7 +1209,7 @@ def cls_collate_fn(batch):
     return DeferredClsBatch([item[0] for item in batch]), default_collate([item[1] for item in batch])
 
 
-class DeferredDetSample(object):
+class DeferredDetSample(_PlannedSample):
     """What `coco_data.Compose.plan` hands out in place of the float image: the source bytes as numpy uint8 [h,w,3] and the drawn
     `flip`, so that a data-loader worker converts nothing.  `.shape` is the (3, h, w) of the tensor it stands for; `host()` is that
     tensor: `to_tensor` and the flip."""
@@ -1215,13 +1218,6 @@ class DeferredDetSample(object):
     def __init__(self, image, flip):
         assert image.dtype == np.uint8 and image.ndim == 3 and image.shape[2] == 3, 'DeferredDetSample: uint8 [h,w,3] is required'
         self.image, self.flip = image, bool(flip)
-
-    def __getstate__(self):
-        return {k: getattr(self, k) for k in self.__slots__}
-
-    def __setstate__(self, state):
-        for k, v in state.items():
-            setattr(self, k, v)
 
     @property
     def shape(self):
@@ -1313,14 +1309,8 @@ class DeferredDetBatch(object):
         max_h = int(math.ceil(max(s[0] for s in image_sizes) / stride) * stride)
         max_w = int(math.ceil(max(s[1] for s in image_sizes) / stride) * stride)
         rows = [(off, h, w, oh, ow, int(flip)) for off, (h, w), (oh, ow), flip in zip(self.offsets, self.sizes, image_sizes, self.flips)]
-        with torch.cuda.device(device):         # (the launch goes to the current device's current stream)
-            buf = self._on_device.get(device)
-            if buf is None:
-                buf = self._on_device[device] = self.buf.to(device, non_blocking=True)
-            batched = torch.empty((len(self), 3, max_h, max_w), dtype=torch.float32, device=device)      # every element is written
-            hip.det_input(buf, rows, mean, std, batched)
-            # (the kernel reads `buf` on the current stream: the allocator must not hand its block out before it has run)
-            buf.record_stream(torch.cuda.current_stream(device))
+        batched = _launch_on_copy(self.buf, device, self._on_device, lambda buf: hip.det_input(      # (every element is written)
+            buf, rows, mean, std, torch.empty((len(self), 3, max_h, max_w), dtype=torch.float32, device=device)))
         DeferredDetBatch.launches += -(-len(self) // hip.DET_INPUT_MAX_BATCH)
         self._cache[key] = (batched, image_sizes)
         return batched, image_sizes
