@@ -914,6 +914,42 @@ int sc2_box_match(const float *gt, const int32_t *gt_off, const float *cand, con
                   const int32_t *cand_off_host, int n_img, int total_gt, int total_cand, float low, float high, int allow_low_quality,
                   int32_t *matches, float *best_iou, void *ws, void *stream);
 
+#define SC2_DETPOST_MAX_CLASSES 128   /* C, background included: a lane owns two classes */
+#define SC2_DETPOST_MAX_DET 1024      /* D = detections_per_img */
+#define SC2_DETPOST_MAX_SEG 2048      /* survivors of ONE class of one image: sorted and suppressed in LDS (the reference runs 1 000 proposals) */
+#define SC2_DETPOST_MAX_CAND 20480    /* survivors of one image: at most 1 / score_thresh classes of a row pass, 19 x 1 000 at 0.05 */
+#define SC2_DETPOST_OVER_CAND 1       /* status bits */
+#define SC2_DETPOST_OVER_SEG 2
+/* torchvision's `RoIHeads.postprocess_detections` for a batch (csrc/det_post.hip; tests/ref_det_post.py restates it).
+ * logits: f32 [R,C], deltas: f32 [R,4C] (16-byte aligned), proposals: f32 [R,4] (16-byte aligned), the rows of image i being
+ * offsets[i] .. offsets[i+1]; offsets: i32 [n+1] on the DEVICE and offsets_host the caller's HOST copy, checked before anything is
+ * launched as sc2_box_match checks its own (first 0, never decreasing, last == R: SC2_ERR_INVALID_ARG otherwise; the kernels read the
+ * device copy and clamp it to 0..R); image_sizes: i32 [n,2] (height, width) on the device.  2 <= C <= SC2_DETPOST_MAX_CLASSES,
+ * 1 <= D <= SC2_DETPOST_MAX_DET, R (C-1) < 2^31 (SC2_ERR_UNSUPPORTED otherwise), n <= 65535; no threshold may be NaN.
+ * Stage A, per (row r, class c >= 1), all in f32 with every operation rounded once:
+ *   score = exp(l_c - max) / sum, max and sum over the row's C logits (sum: classes c and c + 64 first, then a fixed butterfly);
+ *   the box is BoxCoder.decode_single in that function's order: widths = x2 - x1, ctr_x = x1 + 0.5 * widths, dx = d0 / wx,
+ *   dw = d2 / ww cut at bbox_xform_clip, pred_ctr_x = dx * widths + ctr_x, half_w = 0.5 * (exp(dw) * widths), x1' = pred_ctr_x - half_w,
+ *   x2' = pred_ctr_x + half_w (y likewise), then clipped to [0, width] x [0, height];
+ *   the candidate survives iff score > score_thresh and x2' - x1' >= min_size and y2' - y1' >= min_size.  Comparisons with a NaN
+ *   are false: a row whose scores are NaN (a NaN or +infinite logit) yields no candidate.
+ * Stage B, per image: the survivors in order of descending score, equal scores by ascending flat index r_local * (C-1) + (c-1) (the
+ * stable sort of `batched_nms`); greedy NMS within each class with sc2_nms's IoU and test (IoU > nms_thresh, the earlier box first);
+ * the first D kept, in that order, are the image's detections.
+ * boxes: f32 [n,D,4] (16-byte aligned), scores: f32 [n,D], labels: i64 [n,D], count, status: i32 [n].  EVERY element is written
+ * exactly once: slots at or behind count[i] hold zeros.  An image with more than SC2_DETPOST_MAX_CAND survivors, or more than
+ * SC2_DETPOST_MAX_SEG of one class, gets the matching status bit and count 0 (the caller takes another path); status 0 otherwise.
+ * cand_scores f32 [R,C-1], cand_boxes f32 [R,C-1,4] (16-byte aligned): both NULL in production; a test passes both and receives the
+ * whole candidate table of stage A (survivors or not), which stage B then reads in place of the workspace's copy.
+ * Three launches on `stream` whatever n is (rows; (class, image) segments: bitonic sort and the greedy walk in LDS, stopping at D
+ * kept; one merge per image), none when n == 0; nothing is copied to the host, no atomics on global memory: the same bits each call.
+ * ws: sc2_det_postprocess_ws_bytes(R, C, n, D) bytes, 16-byte aligned (0 for dimensions outside the ranges above). */
+long long sc2_det_postprocess_ws_bytes(int R, int C, int n, int D);
+int sc2_det_postprocess(const float *logits, const float *deltas, const float *proposals, const int32_t *offsets, const int32_t *offsets_host,
+                        const int32_t *image_sizes, int R, int C, int n, float wx, float wy, float ww, float wh, float bbox_xform_clip,
+                        float score_thresh, float min_size, float nms_thresh, int D, float *boxes, float *scores, int64_t *labels,
+                        int32_t *count, int32_t *status, float *cand_scores, float *cand_boxes, void *ws, void *stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Segmentation tail (csrc/seg.hip): low-resolution class logits -> labels of the resized map and confusion counts, */
 /* one launch.  tests/ref_seg.py restates it in float64.                                                            */

@@ -8,23 +8,13 @@
 
 #pragma clang fp contract(off)   // `area_a + area_b - w * h`, `start + p * bin + ...`: every step rounded once, as the restatement does
 
-namespace {
+#include "detect_common.h"      // box_iou / box_area, the alignment tests, match_range / match_offsets_ok (shared with det_post.hip)
 
-inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-inline bool aligned8(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0; }
+namespace {
 
 // ------------------------------------------------------------------------------------------------------------------ NMS
 constexpr int NMS_BLOCK = 64;       // boxes per mask word
 constexpr int NMS_SCAN_THREADS = 256;
-
-// IoU in f32, each operation rounded once (contraction is off above; `/` is the correctly rounded IEEE division)
-__device__ __forceinline__ float box_iou(const float4 a, const float area_a, const float4 b, const float area_b) {
-    const float w = fmaxf(0.0f, fminf(a.z, b.z) - fmaxf(a.x, b.x));
-    const float h = fmaxf(0.0f, fminf(a.w, b.w) - fmaxf(a.y, b.y));
-    const float inter = w * h;
-    return inter / (area_a + area_b - inter);
-}
-__device__ __forceinline__ float box_area(const float4 b) { return (b.z - b.x) * (b.w - b.y); }
 
 // Launch 1: workgroup (cb, rb), cb >= rb, compares the 64 boxes of row block rb (one per lane) with the 64 boxes of column block cb
 // (staged in LDS) and writes one word per row: bit c set iff box cb*64+c comes later in the order, is of the row's group and
@@ -427,12 +417,6 @@ struct MatchArgs {
     float low, high;
 };
 
-// the bounds of image `img` in an array of `total` rows, from the device's offsets: clamped, so that whatever they hold stays inside
-__device__ __forceinline__ void match_range(const int32_t *off, int img, int total, int &b, int &e) {
-    b = min(max(off[img], 0), total);
-    e = min(max(off[img + 1], b), total);
-}
-
 // Launch 1: workgroup (chunk, image): the maximum IoU of every gt box of the image over candidates [chunk * 2048, +2048) of it.
 // A thread holds eight candidates in registers; per gt box a wave reduces by shuffles, the four waves through LDS.
 __global__ __launch_bounds__(MATCH_THREADS) void match_gtmax_kernel(const MatchArgs a) {
@@ -551,17 +535,6 @@ __global__ __launch_bounds__(MATCH_THREADS) void match_assign_kernel(const Match
         a.matches[cbeg + q] = m;
         if (a.best_iou) a.best_iou[cbeg + q] = best[i];
     }
-}
-
-// offsets as the caller's host copy states them: start at 0, never decrease, end at the total
-inline bool match_offsets_ok(const int32_t *off, int n_img, int total, int &longest) {
-    if (off[0] != 0) return false;
-    longest = 0;
-    for (int i = 0; i < n_img; ++i) {
-        if (off[i + 1] < off[i] || off[i + 1] > total) return false;
-        longest = off[i + 1] - off[i] > longest ? off[i + 1] - off[i] : longest;
-    }
-    return off[n_img] == total;
 }
 
 }  // namespace

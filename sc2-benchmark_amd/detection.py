@@ -10,7 +10,11 @@ Two operations have no torch operator and run on the library's kernels (csrc/det
 non-maximum suppression (`nms`, `batched_nms` -> `hip.batched_nms`) and RoIAlign (`roi_align`, `multiscale_roi_align` ->
 `hip.roi_align`).  CPU tensors, and device tensors while `hip.host_policy.nms_hip` / `roi_align_hip` are off (A/B), take a
 torch-op implementation of the same definitions (include/sc2_bottleneck.h states them; tests/ref_detection.py restates
-them independently).  Everything else is small tensor algebra and two small GEMM stacks on torch ops.
+them independently).  The RoI heads' `postprocess_detections` runs for the whole batch on csrc/det_post.hip (`hip.det_postprocess`:
+softmax, decode, clip, the two filters, per-class NMS and the first `detections_per_img`, three launches and one read-back) for f32
+device tensors while `hip.host_policy.det_post_hip` is on; otherwise, and for a batch above that kernel's candidate caps, the
+per-image loop of torch ops around `batched_nms` (tests/ref_det_post.py restates the stage).  Everything else is small tensor
+algebra and two small GEMM stacks on torch ops.
 
 `RCNNTransformWithCompression` (sc2bench/models/detection/transform.py) is the transform of the input-compression baseline: a
 codec between resize and normalise; for plain JPEG on device images it runs on csrc/rcnn_input.hip + csrc/jpeg_image.hip.
@@ -667,7 +671,34 @@ class RoIHeads(nn.Module):
         self.box_coder = BoxCoder((10.0, 10.0, 5.0, 5.0) if bbox_reg_weights is None else bbox_reg_weights)
         self.score_thresh, self.nms_thresh, self.detections_per_img = score_thresh, nms_thresh, detections_per_img
 
+    def _postprocess_on_kernel(self, class_logits, box_regression, proposals, image_shapes):
+        """The whole batch on `hip.det_postprocess` (three launches, one read-back of the counts and the status words) -> the lists
+        of `postprocess_detections`, or None where that path does not apply -- CPU tensors, `hip.host_policy.det_post_hip` or
+        `nms_hip` off, another dtype than f32, a class count or `detections_per_img` outside the kernel's range -- or where an image exceeds one of
+        the kernel's candidate caps (a non-zero status): the caller then runs the loop below."""
+        if not (class_logits.is_cuda and hip.host_policy.det_post_hip and hip.host_policy.nms_hip):     # (nms_hip off: the tail on torch ops, A/B)
+            return None
+        tensors = [class_logits, box_regression] + list(proposals)
+        if any(t.dtype != torch.float32 or t.device != class_logits.device for t in tensors) or class_logits.dim() != 2:
+            return None
+        C, D, n = int(class_logits.shape[-1]), int(self.detections_per_img), len(proposals)
+        if not (2 <= C <= hip.DETPOST_MAX_CLASSES and 1 <= D <= hip.DETPOST_MAX_DET and 1 <= n == len(image_shapes) and n <= 65535
+                and int(class_logits.shape[0]) * (C - 1) < 2 ** 31):
+            return None
+        res = hip.det_postprocess(class_logits.detach().contiguous(), box_regression.detach().contiguous(),
+                                  torch.cat(list(proposals), dim=0).detach().contiguous(), [int(p.shape[0]) for p in proposals],
+                                  [(int(h), int(w)) for h, w in image_shapes], self.box_coder.weights, self.box_coder.bbox_xform_clip,
+                                  self.score_thresh, 1e-2, self.nms_thresh, D)
+        counts, status = res.count_status.cpu().tolist()
+        if any(status):
+            return None
+        return ([res.boxes[i, :k] for i, k in enumerate(counts)], [res.scores[i, :k] for i, k in enumerate(counts)],
+                [res.labels[i, :k] for i, k in enumerate(counts)])
+
     def postprocess_detections(self, class_logits, box_regression, proposals, image_shapes):
+        on_kernel = self._postprocess_on_kernel(class_logits, box_regression, proposals, image_shapes)
+        if on_kernel is not None:
+            return on_kernel
         device = class_logits.device
         num_classes = class_logits.shape[-1]
         boxes_per_image = [b.shape[0] for b in proposals]

@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     'sc2_gdn_bwd_pre_blocks', 'sc2_colsum_blocks', 'sc2_gdn_bwd_post_blocks', 'sc2_layout_blocks', 'sc2_gdn1_rows_units', 'sc2_gdn1_rows_workgroups',
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
-    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_roi_align_backward', 'sc2_box_match_ws_bytes', 'sc2_box_match', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_seg_augment_workspace', 'sc2_seg_augment', 'sc2_cls_input_workspace', 'sc2_cls_input', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
+    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_roi_align_backward', 'sc2_box_match_ws_bytes', 'sc2_box_match', 'sc2_det_postprocess_ws_bytes', 'sc2_det_postprocess', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_seg_augment_workspace', 'sc2_seg_augment', 'sc2_cls_input_workspace', 'sc2_cls_input', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
     'sc2_jpeg_max_bytes', 'sc2_jpeg_tensor_codec', 'sc2_jpeg_image_max_bytes', 'sc2_jpeg_image_workspace_bytes', 'sc2_jpeg_image_codec',
     'sc2_rcnn_resize_u8', 'sc2_rcnn_normalize_pad', 'sc2_det_input',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
@@ -69,6 +69,9 @@ NMS_MAX_BOXES = 16384      # SC2_NMS_MAX_BOXES
 ROI_MAX_LEVELS = 5         # SC2_ROI_MAX_LEVELS
 MATCH_CHUNK = 2048         # SC2_MATCH_CHUNK: candidates per workgroup of sc2_box_match's first launch
 MATCH_CAND_PER_WG, MATCH_GT_TILE = 1024, 64     # ... per workgroup of its second launch; gt boxes staged at a time
+DETPOST_MAX_CLASSES, DETPOST_MAX_DET = 128, 1024      # SC2_DETPOST_*: C (background included) and detections per image
+DETPOST_MAX_SEG, DETPOST_MAX_CAND = 2048, 20480       # survivors of one class of an image / of an image
+DETPOST_OVER_CAND, DETPOST_OVER_SEG = 1, 2            # status bits
 SEG_MAX_CLASSES = 64       # SC2_SEG_MAX_CLASSES
 SEG_CE_MEAN, SEG_CE_SUM, SEG_CE_NONE = 0, 1, 2     # SC2_SEG_CE_*
 COCO_THRS, COCO_RECS, COCO_AREAS, COCO_MAXDETS = 10, 101, 4, 3     # SC2_COCO_*
@@ -161,6 +164,7 @@ class HostPolicy(object):
     roi_align_hip = True       # detection.roi_align / multiscale_roi_align of device tensors on sc2_roi_align (False: torch ops, A/B)
     box_match_hip = True       # detection.match_boxes (the RPN's and the RoI heads' target assignment in training) of device tensors on sc2_box_match (False: the [G, A] `box_iou` matrix + `Matcher` on torch ops, A/B; tools/det_train_times.py, 6 images x 242 991 anchors x 20 gt boxes, 0.3 / 0.7 with low-quality matches: 0.17 against 2.41 ms, identical matches)
     roi_align_bwd_hip = True   # the backward of detection.multiscale_roi_align of f32 device maps on sc2_roi_align_backward (False: autograd through the torch-op restatement, forward included, A/B; tools/det_train_times.py, 3 072 RoIs over four maps of 6 images, C = 256, P = 7, S = 2: forward + backward 2.03 against 137.1 ms, the backward launch with its binning 1.64 ms)
+    det_post_hip = True        # detection.RoIHeads.postprocess_detections of f32 device tensors on sc2_det_postprocess: three launches and one read-back per batch (False, or nms_hip off: softmax + decode, then the per-image loop of torch ops around batched_nms, A/B; a batch above the kernel's candidate caps takes that loop too; tools/det_post_times.py, 6 images x 1 000 proposals x 91 classes with 300 - 390 candidates per image above 0.05: 0.196 against 2.271 ms per batch, medians of 7 alternating rounds, the three launches alone 0.095 ms)
     coco_eval_hip = True       # coco_eval.CocoBoxEvaluator.accumulate of device tensors on sc2_coco_match + sc2_coco_accumulate (False: the torch / numpy host path of the same module; tools/coco_eval_times.py)
     jpeg_codec_hip = True      # transforms.PILTensorModule(format='JPEG') of f32 device tensors up to 64 x 64 on sc2_jpeg_tensor_codec (False: PIL per channel group on the host, A/B; tools/jpeg_codec_times.py: 0.36 against 42.7 ms at [1,512,28,28])
     jpeg_image_hip = True      # transforms.PILImageModule(format='JPEG').forward_batch of equal-size RGB / grey PIL images up to 2048 x 2048 on sc2_jpeg_image_codec (False: PIL per image on the host, A/B; tools/jpeg_image_times.py, codec + ToTensor + Normalize to the classifier input: 0.39 against 0.50 ms at [1,3,224,224], 10.4 against 174 ms at [256,3,224,224])
@@ -350,6 +354,9 @@ def lib():
     L.sc2_box_match_ws_bytes.argtypes = [i32, i32]
     L.sc2_box_match_ws_bytes.restype = i64
     L.sc2_box_match.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, i32, vp, vp, vp, vp]
+    L.sc2_det_postprocess_ws_bytes.argtypes = [i32, i32, i32, i32]
+    L.sc2_det_postprocess_ws_bytes.restype = i64
+    L.sc2_det_postprocess.argtypes = [vp] * 6 + [i32] * 3 + [f32] * 8 + [i32] + [vp] * 9
     L.sc2_seg_predict.argtypes = [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, i32, vp, vp, vp, vp]
     L.sc2_seg_ce_ws_bytes.argtypes = [i32, i32, i32]
     L.sc2_seg_ce_ws_bytes.restype = i64
@@ -1357,6 +1364,82 @@ def box_match_offsets(gt_boxes, gt_offsets, boxes, offsets, low, high, allow_low
     return matches, best
 
 
+DetPostResult = collections.namedtuple('DetPostResult', ['boxes', 'scores', 'labels', 'count_status', 'candidates'])
+_det_post_ws = dict()          # (device index, stream, bytes) -> the workspace of sc2_det_postprocess
+_DET_POST_WS_KEPT = 4
+
+
+def det_postprocess_ws_bytes(R, C, n, D):
+    """Bytes of sc2_det_postprocess's workspace (0: dimensions outside the kernel's range)."""
+    return int(lib().sc2_det_postprocess_ws_bytes(int(R), int(C), int(n), int(D)))
+
+
+def _stream_workspace(cache, kept, device, n_bytes):
+    """One workspace per (device, stream, size) in `cache`: the launches of a stream are ordered, so its next call may write where the
+    last one read.  The `kept` most recent sizes stay."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream, n_bytes)
+    ws = cache.pop(key, None)
+    if ws is None:
+        ws = torch.empty((n_bytes,), dtype=torch.uint8, device=device)
+    cache[key] = ws               # (most recent last)
+    while len(cache) > kept:
+        cache.pop(next(iter(cache)))
+    return ws
+
+
+def det_postprocess(logits, deltas, proposals, counts, image_sizes, weights, bbox_xform_clip, score_thresh, min_size, nms_thresh,
+                    detections_per_img, out=None, ws=None, want_candidates=False, tag=None):
+    """torchvision's `RoIHeads.postprocess_detections` for a batch in three launches (include/sc2_bottleneck.h: sc2_det_postprocess).
+    logits f32 [R,C], deltas f32 [R,4C], proposals f32 [R,4], all contiguous on the device; counts: the proposals per image and
+    image_sizes: (height, width) per image, as Python ints; weights: BoxCoder's four; D = detections_per_img.
+    2 <= C <= DETPOST_MAX_CLASSES and 1 <= D <= DETPOST_MAX_DET (ValueError otherwise: there is no other path in this module).
+    -> DetPostResult: boxes f32 [n,D,4], scores f32 [n,D], labels i64 [n,D], every slot written (zeros behind an image's detections);
+    count_status i32 [2,n] -- row 0 the detections per image, row 1 the status (0, or DETPOST_OVER_CAND / DETPOST_OVER_SEG for an image
+    above a cap, whose count is 0) -- one tensor so that one copy brings both to the host; nothing synchronises here.
+    `out`: (boxes, scores, labels, count_status) buffers of the caller, `ws`: a uint8 workspace of det_postprocess_ws_bytes(...) bytes
+    (default: cached per device, stream and size).  want_candidates: `candidates` = (scores f32 [R,C-1], boxes f32 [R,C-1,4]), stage
+    A's whole table (a test hook), else None."""
+    _dev(logits, 'logits')
+    _dev(deltas, 'deltas')
+    _dev(proposals, 'proposals')
+    dev = logits.device
+    R, C, n, D = int(logits.shape[0]), int(logits.shape[1]), len(counts), int(detections_per_img)
+    assert logits.dtype == torch.float32 and logits.dim() == 2 and logits.is_contiguous()
+    assert deltas.dtype == torch.float32 and deltas.shape == (R, 4 * C) and deltas.is_contiguous() and deltas.device == dev
+    assert proposals.dtype == torch.float32 and proposals.shape == (R, 4) and proposals.is_contiguous() and proposals.device == dev
+    assert len(image_sizes) == n and len(weights) == 4
+    if not (2 <= C <= DETPOST_MAX_CLASSES and 1 <= D <= DETPOST_MAX_DET):
+        raise ValueError('det_postprocess: {} classes, {} detections per image (2..{}, 1..{})'.format(C, D, DETPOST_MAX_CLASSES, DETPOST_MAX_DET))
+    offsets = _offsets(counts)
+    flat = offsets + [int(v) for hw in image_sizes for v in hw]
+    if len(flat) != 3 * n + 1 or not all(-2 ** 31 <= v < 2 ** 31 for v in flat):
+        raise ValueError('det_postprocess: image sizes are (height, width) pairs; every offset and size fits 32 bits')
+    if out is None:
+        out = (torch.empty((n, D, 4), dtype=torch.float32, device=dev), torch.empty((n, D), dtype=torch.float32, device=dev),
+               torch.empty((n, D), dtype=torch.int64, device=dev), torch.empty((2, n), dtype=torch.int32, device=dev))
+    boxes, scores, labels, count_status = out
+    for t, dt, shape in ((boxes, torch.float32, (n, D, 4)), (scores, torch.float32, (n, D)), (labels, torch.int64, (n, D)),
+                         (count_status, torch.int32, (2, n))):
+        assert t.dtype == dt and t.shape == shape and t.is_contiguous() and t.device == dev
+    n_bytes = det_postprocess_ws_bytes(R, C, n, D)
+    if ws is None:
+        ws = _stream_workspace(_det_post_ws, _DET_POST_WS_KEPT, dev, max(n_bytes, 16))
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= n_bytes and ws.device == dev
+    cand = None
+    if want_candidates:
+        cand = (torch.empty((R, C - 1), dtype=torch.float32, device=dev), torch.empty((R, C - 1, 4), dtype=torch.float32, device=dev))
+    host = (ctypes.c_int32 * (n + 1))(*offsets)
+    both = torch.tensor(flat, dtype=torch.int32).to(dev)
+    with _timed(tag or 'det_postprocess'):
+        _check(lib().sc2_det_postprocess(_ptr(logits), _ptr(deltas), _ptr(proposals), _ptr(both[:n + 1]), host, _ptr(both[n + 1:]), R, C, n,
+                                         float(weights[0]), float(weights[1]), float(weights[2]), float(weights[3]),
+                                         float(bbox_xform_clip), float(score_thresh), float(min_size), float(nms_thresh), D,
+                                         _ptr(boxes), _ptr(scores), _ptr(labels), _ptr(count_status[0]), _ptr(count_status[1]),
+                                         _ptr(cand[0]) if cand else None, _ptr(cand[1]) if cand else None, _ptr(ws), _stream()),
+               'det_postprocess')
+    return DetPostResult(boxes, scores, labels, count_status, cand)
+
+
 # --------------------------------------------------------------------------------------------- #
 # segmentation tail: labels of the resized logits and confusion counts in one launch (csrc/seg.hip)
 # --------------------------------------------------------------------------------------------- #
@@ -1523,16 +1606,8 @@ def jpeg_image_max_bytes(C, H, W):
 
 
 def _jpeg_image_workspace(device, n_bytes):
-    """One workspace per (device, stream, size): the launches of a stream are ordered, so its next call may write where the last one
-    read.  The few most recent sizes are kept."""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream, n_bytes)
-    ws = _jpeg_image_ws.pop(key, None)
-    if ws is None:
-        ws = torch.empty((n_bytes,), dtype=torch.uint8, device=device)
-    _jpeg_image_ws[key] = ws               # (most recent last)
-    while len(_jpeg_image_ws) > _JPEG_IMAGE_WS_KEPT:
-        _jpeg_image_ws.pop(next(iter(_jpeg_image_ws)))
-    return ws
+    """One workspace per (device, stream, size); the few most recent sizes are kept (`_stream_workspace`)."""
+    return _stream_workspace(_jpeg_image_ws, _JPEG_IMAGE_WS_KEPT, device, n_bytes)
 
 
 def jpeg_image_codec(x_u8, quality, want_bytes=False, tag=None):
