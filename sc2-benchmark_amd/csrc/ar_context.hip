@@ -26,7 +26,7 @@
 // deterministic and batch invariant, and its encoder and decoder run the same step code too.
 #include <math.h>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 namespace {
 
@@ -127,8 +127,7 @@ __device__ __forceinline__ int ar_dec_status(const ArDec &d, bool last) {
     return st;
 }
 
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __builtin_bit_cast(float, w & 0xFFFF0000u); }
+using namespace sc2prim;   // gfx950_prims.h: bf_lo / bf_hi
 
 // The two weight forms.  A lane loads the weights of two adjacent outputs as ONE value: a 4-byte pair of bf16 (Wt = uint16_t) or
 // an 8-byte pair of f32 (Wt = float; N is even, so every row starts on an 8-byte boundary of an 8-byte aligned matrix).

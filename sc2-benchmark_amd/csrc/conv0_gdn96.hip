@@ -28,7 +28,7 @@
 #include <atomic>
 #include <type_traits>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 #ifndef SC2_ENC0_ROWS_EARLY
 #define SC2_ENC0_ROWS_EARLY 1
@@ -62,11 +62,7 @@ constexpr int GAM_BYTES = 6 * KS2 * 64 * 16;                        // 18 432
 constexpr int Y_Q = (2 * OW * (CH / 8) + 255) / 256;                     // output 16-byte chunks per thread (11)
 constexpr int IN_Q = (IN_ROWS * (OW + 2) + 255) / 256;              // staged 16-byte chunks per thread (4)
 
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack2(f32x2_t v) {   // one v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
+using namespace sc2prim;   // gfx950_prims.h: the bf16 pack
 
 // SEG = false: one 112-pixel segment per row (the 224-pixel-wide geometry), the unit's output is one contiguous block
 // EMIT (round 5, the training forward): the conv output t leaves too -- the tensor the GDN's backward needs.  The LDS image holds

@@ -21,7 +21,7 @@
 
 #include <type_traits>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 #ifndef SC2_NT_KRES
 #define SC2_NT_KRES 0   // non-temporal output stores: measured SLOWER here (the consumer launch finds part of this map in L2 / the memory-side cache: head + 2.5 %, dec.conv2 + 2 %); 1: A/B
@@ -29,32 +29,7 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack2(f32x2_t v) {   // one v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t r, lds_ptr_t dst, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, (int)voff, (int)soff, 0, 0);
-}
-#else   // host pass: stand-ins (see conv_igemm_impl.h)
-typedef int buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *, uint32_t) { return 0; }
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t, lds_ptr_t, uint32_t, uint32_t) {}
-#endif
-
-__device__ __forceinline__ uint4 lds_read16(uint32_t addr) {
-    uint4 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-}
+using namespace sc2prim;   // gfx950_prims.h: descriptors, direct-to-LDS loads, LDS asm, the bf16 pack
 
 struct KresArgs {
     const uint16_t *__restrict__ x;      // bf16 NHWC [N, H, W, K]

@@ -25,7 +25,7 @@
 
 #include <atomic>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 #ifndef SC2_NT_PAIR
 #define SC2_NT_PAIR 0   // non-temporal output stores: measured SLOWER here (the consumer launch finds part of this map in L2 / the memory-side cache: head + 2.5 %, dec.conv2 + 2 %); 1: A/B
@@ -33,52 +33,9 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint32_t pack2(f32x2_t v) {   // one v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
-
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t r, lds_ptr_t dst, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, (int)voff, (int)soff, 0, 0);
-}
-__device__ __forceinline__ uint4 buf_load16(buf_rsrc_t r, uint32_t voff, uint32_t soff) {
-    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-// (the wait states behind a 16-byte buffer store: see buf_store16 in conv2x2_win.hip)
-__device__ __forceinline__ void buf_store16(buf_rsrc_t r, uint32_t voff, uint32_t soff, u32x4_t v) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)voff, (int)soff, SC2_NT_PAIR ? SC2_BUF_AUX_NT : 0);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 1" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-#else   // host pass: stand-ins
-typedef int buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *, uint32_t) { return 0; }
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t, lds_ptr_t, uint32_t, uint32_t) {}
-__device__ __forceinline__ uint4 buf_load16(buf_rsrc_t, uint32_t, uint32_t) { return make_uint4(0, 0, 0, 0); }
-__device__ __forceinline__ void buf_store16(buf_rsrc_t, uint32_t, uint32_t, u32x4_t) {}
-#endif
-
-// LDS accesses the compiler must not see: hipcc knows that an LDS-DMA load writes LDS and drains vmcnt(0) in front of every LDS
-// access it can see behind one (may-alias); between issuing the next tile's identity rows and the counted wait for them, the o
-// tile is written and read through these
-template <int OFF>
-__device__ __forceinline__ u32x4_t lds_read16_imm(uint32_t addr) {
-    u32x4_t v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
-__device__ __forceinline__ void lds_write16(uint32_t addr, u32x4_t v) {
-    asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(v) : "memory");
-}
+using namespace sc2prim;   // gfx950_prims.h: descriptors, buffer access, LDS asm and their hazard notes
+// (LDS asm here: between issuing the next tile's identity rows and the counted wait for them, the o tile is written and read
+//  through lds_write16 / lds_read16_imm, which the compiler does not see)
 
 #ifndef SC2_PAIR_DBG
 #define SC2_PAIR_DBG 0   // timing experiments (results garbage): 1 = no identity loads, 2 = no output stores, 4 = no second GEMM
@@ -385,7 +342,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pair_kernel(const PairArgs p) 
 #pragma unroll
             for (int k = 0; k < IQ; ++k) {
                 const int q = tq + 512 * k;
-                buf_store16(rs_h, (q < P * CPR && m0 + q / CPR < p.M && !(SC2_PAIR_DBG & 2)) ? (uint32_t)q * 16u : OOB, so, hv[k]);
+                buf_store16<SC2_NT_PAIR>(rs_h, (q < P * CPR && m0 + q / CPR < p.M && !(SC2_PAIR_DBG & 2)) ? (uint32_t)q * 16u : OOB, so, hv[k]);
             }
         }
         {
@@ -393,7 +350,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_pair_kernel(const PairArgs p) 
 #pragma unroll
             for (int k = 0; k < UQ; ++k) {
                 const int q = tq + 512 * k;
-                buf_store16(rs_u, (q < P * UCPR && m0 + q / UCPR < p.M && !(SC2_PAIR_DBG & 2)) ? (uint32_t)q * 16u : OOB, so, uv[k]);
+                buf_store16<SC2_NT_PAIR>(rs_u, (q < P * UCPR && m0 + q / UCPR < p.M && !(SC2_PAIR_DBG & 2)) ? (uint32_t)q * 16u : OOB, so, uv[k]);
             }
         }
         tile = next_tile;

@@ -21,7 +21,7 @@
 
 #include <type_traits>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 #ifndef SC2_STREAM_EARLY
 #define SC2_STREAM_EARLY 1
@@ -47,12 +47,7 @@ struct StreamArgs {
 // Unit shapes (pixels x channels): 128 x 256 for K in {128, 256} when Cout % 256 == 0, 128 x 128 for the narrow layers,
 // 64 x 128 for K = 512 (its weights - 16 channels x 512 per wave - still fit the registers: 64 VGPRs).
 
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack2(f32x2_t v) {   // one v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
+using namespace sc2prim;   // gfx950_prims.h: vector typedefs, the bf16 pack
 
 // The tail of a unit (next unit's loads, this unit's stores) is straight-line code: addresses are clamped instead of
 // guarded, so the compiler's vmcnt bookkeeping stays exact and its wait for the loads is vmcnt(<stores issued after

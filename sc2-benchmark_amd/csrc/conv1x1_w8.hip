@@ -49,83 +49,11 @@
 // bit-equality tests of tests/test_gpu_conv1x1_w8.py (five launches behind another shape), as for conv2x2_win.hip.
 #include <stdlib.h>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint32_t pack2(float a, float b) {   // one v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){a, b}, bf16x2_t));
-}
-__device__ __forceinline__ float bf_lo(uint32_t v) { return __builtin_bit_cast(float, v << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t v) { return __builtin_bit_cast(float, v & 0xFFFF0000u); }
-
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t r, lds_ptr_t dst, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, (int)voff, (int)soff, 0, 0);
-}
-__device__ __forceinline__ uint4 buf_load16(buf_rsrc_t r, uint32_t voff, uint32_t soff) {
-    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-// (a 16-byte buffer store with an SGPR soffset reads its data registers for a few cycles after issue and hipcc's hazard recogniser
-//  exempts that form: two wait states behind every store -- conv2x2_win.hip has the full note, tools/audit_vmcnt.py --stores the check)
-__device__ __forceinline__ void buf_store16(buf_rsrc_t r, uint32_t voff, uint32_t soff, u32x4_t v) {
-    __builtin_amdgcn_raw_buffer_store_b128(v, r, (int)voff, (int)soff, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_nop 1" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-}
-#else   // host pass: stand-ins (see conv_igemm_impl.h)
-typedef int buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *, uint32_t) { return 0; }
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t, lds_ptr_t, uint32_t, uint32_t) {}
-__device__ __forceinline__ uint4 buf_load16(buf_rsrc_t, uint32_t, uint32_t) { return make_uint4(0, 0, 0, 0); }
-__device__ __forceinline__ void buf_store16(buf_rsrc_t, uint32_t, uint32_t, u32x4_t) {}
-#endif
-
-// Weight fragments: INLINE-ASM loads, hand-counted `s_waitcnt vmcnt(N)` (conv2x2_win.hip, rules (i) - (iv): a fragment register is
-// written by its load and read only by the MFMAs of its k-step behind wait_vm, which does not name the registers; the load of
-// k-step k + 4 goes into the registers of k-step k behind that step's last MFMA).
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ i32x4_t rsrc_words(const void *base, uint32_t bytes) {   // raw buffer descriptor: base, no stride, size, 32-bit raw data format
-    const uint64_t a = (uint64_t)(uintptr_t)base;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-// ("s_nop 4": the hazard recognizer does not look into inline asm; the scalar offset / descriptor may have been written by a VALU
-//  instruction just before -- hipcc restores spilled SGPRs with v_readlane_b32 -- and a VMEM instruction needs 5 wait states behind a
-//  VALU write of an SGPR it reads)
-__device__ __forceinline__ void wload16(u32x4_t &d, i32x4_t r, uint32_t voff, uint32_t soff) {   // ("; wfrag": marker for the audit)
-    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen ; wfrag" : "=&v"(d) : "v"(voff), "s"(r), "s"(soff) : "memory");
-}
-__device__ __forceinline__ void cload16(u32x4_t &d, i32x4_t r, uint32_t voff, uint32_t soff) {   // epilogue constants (wait_vm_tied)
-    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen" : "=&v"(d) : "v"(voff), "s"(r), "s"(soff) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// (epilogue constants only: consumed by vector ALU code, which nothing else orders behind the wait)
-template <int N>
-__device__ __forceinline__ void wait_vm_tied(u32x4_t &a, u32x4_t &b) {
-    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
-}
-template <int OFF>
-__device__ __forceinline__ u32x4_t lds_read16_imm(uint32_t addr) {
-    u32x4_t v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
-template <int N>
-__device__ __forceinline__ void wait_lgkm(u32x4_t &v) {
-    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N) : "memory");
-}
+using namespace sc2prim;   // gfx950_prims.h: descriptors, buffer access, the asm weight loads, counted waits (rules (i) - (iv)), LDS asm
 
 struct W8Args {
     const uint16_t *__restrict__ x;      // bf16 NHWC [N, H, W, Cin]

@@ -22,7 +22,7 @@
 
 #include <type_traits>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 #ifndef SC2_NT_WIN1
 #define SC2_NT_WIN1 0   // non-temporal output stores: measured SLOWER here (the consumer launch finds part of this map in L2 / the memory-side cache: head + 2.5 %, dec.conv2 + 2 %); 1: A/B
@@ -30,73 +30,13 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint32_t pack2(float a, float b) {   // one v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){a, b}, bf16x2_t));
-}
-__device__ __forceinline__ float bf_lo(uint32_t v) { return __builtin_bit_cast(float, v << 16); }
-__device__ __forceinline__ float bf_hi(uint32_t v) { return __builtin_bit_cast(float, v & 0xFFFF0000u); }
+using namespace sc2prim;   // gfx950_prims.h: descriptors, buffer access, the asm weight loads, counted waits, LDS asm and their hazard notes
 
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t r, lds_ptr_t dst, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, (int)voff, (int)soff, 0, 0);
-}
-__device__ __forceinline__ uint4 buf_load16(buf_rsrc_t r, uint32_t voff, uint32_t soff) {
-    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-// (masked lanes out of range instead of a branch around the store; literal soffset 0: see conv3x3_win.hip buf_store16_z)
-typedef unsigned win_u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void buf_store16_z(buf_rsrc_t r, uint32_t voff, uint4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(win_u32x4_t{v.x, v.y, v.z, v.w}, r, (int)voff, 0, SC2_NT_WIN1 ? SC2_BUF_AUX_NT : 0);
-}
-#else   // host pass: stand-ins (see conv_igemm_impl.h)
-typedef int buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *, uint32_t) { return 0; }
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t, lds_ptr_t, uint32_t, uint32_t) {}
-__device__ __forceinline__ uint4 buf_load16(buf_rsrc_t, uint32_t, uint32_t) { return make_uint4(0, 0, 0, 0); }
-__device__ __forceinline__ void buf_store16_z(buf_rsrc_t, uint32_t, uint4) {}
-#endif
-
-// Weight fragments are loaded by INLINE ASM and waited for with hand-counted `s_waitcnt vmcnt(N)` (round 4; conv2x2_win.hip has
-// the full note): with the compiler's own loads the conditional window fill in front of a slab made its scoreboard merge
+// Weight fragments are loaded by INLINE ASM and waited for with hand-counted `s_waitcnt vmcnt(N)` (round 4; gfx950_prims.h has
+// the full note and the rules): with the compiler's own loads the conditional window fill in front of a slab made its scoreboard merge
 // conservative -- the first k-step of every slab waited `vmcnt(9)` right behind eight freshly issued window pieces, i.e. for one of
-// THEM to land (tools/audit_vmcnt.py): ~a memory round trip per 50 MFMAs.  The rules that keep this safe are in conv2x2_win.hip: a fragment
-// register is read only by the MFMAs of its k-step, each of which consumes a pixel fragment that went through wait_lgkm behind
-// wait_vm; the load of k-step k + PF goes into the registers of k-step k behind that step's last MFMA.
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ i32x4_t rsrc_words(const void *base, uint32_t bytes) {   // raw buffer descriptor: base, no stride, size, 32-bit raw data format
-    const uint64_t a = (uint64_t)(uintptr_t)base;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-// ("s_nop 4": the hazard recognizer does not look into inline asm.  The scalar offset / descriptor may have been written by a
-//  VALU instruction just before -- hipcc restores spilled SGPRs with v_readlane_b32 -- and a VMEM instruction needs 5 wait states
-//  behind a VALU write of an SGPR it reads: without them the loads of the tail-mode kernel used a stale offset (wrong weights) and
-//  conv1x1_win a stale descriptor (memory fault).)
-__device__ __forceinline__ void wload16(u32x4_t &d, i32x4_t r, uint32_t voff, uint32_t soff) {
-    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen ; wfrag" : "=&v"(d) : "v"(voff), "s"(r), "s"(soff) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {   // (does not name the fragment registers: conv2x2_win.hip, rule (ii))
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <int OFF>
-__device__ __forceinline__ u32x4_t lds_read16_imm(uint32_t addr) {
-    u32x4_t v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
-template <int N>
-__device__ __forceinline__ void wait_lgkm(u32x4_t &v) {
-    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N) : "memory");
-}
+// THEM to land (tools/audit_vmcnt.py): ~a memory round trip per 50 MFMAs.
+// (output stores: masked lanes out of range instead of a branch around the store, literal soffset 0 -- buf_store16_z)
 
 struct P1Args {
     const uint16_t *__restrict__ x;      // bf16 NHWC [N, H, W, Cin]
@@ -338,7 +278,7 @@ __global__ __launch_bounds__(256, NBUF == 2 ? (T::MT == 7 ? 3 : 2) : 1) void con
                 }
             }
             const uint4 o = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
-            buf_store16_z(rs_y, m < p.M ? (uint32_t)((m * Cout + n0 + 8 * fq) * 2) : 0x80000000u, o);
+            buf_store16_z<SC2_NT_WIN1>(rs_y, m < p.M ? (uint32_t)((m * Cout + n0 + 8 * fq) * 2) : 0x80000000u, o);
         }
     };
     if (p.mask != nullptr) {

@@ -27,47 +27,17 @@
 
 #include <atomic>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t pack2(f32x2_t v) {   // one v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t));
-}
+using namespace sc2prim;   // gfx950_prims.h: descriptors, direct-to-LDS loads, lds_read16 / lds_write16, the bf16 pack
 
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t r, lds_ptr_t dst, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, (int)voff, (int)soff, 0, 0);
-}
-#else   // host pass: stand-ins (see conv_igemm_impl.h)
-typedef int buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *, uint32_t) { return 0; }
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t, lds_ptr_t, uint32_t, uint32_t) {}
-#endif
-
-__device__ __forceinline__ uint4 lds_read16(uint32_t addr) {
-    uint4 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-}
 // Round 4: EVERY LDS access of the unit loop is inline asm and every barrier a raw s_barrier.  hipcc knows that a direct-to-LDS
 // load writes LDS: in front of any LDS access it can see -- and of every __syncthreads() -- it drains vmcnt(0).  The next slab's
 // (or unit's) pieces are in flight all the time, so each such access waited for them (a loaded HBM round trip: the reduction
 // rounds took 4.5 - 7 k of a unit's 22 - 24 k cycles, tools/enc2_stamps.py) and the counted `vmcnt(3)` at a unit's first slab was
 // void.  Results of asm reads are consumed behind `lds_wait()` = s_waitcnt lgkmcnt(0) + a scheduling barrier.
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void lds_write16(uint32_t addr, uint4 v) {
-    const u32x4_t q = {v.x, v.y, v.z, v.w};
-    asm volatile("ds_write_b128 %0, %1" ::"v"(addr), "v"(q) : "memory");
-}
 __device__ __forceinline__ void lds_write8(uint32_t addr, uint2 v) {
     const u32x2_t q = {v.x, v.y};
     asm volatile("ds_write_b64 %0, %1" ::"v"(addr), "v"(q) : "memory");

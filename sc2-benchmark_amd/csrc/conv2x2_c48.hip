@@ -14,25 +14,11 @@
 //     the chip, not by the problem.
 // Same k order (kh, kw, ci), same MFMA instruction and operand roles as the tile kernel: results are bit-identical to
 // sc2_conv2d_fwd's (tests/test_gpu_kernels.py::test_conv2x2_c48).
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 namespace {
 
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ uint4 buf_load16(buf_rsrc_t r, uint32_t voff, uint32_t soff) {
-    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-#else   // host pass: stand-ins (see conv_igemm_impl.h)
-typedef int buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *, uint32_t) { return 0; }
-__device__ __forceinline__ uint4 buf_load16(buf_rsrc_t, uint32_t, uint32_t) { return make_uint4(0, 0, 0, 0); }
-#endif
+using namespace sc2prim;   // gfx950_prims.h: descriptors, buffer loads
 
 struct C48Args {
     const uint16_t *__restrict__ x;      // bf16 NHWC [N, H, W, 48]

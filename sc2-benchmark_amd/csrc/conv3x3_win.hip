@@ -23,7 +23,7 @@
 
 #include <type_traits>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 #ifndef SC2_NT_WIN3
 #define SC2_NT_WIN3 0   // non-temporal output stores: measured SLOWER here (the consumer launch finds part of this map in L2 / the memory-side cache: head + 2.5 %, dec.conv2 + 2 %); 1: A/B
@@ -31,75 +31,12 @@
 
 namespace {
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint32_t pack2(float a, float b) {   // one v_cvt_pk_bf16_f32
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector((f32x2_t){a, b}, bf16x2_t));
-}
-
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t r, lds_ptr_t dst, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, (int)voff, (int)soff, 0, 0);
-}
-__device__ __forceinline__ uint4 buf_load16(buf_rsrc_t r, uint32_t voff, uint32_t soff) {
-    return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
-}
-// 16-byte store through a descriptor, masked lanes sent out of range instead of branching around the store.  soffset is the
-// LITERAL 0: that is the form for which hipcc inserts the wait states of the ">64-bit store data" hazard itself (with an SGPR
-// soffset it does not: conv2x2_win.hip buf_store16, tools/micro/store_hazard.hip)
-typedef unsigned win_u32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void buf_store16_z(buf_rsrc_t r, uint32_t voff, uint4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(win_u32x4_t{v.x, v.y, v.z, v.w}, r, (int)voff, 0, SC2_NT_WIN3 ? SC2_BUF_AUX_NT : 0);
-}
-#else   // host pass: stand-ins (see conv_igemm_impl.h)
-typedef int buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *, uint32_t) { return 0; }
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t, lds_ptr_t, uint32_t, uint32_t) {}
-__device__ __forceinline__ uint4 buf_load16(buf_rsrc_t, uint32_t, uint32_t) { return make_uint4(0, 0, 0, 0); }
-__device__ __forceinline__ void buf_store16_z(buf_rsrc_t, uint32_t, uint4) {}
-#endif
+using namespace sc2prim;   // gfx950_prims.h: descriptors, buffer access, the asm weight loads, counted waits, LDS asm and their hazard notes
 
 // Weight fragments of the stride-1 kernel are loaded by INLINE ASM and waited for with hand-counted `s_waitcnt vmcnt(N)` (round 4;
-// conv2x2_win.hip has the full note): with the compiler's own loads the conditional window fill in front of a slab made its
-// scoreboard merge conservative, and the first k-step of every other slab waited `vmcnt(2)` = for the window pieces of the NEXT
-// slab issued a few instructions earlier (tools/audit_vmcnt.py).  The rules that keep this safe are in conv2x2_win.hip: a fragment
-// register is read only by the MFMAs of its k-step, each of which consumes a pixel fragment that went through wait_lgkm behind
-// wait_vm; the load of k-step k + PF goes into the registers of k-step k behind that step's last MFMA.
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ i32x4_t rsrc_words(const void *base, uint32_t bytes) {   // raw buffer descriptor: base, no stride, size, 32-bit raw data format
-    const uint64_t a = (uint64_t)(uintptr_t)base;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-// ("s_nop 4": the hazard recognizer does not look into inline asm.  The scalar offset / descriptor may have been written by a
-//  VALU instruction just before -- hipcc restores spilled SGPRs with v_readlane_b32 -- and a VMEM instruction needs 5 wait states
-//  behind a VALU write of an SGPR it reads: without them the loads of the tail-mode kernel used a stale offset (wrong weights) and
-//  conv1x1_win a stale descriptor (memory fault).)
-__device__ __forceinline__ void wload16(u32x4_t &d, i32x4_t r, uint32_t voff, uint32_t soff) {
-    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen ; wfrag" : "=&v"(d) : "v"(voff), "s"(r), "s"(soff) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {   // (does not name the fragment registers: conv2x2_win.hip, rule (ii))
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <int OFF>
-__device__ __forceinline__ u32x4_t lds_read16_imm(uint32_t addr) {
-    u32x4_t v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
-// wait until at most N of this wave's LDS reads are outstanding; `v` (the destination of the read being waited for) is
-// threaded through so that its consumers cannot be scheduled above the wait
-template <int N>
-__device__ __forceinline__ void wait_lgkm(u32x4_t &v) {
-    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(v) : "n"(N) : "memory");
-}
+// gfx950_prims.h has the full note and the rules): with the compiler's own loads the conditional window fill in front of a slab made
+// its scoreboard merge conservative, and the first k-step of every other slab waited `vmcnt(2)` = for the window pieces of the NEXT
+// slab issued a few instructions earlier (tools/audit_vmcnt.py).
 
 struct WinArgs {
     const uint16_t *__restrict__ x;      // bf16 NHWC [N, H, W, Cin]
@@ -381,7 +318,7 @@ __global__ __launch_bounds__(256, G::MT == 7 ? 3 : 2) void conv3x3_win_kernel(co
             }
             const uint4 o = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
             const bool ok = (ml < G::PX) & (m < M);
-            buf_store16_z(rs_y, ok ? (uint32_t)((m * Cout + n0 + 8 * fq) * 2) : 0x80000000u, o);
+            buf_store16_z<SC2_NT_WIN3>(rs_y, ok ? (uint32_t)((m * Cout + n0 + 8 * fq) * 2) : 0x80000000u, o);
         }
     };
     if constexpr (MASK_) finish(std::false_type{}, std::true_type{});
@@ -553,7 +490,7 @@ __global__ __launch_bounds__(256, G::MT == 7 ? 3 : 2) void conv3x3s2_win_kernel(
             }
             const uint4 o = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
             const bool ok = (ml < G::PX) & (m < M);
-            buf_store16_z(rs_y, ok ? (uint32_t)((m * Cout + n0 + 8 * fq) * 2) : 0x80000000u, o);
+            buf_store16_z<SC2_NT_WIN3>(rs_y, ok ? (uint32_t)((m * Cout + n0 + 8 * fq) * 2) : 0x80000000u, o);
         }
     };
     if (p.relu != 0) finish(std::true_type{});

@@ -33,14 +33,8 @@
 
 namespace sc2conv {
 
-// ds_read_b128 at addr + OFF (immediate): the fragment rows of a lane are 1 KB apart (16 tile rows x 64 B, same swizzle),
+// lds_read16_imm (gfx950_prims.h; into uint4 here): the fragment rows of a lane are 1 KB apart (16 tile rows x 64 B, same swizzle),
 // so ONE address register serves all eight pixel fragments and one the four weight fragments
-template <int OFF>
-__device__ __forceinline__ uint4 lds_read16_imm(uint32_t addr) {
-    uint4 v;
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
 
 // PIPE: the fragment reads of a phase are issued one phase EARLY, at the top of the previous phase's MFMA interval (second
 // register sets for the pixel and weight fragments), so that a wave's load interval holds only its two direct-to-LDS loads
@@ -218,22 +212,22 @@ __global__ __launch_bounds__(512, 2) void conv_igemm8p_kernel(const ConvArgs p, 
             static_assert(NT == 4, "four weight fragments per wave");
             const uint32_t a_rd0 = a_rd[0], b_rd0 = b_rd[0];   // a_rd[i] = a_rd0 + 1024 i, b_rd[j] = b_rd0 + 1024 j
             auto read_b = [&](uint32_t base, uint4 (&b)[NT]) {
-                b[0] = lds_read16_imm<0>(base + b_rd0);
-                b[1] = lds_read16_imm<1024>(base + b_rd0);
-                b[2] = lds_read16_imm<2048>(base + b_rd0);
-                b[3] = lds_read16_imm<3072>(base + b_rd0);
+                b[0] = lds_read16_imm<0, uint4>(base + b_rd0);
+                b[1] = lds_read16_imm<1024, uint4>(base + b_rd0);
+                b[2] = lds_read16_imm<2048, uint4>(base + b_rd0);
+                b[3] = lds_read16_imm<3072, uint4>(base + b_rd0);
             };
             auto read_a_lo = [&](uint32_t base, uint4 (&a)[4]) {
-                a[0] = lds_read16_imm<0>(base + a_rd0);
-                a[1] = lds_read16_imm<1024>(base + a_rd0);
-                a[2] = lds_read16_imm<2048>(base + a_rd0);
-                a[3] = lds_read16_imm<3072>(base + a_rd0);
+                a[0] = lds_read16_imm<0, uint4>(base + a_rd0);
+                a[1] = lds_read16_imm<1024, uint4>(base + a_rd0);
+                a[2] = lds_read16_imm<2048, uint4>(base + a_rd0);
+                a[3] = lds_read16_imm<3072, uint4>(base + a_rd0);
             };
             auto read_a_hi = [&](uint32_t base, uint4 (&a)[4]) {
-                a[0] = lds_read16_imm<4096>(base + a_rd0);
-                a[1] = lds_read16_imm<5120>(base + a_rd0);
-                a[2] = lds_read16_imm<6144>(base + a_rd0);
-                a[3] = lds_read16_imm<7168>(base + a_rd0);
+                a[0] = lds_read16_imm<4096, uint4>(base + a_rd0);
+                a[1] = lds_read16_imm<5120, uint4>(base + a_rd0);
+                a[2] = lds_read16_imm<6144, uint4>(base + a_rd0);
+                a[3] = lds_read16_imm<7168, uint4>(base + a_rd0);
             };
             read_b(lds_base, bvA);
             read_a_lo(lds_base, av0);
@@ -304,12 +298,12 @@ __global__ __launch_bounds__(512, 2) void conv_igemm8p_kernel(const ConvArgs p, 
                 const int nbuf = (kt + S - 1) % S;
                 uint4 bv[NT], av[MT];
                 static_assert(NT == 4 && MT == 8, "fragment counts");
-                bv[0] = lds_read16_imm<0>(sb + b_rd0); bv[1] = lds_read16_imm<1024>(sb + b_rd0);
-                bv[2] = lds_read16_imm<2048>(sb + b_rd0); bv[3] = lds_read16_imm<3072>(sb + b_rd0);
-                av[0] = lds_read16_imm<0>(sb + a_rd0); av[1] = lds_read16_imm<1024>(sb + a_rd0);
-                av[2] = lds_read16_imm<2048>(sb + a_rd0); av[3] = lds_read16_imm<3072>(sb + a_rd0);
-                av[4] = lds_read16_imm<4096>(sb + a_rd0); av[5] = lds_read16_imm<5120>(sb + a_rd0);
-                av[6] = lds_read16_imm<6144>(sb + a_rd0); av[7] = lds_read16_imm<7168>(sb + a_rd0);
+                bv[0] = lds_read16_imm<0, uint4>(sb + b_rd0); bv[1] = lds_read16_imm<1024, uint4>(sb + b_rd0);
+                bv[2] = lds_read16_imm<2048, uint4>(sb + b_rd0); bv[3] = lds_read16_imm<3072, uint4>(sb + b_rd0);
+                av[0] = lds_read16_imm<0, uint4>(sb + a_rd0); av[1] = lds_read16_imm<1024, uint4>(sb + a_rd0);
+                av[2] = lds_read16_imm<2048, uint4>(sb + a_rd0); av[3] = lds_read16_imm<3072, uint4>(sb + a_rd0);
+                av[4] = lds_read16_imm<4096, uint4>(sb + a_rd0); av[5] = lds_read16_imm<5120, uint4>(sb + a_rd0);
+                av[6] = lds_read16_imm<6144, uint4>(sb + a_rd0); av[7] = lds_read16_imm<7168, uint4>(sb + a_rd0);
                 issue_a(nbuf);
                 issue_b(kt + S - 1, nbuf);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

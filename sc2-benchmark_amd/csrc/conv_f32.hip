@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "conv_precise.h"
+#include "gfx950_prims.h"
 
 namespace {
 
@@ -43,20 +44,17 @@ struct F32Args : PreciseArgs {         // (n_steps = K_pad / 16; ep_x: with the 
     int planar;                        // with skip_j3: x is f32 NCHW [N, 3, H, W] (the reference's input layout), read in place
 };
 
+using namespace sc2prim;   // gfx950_prims.h: lds_ptr_t, lds_read16
+
 typedef f32x4_t f4_t;
 
 #ifndef SC2_F32_WAVES
 #define SC2_F32_WAVES 4  // waves per SIMD the register allocation must allow for the narrow tiles (NT * MT <= 6)
 #endif
 
-typedef __attribute__((address_space(3))) void *f32_lds_ptr_t;
 // LDS reads of the k loop are inline asm (and its barriers raw s_barrier): hipcc knows that a direct-to-LDS load writes LDS and
 // drains the vector-memory counter in front of every LDS access it can see -- the operand prefetch with it (conv2_gdn48.hip).
-__device__ __forceinline__ f4_t f32_lds_read16(uint32_t addr) {
-    f4_t v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-}
+__device__ __forceinline__ f4_t f32_lds_read16(uint32_t addr) { return __builtin_bit_cast(f4_t, lds_read16(addr)); }
 // The k loop issues its vector-memory instructions itself (asm) and counts them itself: hipcc's counter model put vmcnt(0) /
 // vmcnt(1) in front of address arithmetic that reuses a dead operand register and in front of every LDS access after a
 // direct-to-LDS load it knows about -- the two-step prefetch was gone again.  ("s_nop 4": the descriptor may have been written by
@@ -124,7 +122,7 @@ __global__ __launch_bounds__(256, (NT * MT <= 6 ? SC2_F32_WAVES : SC2_F32_WAVES1
     // loads its 16 waves keep in flight, and prefetching FURTHER ahead made the launch slower.)
     const f32_desc_t rs_x = f32_make_desc(p.x, p.x_bytes);
     const f32_desc_t rs_w = f32_make_desc(p.w, p.w_bytes);
-    const uint32_t lds_base = (uint32_t)(uintptr_t)(f32_lds_ptr_t)ktab;
+    const uint32_t lds_base = (uint32_t)(uintptr_t)(lds_ptr_t)ktab;
     const uint32_t ring = lds_base + p.ring_off;
     constexpr uint32_t GROUP_BYTES = 4u * NT * 1024u;
     const uint32_t w_chunk = (uint32_t)chunk * (uint32_t)p.n_steps * (NT * 1024u) + (uint32_t)lane * 16u;

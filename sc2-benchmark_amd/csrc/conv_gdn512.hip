@@ -23,7 +23,7 @@
 
 #include <atomic>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 #ifndef SC2_DEC_NT
 #define SC2_DEC_NT 1       // non-temporal output stores (the 822 MB map is read by the NEXT launch, from HBM / the memory-side cache either way): - 2 %
@@ -59,32 +59,9 @@ namespace {
 // The loads of step k + 3 go into the registers of step k behind that step's last MFMA (two whole steps = 64 MFMAs of this
 // wave, ~2 k cycles with its partner, between request and use); vmcnt retires in issue order, so the wait for step k is "all
 // but the 8 loads of the two steps behind it".
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-// one v_cvt_pk_bf16_f32 on an explicit (e0, e1) pair.  With scalar element-wise code the SLP vectoriser paired the wrong
-// elements ((e0, e2), (e1, e3)) and re-interleaved them with and / shift / or_sdwa / v_mov: 870 vector instructions per wave for
-// the in-place epilogue of a tile where 350 do (round 4).
-__device__ __forceinline__ uint32_t pack2(f32x2_t v) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t)); }
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ i32x4_t rsrc_words(const void *base, uint32_t bytes) {   // raw buffer descriptor: base, no stride, size, 32-bit raw data format
-    const uint64_t a = (uint64_t)(uintptr_t)base;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-// ("s_nop 4": the hazard recognizer does not look into inline asm.  The scalar offset / descriptor may have been written by a
-//  VALU instruction just before -- hipcc restores spilled SGPRs with v_readlane_b32 -- and a VMEM instruction needs 5 wait states
-//  behind a VALU write of an SGPR it reads: without them the loads of the tail-mode kernel used a stale offset (wrong weights) and
-//  conv1x1_win a stale descriptor (memory fault).)
-__device__ __forceinline__ void wload16(u32x4_t &d, i32x4_t r, uint32_t voff, uint32_t soff) {
-    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen ; wfrag" : "=&v"(d) : "v"(voff), "s"(r), "s"(soff) : "memory");
-}
-// (the wait does not name the fragment registers -- as tied operands the compiler may copy them in front of the wait, i.e.
-//  while their loads are in flight: conv2x2_win.hip, rule (ii).  The MFMAs of a step consume |t| fragments read from LDS by
-//  ordinary loads, which the "memory" clobber keeps behind the wait.)
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
+// (gfx950_prims.h: wload16 / wait_vm and the rules that go with them.  wait_vm does not name the fragment registers; the MFMAs of a
+//  step consume |t| fragments read from LDS by ordinary loads, which the "memory" clobber keeps behind the wait.)
+using namespace sc2prim;
 
 struct DecArgs {
     const uint16_t *__restrict__ x;      // bf16 NHWC [N,H,W,CIN]
@@ -112,7 +89,6 @@ __device__ __forceinline__ int img_off(int row, int c16) { return row * (CH * 2)
 // order, loads and stores alike).  The counted waits of the phase grow by the stores issued behind a step's own loads: 8, 9, 10, 10,
 // ... 10, 6, 2 (tools/audit_vmcnt.py --counts follows them).  Rows past M (the last tile) are dropped by the descriptor's range
 // check and keep their place in that order (tools/micro/oob_store_order.hip).
-typedef __amdgpu_buffer_rsrc_t buf_rsrc_t;
 
 template <int CIN, bool INVERSE, bool EMIT = false>
 __global__ __launch_bounds__(512, 2) void conv2x2_gdn512_kernel(const DecArgs p) {
@@ -270,7 +246,9 @@ __global__ __launch_bounds__(512, 2) void conv2x2_gdn512_kernel(const DecArgs p)
 #pragma unroll
         for (int h = 0; h < GR; ++h) fetch_g(h, gb[h]);
         // EMIT: chunk `lane` of row wn + 8 r of the tile's t, r = 0 .. 15 (one per k-step)
-        [[maybe_unused]] buf_rsrc_t rs_t;
+        // (the descriptor type and builtin themselves, not gfx950_prims.h's make_rsrc: its host-pass stand-in is an int, which the store
+        //  builtin below -- an SGPR-soffset store WITHOUT buf_store16's wait states, kept as it is -- does not take on the host pass)
+        [[maybe_unused]] __amdgpu_buffer_rsrc_t rs_t;
         if constexpr (EMIT) rs_t = __builtin_amdgcn_make_buffer_rsrc(p.t_out, 0, (int)((uint32_t)p.M * (uint32_t)(CH * 2)), 0x00020000);
         [[maybe_unused]] const uint32_t t_so = (uint32_t)m0 * (uint32_t)(CH * 2);
         auto emit_t = [&](int r) {

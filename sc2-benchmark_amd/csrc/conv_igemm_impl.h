@@ -32,9 +32,11 @@
 #pragma once
 #include <stdlib.h>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 namespace sc2conv {
+
+using namespace sc2prim;   // descriptors, direct-to-LDS loads, lds_read16 and the typedefs (gfx950_prims.h)
 
 // epilogues that read an activation operand x through ep_x (GDN forms: y = x * f(beta + acc); residual add)
 template <bool SQ = true>
@@ -50,8 +52,6 @@ __device__ __forceinline__ uint4 bf16x8_square(uint4 v) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const float lo = __builtin_bit_cast(float, w[t] << 16), hi = __builtin_bit_cast(float, w[t] & 0xFFFF0000u);
-        typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-        typedef float f32x2_t __attribute__((ext_vector_type(2)));
         const f32x2_t sq = {lo * lo, hi * hi};
         w[t] = __builtin_bit_cast(uint32_t, __builtin_convertvector(sq, bf16x2_t));
     }
@@ -142,33 +142,7 @@ struct Cfg {
 // land on 16 distinct 16-byte slots of the 256-byte bank row in every ds_read_b128 lane group.
 __device__ __forceinline__ int lds_off(int r, int c) { return r * 64 + ((c ^ ((r >> 1) & 3)) << 4); }
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
-
 static __device__ uint4 g_zero16;   // (one per translation unit) 16 zero bytes: the source of every out-of-image / K-tail chunk
-
-// Buffer descriptors and buffer-addressed direct-to-LDS loads.  The host pass of hipcc parses kernel bodies too and has
-// neither the type nor the builtins: it gets stand-ins (a kernel whose body fails to parse silently loses its host stub).
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(base), 0, (int)bytes, 0x00020000);
-}
-// 16 bytes per lane from base + voff + soff (voff per lane, out of range -> zeros; soff scalar) to LDS at dst + 16 * lane
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t r, lds_ptr_t dst, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, (int)voff, (int)soff, 0, 0);
-}
-#else
-typedef int buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *, uint32_t) { return 0; }
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t, lds_ptr_t, uint32_t, uint32_t) {}
-#endif
-
-__device__ __forceinline__ uint4 lds_read16(uint32_t addr) {
-    uint4 v;
-    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(addr) : "memory");
-    return v;
-}
 
 // ------------------------------------------------------------------------------------------------ store epilogue
 // Accumulator layout.  The MFMAs are issued with the WEIGHT fragment as the A operand and the activation fragment as

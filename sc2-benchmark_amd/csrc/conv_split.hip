@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "conv_precise.h"
+#include "gfx950_prims.h"
 
 namespace {
 
@@ -31,19 +32,10 @@ struct SplitArgs : PreciseArgs {        // (n_steps = ceil(K / 32))
 typedef f32x4_t sf4_t;
 typedef __attribute__((ext_vector_type(4))) unsigned su4_t;
 
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t split_rsrc_t;
-__device__ __forceinline__ split_rsrc_t split_make_rsrc(const void *base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);
+using namespace sc2prim;   // gfx950_prims.h: descriptors, buffer loads
+__device__ __forceinline__ su4_t split_buf_load16(buf_rsrc_t r, uint32_t voff) {   // out of range: zeros
+    return __builtin_bit_cast(su4_t, buf_load16(r, voff, 0u));
 }
-__device__ __forceinline__ su4_t split_buf_load16(split_rsrc_t r, uint32_t voff) {   // out of range: zeros
-    return __builtin_bit_cast(su4_t, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, 0, 0));
-}
-#else   // host pass: stand-ins
-typedef int split_rsrc_t;
-__device__ __forceinline__ split_rsrc_t split_make_rsrc(const void *, uint32_t) { return 0; }
-__device__ __forceinline__ su4_t split_buf_load16(split_rsrc_t, uint32_t) { return su4_t{0u, 0u, 0u, 0u}; }
-#endif
 
 // eight f32 values -> NS fragments of eight bf16 each, two elements at a time: one v_cvt_pk_bf16_f32 (round to nearest even)
 // makes a dword of the fragment, a shift and a mask give the two parts back as f32, two exact subtractions leave the remainders
@@ -109,8 +101,8 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(const SplitArgs p) {
             for (int nt = 0; nt < NT; ++nt) tot[mt][nt] = sf4_t{0.f, 0.f, 0.f, 0.f};
     }
 
-    const split_rsrc_t rs_x = split_make_rsrc(p.x, p.x_bytes);
-    const split_rsrc_t rs_w = split_make_rsrc(p.w, p.w_bytes);
+    const buf_rsrc_t rs_x = make_rsrc(p.x, p.x_bytes);
+    const buf_rsrc_t rs_w = make_rsrc(p.w, p.w_bytes);
     su4_t *ring = smem + (p.ring_off >> 4);
     const uint32_t w_chunk = (uint32_t)chunk * (uint32_t)n * (uint32_t)STEP_VECS;     // in vectors
     const uint32_t w_end = w_chunk + (uint32_t)n * (uint32_t)STEP_VECS;

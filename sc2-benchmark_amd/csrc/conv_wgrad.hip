@@ -23,12 +23,11 @@
 
 #include <type_traits>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-typedef const __attribute__((address_space(1))) void *gbl_ptr_t;
+using namespace sc2prim;   // gfx950_prims.h: lds_ptr_t, gbl_ptr_t
 
 __device__ uint4 g_wzero16;
 

@@ -33,7 +33,7 @@
 //   * __builtin_bit_cast(uint32_t, vec[e]) on an ext_vector element LVALUE reads element 0, whatever e is (copy the element first).
 #include <stdlib.h>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 #ifndef SC2_ROWS_GR
 #define SC2_ROWS_GR 3
@@ -41,23 +41,8 @@
 
 namespace {
 
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
+using namespace sc2prim;   // gfx950_prims.h: descriptors, direct-to-LDS loads, rsrc_words / wload16 / wait_vm ("s_nop 4": see there), the bf16 pack
 
-__device__ __forceinline__ uint32_t pack2(f32x2_t v) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t)); }
-__device__ __forceinline__ i32x4_t rsrc_words(const void *base, uint32_t bytes) {
-    const uint64_t a = (uint64_t)(uintptr_t)base;
-    return i32x4_t{(int)(uint32_t)a, (int)(uint32_t)((a >> 32) & 0xFFFFu), (int)bytes, 0x00020000};
-}
-// ("s_nop 4": a VMEM instruction needs 5 wait states behind a VALU write of an SGPR it reads, and the hazard recognizer does not
-//  look into inline asm -- conv_gdn512.hip)
-__device__ __forceinline__ void wload16(u32x4_t &d, i32x4_t r, uint32_t voff, uint32_t soff) {
-    asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, %3 offen ; wfrag" : "=&v"(d) : "v"(voff), "s"(r), "s"(soff) : "memory");
-}
 __device__ __forceinline__ void park8(u32x2_t d, i32x4_t r, uint32_t voff) {
     asm volatile("s_nop 4\n\tbuffer_store_dwordx2 %0, %1, %2, 0 offen ; park" ::"v"(d), "v"(voff), "s"(r) : "memory");
 }
@@ -70,11 +55,7 @@ __device__ __forceinline__ void store16_nt(u32x4_t d, i32x4_t r, uint32_t voff) 
 __device__ __forceinline__ void gload8(u32x2_t &d, i32x4_t r, uint32_t voff) {
     asm volatile("s_nop 4\n\tbuffer_load_dwordx2 %0, %1, %2, 0 offen ; gop" : "=&v"(d) : "v"(voff), "s"(r) : "memory");
 }
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// ... naming the eight registers of a g group: what reads them stays behind the wait
+// a counted wait naming the eight registers of a g group: what reads them stays behind the wait
 template <int N>
 __device__ __forceinline__ void wait_vm_q(u32x2_t (&q)[8]) {
     asm volatile("s_waitcnt vmcnt(%8)"
@@ -82,20 +63,6 @@ __device__ __forceinline__ void wait_vm_q(u32x2_t (&q)[8]) {
                  : "n"(N)
                  : "memory");
 }
-
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t r, lds_ptr_t dst, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, (int)voff, (int)soff, 0, 0);
-}
-#else   // host pass: stand-ins (see conv_igemm_impl.h)
-typedef int buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *, uint32_t) { return 0; }
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t, lds_ptr_t, uint32_t, uint32_t) {}
-#endif
 
 struct RowsArgs {
     const uint16_t *__restrict__ x;      // bf16 [M, 512]

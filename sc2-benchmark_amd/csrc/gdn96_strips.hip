@@ -24,34 +24,11 @@
 
 #include <type_traits>
 
-#include "sc2_common.h"
+#include "gfx950_prims.h"
 
 namespace {
 
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void *lds_ptr_t;
-
-__device__ __forceinline__ uint32_t pack2(f32x2_t v) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_t)); }
-
-#if defined(__HIP_DEVICE_COMPILE__)
-typedef __amdgpu_buffer_rsrc_t buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *base, uint32_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t *>(base), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t r, lds_ptr_t dst, uint32_t voff, uint32_t soff) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, (int)voff, (int)soff, 0, 0);
-}
-__device__ __forceinline__ void buf_store16(buf_rsrc_t r, uint32_t voff, uint4 v) {
-    typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-    __builtin_amdgcn_raw_buffer_store_b128(u32x4_t{v.x, v.y, v.z, v.w}, r, (int)voff, 0, 0);
-}
-#else   // host pass: stand-ins (see conv_igemm_impl.h)
-typedef int buf_rsrc_t;
-__device__ __forceinline__ buf_rsrc_t make_rsrc(const uint16_t *, uint32_t) { return 0; }
-__device__ __forceinline__ void buf_load_lds16(buf_rsrc_t, lds_ptr_t, uint32_t, uint32_t) {}
-__device__ __forceinline__ void buf_store16(buf_rsrc_t, uint32_t, uint4) {}
-#endif
+using namespace sc2prim;   // gfx950_prims.h: descriptors, direct-to-LDS loads, the literal-soffset store, the bf16 pack
 
 struct StripArgs {
     const uint16_t *__restrict__ x;      // bf16 [M, 96]
@@ -137,7 +114,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void gdn96_strips_kernel(const Strip
 #pragma unroll
         for (int pc = 0; pc < PIECES; ++pc) {
             const uint4 v = *reinterpret_cast<const uint4 *>(area + pc * 1024 + lane * 16);
-            buf_store16(rs, (src[pc] != OOB && prow[pc] < rows_valid) ? base + src[pc] : OOB, v);
+            buf_store16_z(rs, (src[pc] != OOB && prow[pc] < rows_valid) ? base + src[pc] : OOB, v);
         }
     };
 

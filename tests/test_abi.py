@@ -92,7 +92,8 @@ def test_asm_weight_loads_are_never_copied_in_flight():
     a spill placed between the load and the wait reads stale data (seen: a tied wait operand made hipcc copy the
     fragment IN FRONT of the wait; the forward-GDN1 variant spilled fragments across its epilogue).
     tools/audit_vmcnt.py --copies compiles the kernels to ISA and follows every marked load (`; wfrag`) through the
-    control-flow graph to its first MFMA: nothing else may read the register on the way."""
+    control-flow graph to its first MFMA: nothing else may read the register on the way.  The loads, the waits and the rules
+    they are written to are in csrc/gfx950_prims.h."""
     import os
     import subprocess
     import sys
@@ -105,7 +106,7 @@ def test_asm_weight_loads_are_never_copied_in_flight():
     r = subprocess.run([sys.executable, os.path.join(root, 'tools', 'audit_vmcnt.py'), '--copies'] + files, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     # the second hazard the compiler does not cover: a 16-byte buffer store with an SGPR soffset directly followed by a VALU write
-    # of its data registers (tools/micro/store_hazard.hip; the kernels' buf_store16 carries the wait states)
+    # of its data registers (tools/micro/store_hazard.hip; buf_store16 of csrc/gfx950_prims.h carries the wait states)
     stores = [os.path.join(csrc, f) for f in ('conv2x2_win.hip', 'conv1x1_pair.hip', 'conv3x3_win.hip', 'conv1x1_win.hip', 'gdn512_rows.hip')]
     r2 = subprocess.run([sys.executable, os.path.join(root, 'tools', 'audit_vmcnt.py'), '--stores'] + stores, capture_output=True, text=True)
     assert r2.returncode == 0 and r2.stdout.count(': ok') == len(stores), r2.stdout + r2.stderr

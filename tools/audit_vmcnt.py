@@ -17,7 +17,7 @@ not wait for it -- the class of commit 9bc486e, which --copies cannot see becaus
 --copies: the second hazard of hand-counted waits.  A register written by an inline-asm `buffer_load_dwordx4` / `global_load_dwordx4` (between
 ;;#ASMSTART / ;;#ASMEND) holds its value only once the load has landed, which the compiler does not know: any instruction
 other than an MFMA that READS such a register (a v_mov the register allocator placed to satisfy a tied operand or a phi)
-may copy it while the load is in flight.  The kernels mark their weight-fragment loads with the asm comment `; wfrag`; the
+may copy it while the load is in flight (csrc/gfx950_prims.h states the rules).  Its `wload16` marks the weight-fragment loads with the asm comment `; wfrag`; the
 check walks each kernel's listing in layout order, keeps a register 'hot' from a marked load until some other instruction
 writes it, and reports every instruction but a v_mfma that reads a hot register.
 
@@ -27,7 +27,7 @@ statement per operand register behind the s_waitcnt) takes those registers off t
 --stores: `buffer_store_dwordx3/x4 vData, vOff, rsrc, sN` (SGPR soffset) directly followed by a VALU write of one of its data
 registers.  hipcc's hazard recogniser exempts this form from the ">64-bit store data" hazard; gfx950 has the hazard all the same
 (tools/micro/store_hazard.hip, profiles/r04_store_hazard.txt).  The kernels that store this way put wait states behind every
-store (`buf_store16`); this mode checks the listing for any such store the compiler left unprotected.
+store (`buf_store16` of csrc/gfx950_prims.h, which has the note); this mode checks the listing for any such store the compiler left unprotected.
 """
 import re
 import sys
