@@ -950,6 +950,48 @@ int sc2_det_postprocess(const float *logits, const float *deltas, const float *p
                         float score_thresh, float min_size, float nms_thresh, int D, float *boxes, float *scores, int64_t *labels,
                         int32_t *count, int32_t *status, float *cand_scores, float *cand_boxes, void *ws, void *stream);
 
+#define SC2_RPNPOST_MAX_LEVELS 8          /* L */
+#define SC2_RPNPOST_MAX_PRE_NMS 2048      /* K = pre-NMS top-n per level: one level's selection is sorted and suppressed in LDS (training runs 2 000) */
+#define SC2_RPNPOST_MAX_POST_NMS 2048     /* P = post-NMS top-n per image */
+#define SC2_RPNPOST_MAX_KEYS 16384        /* sum over the levels of min(K, n_l): an image's kept keys are merged in one workgroup's LDS (128 KiB) */
+#define SC2_RPNPOST_MAX_ANCHORS 536870912 /* T, the anchors of one image, stays BELOW this (2^31 / 4) */
+/* torchvision's `RegionProposalNetwork.filter_proposals`, with the decode of the boxes it keeps, for a batch (csrc/rpn_post.hip;
+ * tests/ref_rpn_post.py restates it).  The RPN head's outputs are read in place: no permute, no concat, no decode of all anchors.
+ * objectness, deltas: HOST arrays of L device pointers: level l's objectness map f32 [N, A_l, H_l, W_l] and delta map
+ * f32 [N, 4 A_l, H_l, W_l] (channel 4 a + c), NCHW and contiguous; num_anchors, heights, widths: HOST arrays of A_l, H_l, W_l (>= 1).
+ * Level l has n_l = A_l H_l W_l anchors, index t = (h W_l + w) A_l + a within the level (the order of
+ * `concat_box_prediction_layers` and of `AnchorGenerator`); anchors: f32 [T,4] of ONE image, T = sum n_l, level l starting at
+ * n_0 + .. + n_(l-1); image_sizes: i32 [N,2] (height, width) on the device.
+ * Caps, checked on the host before anything is launched: 1 <= L <= SC2_RPNPOST_MAX_LEVELS, 1 <= K <= SC2_RPNPOST_MAX_PRE_NMS,
+ * 1 <= P <= SC2_RPNPOST_MAX_POST_NMS, sum_l min(K, n_l) <= SC2_RPNPOST_MAX_KEYS, T < SC2_RPNPOST_MAX_ANCHORS (SC2_ERR_UNSUPPORTED
+ * otherwise); N <= 65535, no threshold NaN, every pointer 16-byte aligned (SC2_ERR_INVALID_ARG otherwise).  The counts are bounded
+ * by K: there is no data-dependent overflow and no status word.
+ * 1. Selection, per (image, level): the k_l = min(K, n_l) anchors greatest by logit, the logits compared as floats -- -0 equals +0,
+ *    every NaN ranks above every number (and equals every other NaN) -- and of equal logits the LOWER index t first.  An anchor's
+ *    RANK is its place in that order.  (torch.topk leaves ties unspecified; this entry specifies them.)
+ * 2. Per selected anchor, in f32 with every operation rounded once: score = 1 / (1 + exp(-logit)); the box is
+ *    BoxCoder.decode_single of (anchor, the four deltas) followed by the clip to the image, as sc2_det_postprocess states it.
+ * 3. It survives iff x2' - x1' >= min_size and y2' - y1' >= min_size and score >= score_thresh (all inclusive: the RPN's rule); a
+ *    comparison with a NaN is false.
+ * 4. Per image, the survivors in order of (score descending, level ascending, rank ascending) -- the stable sort of `batched_nms`
+ *    over the levels' concatenation; greedy NMS within each level in that order with sc2_nms's IoU and test (IoU > nms_thresh, the
+ *    earlier box kept).
+ * 5. The kept boxes of all levels in that order, the first P: boxes f32 [N,P,4], scores f32 [N,P], count i32 [N].  EVERY element
+ *    is written exactly once: slots at or behind count[i] hold zeros.
+ * cand_index i32 [N,L,K], cand_scores f32 [N,L,K], cand_boxes f32 [N,L,K,4], cand_k i32 [N,L]: all NULL in production; a test passes
+ * all four and receives the candidate table of steps 1 and 2 -- slot j < k_l of (image, level): the level-local index, score and
+ * clipped box of rank j; slots behind k_l: index -1, zeros; cand_k: k_l -- which steps 3 to 5 then read in place of the workspace's.
+ * Three launches on `stream` whatever N is ((level, image): radix select over LDS histograms, ordered pick of the ties, sort,
+ * decode; (level, image): sort and greedy walk in LDS; one merge per image), none when N == 0; nothing is copied to the host, no
+ * atomics on global memory: the same bits each call.
+ * ws: sc2_rpn_proposals_ws_bytes(N, L, K, P) bytes, 16-byte aligned (0 for dimensions outside the ranges above). */
+long long sc2_rpn_proposals_ws_bytes(int N, int L, int K, int P);
+int sc2_rpn_proposals(const float *const *objectness, const float *const *deltas, const int32_t *num_anchors, const int32_t *heights,
+                      const int32_t *widths, int L, const float *anchors, const int32_t *image_sizes, int N, int K, int P, float nms_thresh,
+                      float score_thresh, float min_size, float wx, float wy, float ww, float wh, float bbox_xform_clip, float *boxes,
+                      float *scores, int32_t *count, int32_t *cand_index, float *cand_scores, float *cand_boxes, int32_t *cand_k, void *ws,
+                      void *stream);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Segmentation tail (csrc/seg.hip): low-resolution class logits -> labels of the resized map and confusion counts, */
 /* one launch.  tests/ref_seg.py restates it in float64.                                                            */

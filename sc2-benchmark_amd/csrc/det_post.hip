@@ -39,16 +39,10 @@ struct DetPostArgs {
     float wx, wy, ww, wh, clip, score_thresh, min_size, nms_thresh;
 };
 
-// torch.clamp's semantics (a NaN stays a NaN: both comparisons are false)
-__device__ __forceinline__ float clamp_max(float v, float hi) { return v > hi ? hi : v; }
-__device__ __forceinline__ float clamp_box(float v, float hi) { return v < 0.0f ? 0.0f : (v > hi ? hi : v); }
-
 // 64-bit key of a survivor: greater = earlier.  High word: the score's bits mapped so that unsigned order is the floats' order;
 // low word: the complement of the flat index r_local * (C-1) + (c-1), so that of two equal scores the LOWER index is greater.
 __device__ __forceinline__ unsigned long long cand_key(float score, unsigned flat) {
-    const unsigned u = __builtin_bit_cast(unsigned, score);
-    const unsigned ord = u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-    return ((unsigned long long)ord << 32) | (0xFFFFFFFFu - flat);
+    return ((unsigned long long)float_order_bits(score) << 32) | (0xFFFFFFFFu - flat);
 }
 __device__ __forceinline__ unsigned key_flat(unsigned long long k) { return 0xFFFFFFFFu - (unsigned)k; }
 
@@ -84,8 +78,7 @@ __global__ __launch_bounds__(DP_THREADS) void detpost_rows_kernel(const DetPostA
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) s = s + __shfl_xor(s, d, 64);
     const float4 p = a.proposals[r];
-    const float widths = p.z - p.x, heights = p.w - p.y;
-    const float ctr_x = p.x + 0.5f * widths, ctr_y = p.y + 0.5f * heights;
+    const float4 weights = make_float4(a.wx, a.wy, a.ww, a.wh);
     bool pass[2];
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -94,15 +87,7 @@ __global__ __launch_bounds__(DP_THREADS) void detpost_rows_kernel(const DetPostA
         if (c < 1 || c >= C) continue;
         const float score = (h ? e1 : e0) / s;
         const float4 dl = *reinterpret_cast<const float4 *>(a.deltas + ((size_t)r * C + c) * 4);
-        const float dx = dl.x / a.wx, dy = dl.y / a.wy;
-        const float dw = clamp_max(dl.z / a.ww, a.clip), dh = clamp_max(dl.w / a.wh, a.clip);
-        const float pcx = dx * widths + ctr_x, pcy = dy * heights + ctr_y;
-        const float half_w = 0.5f * (expf(dw) * widths), half_h = 0.5f * (expf(dh) * heights);
-        float4 b;
-        b.x = clamp_box(pcx - half_w, img_w);
-        b.y = clamp_box(pcy - half_h, img_h);
-        b.z = clamp_box(pcx + half_w, img_w);
-        b.w = clamp_box(pcy + half_h, img_h);
+        const float4 b = decode_clip_box(p, dl, weights, a.clip, img_w, img_h);
         const size_t at = (size_t)r * nc + (c - 1);
         a.cand_scores[at] = score;
         a.cand_boxes[at] = b;

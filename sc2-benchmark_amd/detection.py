@@ -13,8 +13,12 @@ torch-op implementation of the same definitions (include/sc2_bottleneck.h states
 them independently).  The RoI heads' `postprocess_detections` runs for the whole batch on csrc/det_post.hip (`hip.det_postprocess`:
 softmax, decode, clip, the two filters, per-class NMS and the first `detections_per_img`, three launches and one read-back) for f32
 device tensors while `hip.host_policy.det_post_hip` is on; otherwise, and for a batch above that kernel's candidate caps, the
-per-image loop of torch ops around `batched_nms` (tests/ref_det_post.py restates the stage).  Everything else is small tensor
-algebra and two small GEMM stacks on torch ops.
+per-image loop of torch ops around `batched_nms` (tests/ref_det_post.py restates the stage).  The RPN's proposal selection runs
+the same way on csrc/rpn_post.hip (`hip.rpn_proposals`: the top-k of each level with ties by the lower index, sigmoid, decode and
+clip of the selected anchors, per-level NMS and the first `post_nms_top_n`, three launches on the head's maps as they stand and
+one read-back) for f32 device maps while `hip.host_policy.rpn_post_hip` is on; otherwise, and outside that kernel's caps, concat,
+full decode and `filter_proposals` (tests/ref_rpn_post.py restates the stage).  Everything else is small tensor algebra and two
+small GEMM stacks on torch ops.
 
 `RCNNTransformWithCompression` (sc2bench/models/detection/transform.py) is the transform of the input-compression baseline: a
 codec between resize and normalise; for plain JPEG on device images it runs on csrc/rcnn_input.hip + csrc/jpeg_image.hip.
@@ -581,6 +585,31 @@ class RegionProposalNetwork(nn.Module):
             final_scores.append(scores[keep])
         return final_boxes, final_scores
 
+    def _proposals_on_kernel(self, objectness, pred_bbox_deltas, anchors, image_shapes):
+        """The whole batch on `hip.rpn_proposals` (three launches on the head's per-level outputs as they stand -- no concat, no
+        decode of every anchor -- and one read-back of the counts) -> the per-image list of proposals, or None where that path does
+        not apply: CPU tensors, `hip.host_policy.rpn_post_hip` or `nms_hip` off, another dtype than f32, an anchor generator other
+        than this module's `AnchorGenerator` (whose images share one anchor set by construction), or dimensions outside the
+        kernel's caps.  The caller then runs `filter_proposals`."""
+        if not (len(objectness) > 0 and objectness[0].is_cuda and hip.host_policy.rpn_post_hip and hip.host_policy.nms_hip):     # (nms_hip off: the tail on torch ops, A/B)
+            return None
+        if type(self.anchor_generator) is not AnchorGenerator or len(anchors) == 0 or len(anchors) != len(image_shapes):
+            return None
+        maps = list(objectness) + list(pred_bbox_deltas)
+        if len(objectness) != len(pred_bbox_deltas) or any(t.dtype != torch.float32 or t.device != maps[0].device for t in maps + [anchors[0]]):
+            return None
+        if any(t.dim() != 4 for t in maps) or anchors[0].dim() != 2:
+            return None
+        N, K, P = len(anchors), int(self.pre_nms_top_n()), int(self.post_nms_top_n())
+        shapes = [tuple(int(v) for v in o.shape[1:]) for o in objectness]
+        if (any(int(o.shape[0]) != N or tuple(d.shape) != (N, 4 * s[0], s[1], s[2]) for o, d, s in zip(objectness, pred_bbox_deltas, shapes))
+                or not hip.rpn_proposals_in_range(shapes, N, K, P) or int(anchors[0].shape[0]) != sum(a * h * w for a, h, w in shapes)):
+            return None
+        res = hip.rpn_proposals([o.detach().contiguous() for o in objectness], [d.detach().contiguous() for d in pred_bbox_deltas],
+                                anchors[0].contiguous(), [(int(h), int(w)) for h, w in image_shapes], K, P, self.nms_thresh,
+                                self.score_thresh, self.min_size, self.box_coder.weights, self.box_coder.bbox_xform_clip)
+        return [res.boxes[i, :k] for i, k in enumerate(res.count.cpu().tolist())]
+
     def assign_targets_to_anchors(self, anchors, targets):
         """-> (labels f32 [A] per image: 1 matched, 0 background, -1 between the thresholds; the matched gt box of every anchor).
         Thresholds fg / bg (0.7 / 0.3) with low-quality matches on; an image without gt boxes: all-zero labels and boxes."""
@@ -622,9 +651,12 @@ class RegionProposalNetwork(nn.Module):
         anchors = self.anchor_generator(images, features)
         num_images = len(anchors)
         num_anchors_per_level = [o[0].numel() for o in objectness]
-        objectness, pred_bbox_deltas = concat_box_prediction_layers(objectness, pred_bbox_deltas)
-        proposals = self.box_coder.decode(pred_bbox_deltas.detach().float(), anchors).view(num_images, -1, 4)
-        boxes, _ = self.filter_proposals(proposals, objectness.float(), images.image_sizes, num_anchors_per_level)
+        boxes = self._proposals_on_kernel(objectness, pred_bbox_deltas, anchors, images.image_sizes)
+        if boxes is None or self.training:       # (the loss reads the concatenation)
+            objectness, pred_bbox_deltas = concat_box_prediction_layers(objectness, pred_bbox_deltas)
+        if boxes is None:
+            proposals = self.box_coder.decode(pred_bbox_deltas.detach().float(), anchors).view(num_images, -1, 4)
+            boxes, _ = self.filter_proposals(proposals, objectness.float(), images.image_sizes, num_anchors_per_level)
         losses = {}
         if self.training:
             labels, matched_gt_boxes = self.assign_targets_to_anchors(anchors, targets)

@@ -40,7 +40,7 @@ ABI_SYMBOLS = [
     'sc2_gdn_bwd_pre_blocks', 'sc2_colsum_blocks', 'sc2_gdn_bwd_post_blocks', 'sc2_layout_blocks', 'sc2_gdn1_rows_units', 'sc2_gdn1_rows_workgroups',
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
     'sc2_bq_partial_len', 'sc2_bq_quantize', 'sc2_bq_dequantize', 'sc2_bq_dequantize_nhwc', 'sc2_maxpool_affine_relu_nhwc', 'sc2_avgpool2d_nhwc',
-    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_roi_align_backward', 'sc2_box_match_ws_bytes', 'sc2_box_match', 'sc2_det_postprocess_ws_bytes', 'sc2_det_postprocess', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_seg_augment_workspace', 'sc2_seg_augment', 'sc2_cls_input_workspace', 'sc2_cls_input', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
+    'sc2_nms_ws_bytes', 'sc2_nms', 'sc2_roi_align', 'sc2_roi_align_backward', 'sc2_box_match_ws_bytes', 'sc2_box_match', 'sc2_det_postprocess_ws_bytes', 'sc2_det_postprocess', 'sc2_rpn_proposals_ws_bytes', 'sc2_rpn_proposals', 'sc2_seg_predict', 'sc2_seg_ce_ws_bytes', 'sc2_seg_ce_forward', 'sc2_seg_ce_backward', 'sc2_seg_augment_workspace', 'sc2_seg_augment', 'sc2_cls_input_workspace', 'sc2_cls_input', 'sc2_coco_match_ws_bytes', 'sc2_coco_match', 'sc2_coco_accumulate',
     'sc2_jpeg_max_bytes', 'sc2_jpeg_tensor_codec', 'sc2_jpeg_image_max_bytes', 'sc2_jpeg_image_workspace_bytes', 'sc2_jpeg_image_codec',
     'sc2_rcnn_resize_u8', 'sc2_rcnn_normalize_pad', 'sc2_det_input',
     'sc2_rans_host_tables_create', 'sc2_rans_host_tables_destroy', 'sc2_rans_host_rcp_div', 'sc2_rans_code_host', 'sc2_clock_probe', 'sc2_rans_encode_host', 'sc2_rans_decode_host',
@@ -72,6 +72,8 @@ MATCH_CAND_PER_WG, MATCH_GT_TILE = 1024, 64     # ... per workgroup of its secon
 DETPOST_MAX_CLASSES, DETPOST_MAX_DET = 128, 1024      # SC2_DETPOST_*: C (background included) and detections per image
 DETPOST_MAX_SEG, DETPOST_MAX_CAND = 2048, 20480       # survivors of one class of an image / of an image
 DETPOST_OVER_CAND, DETPOST_OVER_SEG = 1, 2            # status bits
+RPNPOST_MAX_LEVELS, RPNPOST_MAX_PRE_NMS, RPNPOST_MAX_POST_NMS = 8, 2048, 2048     # SC2_RPNPOST_*: L, K (pre-NMS top-n per level), P (post-NMS top-n)
+RPNPOST_MAX_KEYS, RPNPOST_MAX_ANCHORS = 16384, 2 ** 29     # sum over the levels of min(K, n_l) / the anchors of an image stay below this
 SEG_MAX_CLASSES = 64       # SC2_SEG_MAX_CLASSES
 SEG_CE_MEAN, SEG_CE_SUM, SEG_CE_NONE = 0, 1, 2     # SC2_SEG_CE_*
 COCO_THRS, COCO_RECS, COCO_AREAS, COCO_MAXDETS = 10, 101, 4, 3     # SC2_COCO_*
@@ -165,6 +167,7 @@ class HostPolicy(object):
     box_match_hip = True       # detection.match_boxes (the RPN's and the RoI heads' target assignment in training) of device tensors on sc2_box_match (False: the [G, A] `box_iou` matrix + `Matcher` on torch ops, A/B; tools/det_train_times.py, 6 images x 242 991 anchors x 20 gt boxes, 0.3 / 0.7 with low-quality matches: 0.17 against 2.41 ms, identical matches)
     roi_align_bwd_hip = True   # the backward of detection.multiscale_roi_align of f32 device maps on sc2_roi_align_backward (False: autograd through the torch-op restatement, forward included, A/B; tools/det_train_times.py, 3 072 RoIs over four maps of 6 images, C = 256, P = 7, S = 2: forward + backward 2.03 against 137.1 ms, the backward launch with its binning 1.64 ms)
     det_post_hip = True        # detection.RoIHeads.postprocess_detections of f32 device tensors on sc2_det_postprocess: three launches and one read-back per batch (False, or nms_hip off: softmax + decode, then the per-image loop of torch ops around batched_nms, A/B; a batch above the kernel's candidate caps takes that loop too; tools/det_post_times.py, 6 images x 1 000 proposals x 91 classes with 300 - 390 candidates per image above 0.05: 0.196 against 2.271 ms per batch, medians of 7 alternating rounds, the three launches alone 0.095 ms)
+    rpn_post_hip = True        # detection.RegionProposalNetwork.forward of f32 device maps on sc2_rpn_proposals: three launches on the head's per-level maps as they stand and one read-back of the counts per batch (False, or nms_hip off: concat, decode of every anchor, topk per level, then filter_proposals' per-image loop of torch ops around batched_nms, A/B; other anchor generators and dimensions outside the kernel's caps take that path too; tools/rpn_post_times.py, 6 images x 242 991 anchors, all P proposals kept per image: 1.752 against 6.217 ms per batch at top-n 1 000, 2.884 against 11.254 ms at 2 000, medians of 7 alternating rounds, the three launches alone 1.264 / 2.349 ms; on by default: the whole existing GPU suite passes with it, the bit-identity of tests/test_gpu_detection.py's tail included)
     coco_eval_hip = True       # coco_eval.CocoBoxEvaluator.accumulate of device tensors on sc2_coco_match + sc2_coco_accumulate (False: the torch / numpy host path of the same module; tools/coco_eval_times.py)
     jpeg_codec_hip = True      # transforms.PILTensorModule(format='JPEG') of f32 device tensors up to 64 x 64 on sc2_jpeg_tensor_codec (False: PIL per channel group on the host, A/B; tools/jpeg_codec_times.py: 0.36 against 42.7 ms at [1,512,28,28])
     jpeg_image_hip = True      # transforms.PILImageModule(format='JPEG').forward_batch of equal-size RGB / grey PIL images up to 2048 x 2048 on sc2_jpeg_image_codec (False: PIL per image on the host, A/B; tools/jpeg_image_times.py, codec + ToTensor + Normalize to the classifier input: 0.39 against 0.50 ms at [1,3,224,224], 10.4 against 174 ms at [256,3,224,224])
@@ -357,6 +360,9 @@ def lib():
     L.sc2_det_postprocess_ws_bytes.argtypes = [i32, i32, i32, i32]
     L.sc2_det_postprocess_ws_bytes.restype = i64
     L.sc2_det_postprocess.argtypes = [vp] * 6 + [i32] * 3 + [f32] * 8 + [i32] + [vp] * 9
+    L.sc2_rpn_proposals_ws_bytes.argtypes = [i32, i32, i32, i32]
+    L.sc2_rpn_proposals_ws_bytes.restype = i64
+    L.sc2_rpn_proposals.argtypes = [vp] * 5 + [i32] + [vp] * 2 + [i32] * 3 + [f32] * 8 + [vp] * 9
     L.sc2_seg_predict.argtypes = [vp, i32, i32, i32, i32, i32, i64, i64, i64, i64, i32, i32, i32, vp, vp, vp, vp]
     L.sc2_seg_ce_ws_bytes.argtypes = [i32, i32, i32]
     L.sc2_seg_ce_ws_bytes.restype = i64
@@ -1438,6 +1444,88 @@ def det_postprocess(logits, deltas, proposals, counts, image_sizes, weights, bbo
                                          _ptr(cand[0]) if cand else None, _ptr(cand[1]) if cand else None, _ptr(ws), _stream()),
                'det_postprocess')
     return DetPostResult(boxes, scores, labels, count_status, cand)
+
+
+RpnPostResult = collections.namedtuple('RpnPostResult', ['boxes', 'scores', 'count', 'candidates'])
+_rpn_post_ws = dict()          # (device index, stream, bytes) -> the workspace of sc2_rpn_proposals
+_RPN_POST_WS_KEPT = 4
+
+
+def rpn_proposals_ws_bytes(N, L, K, P):
+    """Bytes of sc2_rpn_proposals's workspace (0: dimensions outside the kernel's range)."""
+    return int(lib().sc2_rpn_proposals_ws_bytes(int(N), int(L), int(K), int(P)))
+
+
+def rpn_proposals_in_range(level_shapes, N, K, P):
+    """Whether sc2_rpn_proposals takes these dimensions: level_shapes = [(A_l, H_l, W_l)], N images, K / P the pre- / post-NMS top-n."""
+    counts = [int(a) * int(h) * int(w) for a, h, w in level_shapes]
+    return (1 <= len(counts) <= RPNPOST_MAX_LEVELS and all(c >= 1 for c in counts) and 0 <= N <= 65535 and 1 <= K <= RPNPOST_MAX_PRE_NMS
+            and 1 <= P <= RPNPOST_MAX_POST_NMS and sum(min(K, c) for c in counts) <= RPNPOST_MAX_KEYS and sum(counts) < RPNPOST_MAX_ANCHORS)
+
+
+def rpn_proposals(objectness_levels, delta_levels, anchors, image_sizes, K, P, nms_thresh, score_thresh, min_size, weights, clip,
+                  out=None, ws=None, want_candidates=False, tag=None):
+    """torchvision's `RegionProposalNetwork.filter_proposals`, with the decode of the anchors it selects, for a batch in three
+    launches (include/sc2_bottleneck.h: sc2_rpn_proposals).  objectness_levels / delta_levels: the RPN head's outputs, per level
+    f32 [N,A_l,H_l,W_l] / [N,4 A_l,H_l,W_l], contiguous on the device and read in place; anchors: f32 [T,4], the anchors of ONE
+    image in `AnchorGenerator`'s order; image_sizes: (height, width) per image, as Python ints; K / P: the pre-NMS top-n per level /
+    the post-NMS top-n; weights: BoxCoder's four, clip: its bbox_xform_clip.  Dimensions outside `rpn_proposals_in_range` raise
+    ValueError: there is no other path in this module.
+    -> RpnPostResult: boxes f32 [N,P,4], scores f32 [N,P], every slot written (zeros behind an image's proposals), count i32 [N];
+    nothing synchronises here.  `out`: (boxes, scores, count) buffers of the caller, `ws`: a uint8 workspace of
+    rpn_proposals_ws_bytes(N, L, K, P) bytes (default: cached per device, stream and size).  want_candidates: `candidates` =
+    (index i32 [N,L,K], scores f32 [N,L,K], boxes f32 [N,L,K,4], k i32 [N,L]), the table of the selection by rank (a test hook),
+    else None."""
+    L, N, K, P = len(objectness_levels), len(image_sizes), int(K), int(P)
+    assert len(delta_levels) == L and len(weights) == 4
+    if L < 1:
+        raise ValueError('rpn_proposals: no level')
+    _dev(anchors, 'anchors')
+    dev = anchors.device
+    shapes = []
+    for o, d in zip(objectness_levels, delta_levels):
+        _dev(o, 'objectness')
+        _dev(d, 'deltas')
+        assert o.dtype == torch.float32 and o.dim() == 4 and o.is_contiguous() and o.device == dev and int(o.shape[0]) == N
+        A, H, W = (int(v) for v in o.shape[1:])
+        assert d.dtype == torch.float32 and d.shape == (N, 4 * A, H, W) and d.is_contiguous() and d.device == dev
+        shapes.append((A, H, W))
+    if not rpn_proposals_in_range(shapes, N, K, P):
+        raise ValueError('rpn_proposals: levels {}, {} images, top-n {} / {} outside the kernel\'s range (at most {} levels, {} / {}, '
+                         '{} selected anchors per image)'.format(shapes, N, K, P, RPNPOST_MAX_LEVELS, RPNPOST_MAX_PRE_NMS,
+                                                                 RPNPOST_MAX_POST_NMS, RPNPOST_MAX_KEYS))
+    T = sum(a * h * w for a, h, w in shapes)
+    assert anchors.dtype == torch.float32 and anchors.shape == (T, 4) and anchors.is_contiguous()
+    flat = [int(v) for hw in image_sizes for v in hw]
+    if len(flat) != 2 * N or not all(-2 ** 31 <= v < 2 ** 31 for v in flat):
+        raise ValueError('rpn_proposals: image sizes are (height, width) pairs that fit 32 bits')
+    if out is None:
+        out = (torch.empty((N, P, 4), dtype=torch.float32, device=dev), torch.empty((N, P), dtype=torch.float32, device=dev),
+               torch.empty((N,), dtype=torch.int32, device=dev))
+    boxes, scores, count = out
+    for t, dt, shape in ((boxes, torch.float32, (N, P, 4)), (scores, torch.float32, (N, P)), (count, torch.int32, (N,))):
+        assert t.dtype == dt and t.shape == shape and t.is_contiguous() and t.device == dev
+    n_bytes = rpn_proposals_ws_bytes(N, L, K, P)
+    if ws is None:
+        ws = _stream_workspace(_rpn_post_ws, _RPN_POST_WS_KEPT, dev, max(n_bytes, 16))
+    assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= n_bytes and ws.device == dev
+    cand = None
+    if want_candidates:
+        cand = (torch.empty((N, L, K), dtype=torch.int32, device=dev), torch.empty((N, L, K), dtype=torch.float32, device=dev),
+                torch.empty((N, L, K, 4), dtype=torch.float32, device=dev), torch.empty((N, L), dtype=torch.int32, device=dev))
+    if N == 0:
+        return RpnPostResult(boxes, scores, count, cand)
+    obj_ptrs = (ctypes.c_void_p * L)(*[int(o.data_ptr()) for o in objectness_levels])
+    del_ptrs = (ctypes.c_void_p * L)(*[int(d.data_ptr()) for d in delta_levels])
+    dims = [(ctypes.c_int32 * L)(*[s[q] for s in shapes]) for q in range(3)]
+    sizes = torch.tensor(flat, dtype=torch.int32).to(dev)
+    hook = [_ptr(c) for c in cand] if cand else [None] * 4
+    with _timed(tag or 'rpn_proposals'):
+        _check(lib().sc2_rpn_proposals(obj_ptrs, del_ptrs, dims[0], dims[1], dims[2], L, _ptr(anchors), _ptr(sizes), N, K, P,
+                                       float(nms_thresh), float(score_thresh), float(min_size), float(weights[0]), float(weights[1]),
+                                       float(weights[2]), float(weights[3]), float(clip), _ptr(boxes), _ptr(scores), _ptr(count),
+                                       hook[0], hook[1], hook[2], hook[3], _ptr(ws), _stream()), 'rpn_proposals')
+    return RpnPostResult(boxes, scores, count, cand)
 
 
 # --------------------------------------------------------------------------------------------- #
