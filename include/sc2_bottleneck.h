@@ -690,6 +690,33 @@ int sc2_rans_decode_dequantize_batch_ev(const uint8_t *in, int64_t in_stride, co
                                         int32_t *symbols_out, void *y_hat_bf16_nhwc, int32_t *status, void *workspace,
                                         int64_t workspace_bytes, void *stream, void *ev_dequantize_begin, void *ev_dequantize_end);
 
+/* Which kernels a decode call of these sizes runs under the policy in force: the decision the decode entry points themselves
+ * switch on (one host function, no launch, no device needed), exported so that a test knows which decoder its case reached.
+ * explicit_indexes: the call passes `indexes`; fused_dq: it is sc2_rans_decode_dequantize_batch (with the sizes that call
+ * accepts).  Returns the serial kernel (enum sc2_rans_dec_path), or 0 for sizes no decode call takes (n_streams <= 0,
+ * n_sym < 0, n_cdfs <= 0, cdf_stride < 3, implicit indexes with index_div <= 0).  *waves (may be NULL): waves per workgroup
+ * of SC2_RANS_DEC_RAGGED2 (1, 2, 4, 8), 1 for every other kernel.  *finish (may be NULL): the parallel pass behind the serial
+ * kernel, enum sc2_rans_dec_finish -- for implicit indexes what a call that asks for y_hat (fused_dq) resp. symbols_out runs; a
+ * fused call that also asks for symbols_out runs the transposition behind the dequantising pass; n_sym == 0 runs neither. */
+enum sc2_rans_dec_path {
+    SC2_RANS_DEC_LUT8 = 1,            /* one-lookup bucketed tables (policy rans_lut8), behind the table-building pre-pass */
+    SC2_RANS_DEC_LUT_U8 = 2,          /* two-lookup decoder, byte-sized lookup table: rows of up to 257 entries */
+    SC2_RANS_DEC_LUT_U16 = 3,         /* ... 16-bit lookup table: rows of up to 4 096 entries */
+    SC2_RANS_DEC_RAGGED2 = 4,         /* explicit indexes, four lanes per stream: more than 12 288 table entries, at most 64 rows */
+    SC2_RANS_DEC_RAGGED_8BIT = 5,     /* explicit indexes, one lane per stream, 256 buckets per row (policy rans_ragged2 = 0) */
+    SC2_RANS_DEC_RAGGED_5BIT = 6,     /* ... 32 buckets per row: 65 - 256 rows */
+    SC2_RANS_DEC_GENERIC_LDS = 7,     /* binary search on the rectangular table in LDS: at most 12 288 entries */
+    SC2_RANS_DEC_GENERIC_GLOBAL = 8   /* ... on the table in global memory */
+};
+enum sc2_rans_dec_finish {
+    SC2_RANS_FINISH_NONE = 0,         /* the serial kernel writes symbols_out itself (the generic kernels) */
+    SC2_RANS_FINISH_TRANSPOSE = 1,    /* [position][lane] intermediate -> symbols_out */
+    SC2_RANS_FINISH_DQ_REG = 2,       /* dequantise + NHWC transposition in registers: 8, 16, 24, 32 channels */
+    SC2_RANS_FINISH_DQ_LDS = 3        /* ... through LDS: the other channel counts, or policy rans_dq_lds */
+};
+int sc2_rans_decode_path(int explicit_indexes, int64_t index_div, int n_streams, int64_t n_sym, int n_cdfs, int cdf_stride,
+                         int fused_dq, int *waves, int *finish);
+
 /* ------------------------------------------------------------------------------------------ */
 /* Element-wise pieces of the distillation step (stage 1 of the Entropic-Student recipe:          */
 /* nn.MSELoss(reduction='sum') between student and teacher feature maps, yaml:155-200; ReLU       */

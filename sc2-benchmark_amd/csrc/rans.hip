@@ -519,7 +519,8 @@ __global__ __launch_bounds__(64) void rans_dec_lut_kernel(const RansArgs a) {
 // the far tails of a trained table) -- such a symbol, like an escape, sends its 8-symbol chunk to the exact path, which finds
 // the symbol by bisection over the row's starts.  The tables are built by a parallel pre-pass into the workspace
 // (rans_build_dec_table_kernel: one thread per bucket) and copied row by row into LDS.  Rows of up to 257 entries (symbol
-// index < 256).  Same symbols out, bit for bit (tests/test_gpu_kernels.py: every decoder test runs through this kernel).
+// index < 256).  Policy rans_lut8 = 1 only (the default is the two-lookup decoder above).  Same symbols out, bit for bit
+// (tests/test_gpu_rans_paths.py: the lut8 cases, among them a row of 257 entries with multi-boundary buckets).
 constexpr int kBucketShift = 3, kBucketsPerRow = 65536 >> kBucketShift;      // 8 192 buckets x 8 B = 64 KB per row
 
 __global__ __launch_bounds__(256) void rans_build_dec_table_kernel(const int32_t *__restrict__ cdfs, const int32_t *__restrict__ cdf_sizes,
@@ -1012,7 +1013,8 @@ __global__ __launch_bounds__(64) void rans_dec_ragged_kernel(const RansArgs a) {
 // round trips per symbol -- bucket, probes, {start, next} -- which is now what a symbol costs: ~570 cycles).  One wave per
 // workgroup (each with its own copy of the tables) is the fastest arrangement measured: 19.4 / 19.5 / 20.9 / 26.0 ms at 1 / 2 /
 // 4 / 8 waves per workgroup -- the chip is otherwise idle, and waves that share a CU share its LDS pipe.
-// Same bytes in, same symbols out (tests/test_gpu_hyperprior.py, tests/test_gpu_kernels.py).
+// Same bytes in, same symbols out (one wave: tests/test_gpu_hyperprior.py, tests/test_gpu_kernels.py; 2, 4 and 8 waves per
+// workgroup: tests/test_gpu_rans_paths.py).
 constexpr int kRagged2Cap = 45056;   // u16 entries of packed CDF rows incl. sentinels (88 KB) beside 32 KB of buckets and the 8 KB ring
 constexpr int kRagged2Rows = 64;
 constexpr int kProbe = 8;            // candidate entries examined by the speculative path
@@ -1269,11 +1271,10 @@ void allow_big_lds(K kernel, size_t bytes) {
                                   (int)bytes);
 }
 
-// the dequantising last pass of a decode launch: the register form where it applies, else the LDS form
-int launch_finish_dq(const RansArgs &a, const float *medians, void *y_hat, int n_cdfs, int HW, int n_blocks, hipStream_t s,
+// the dequantising last pass of a decode launch: the register form or the LDS form, as decode_plan chose
+int launch_finish_dq(const RansArgs &a, const float *medians, void *y_hat, int n_cdfs, int HW, int n_blocks, bool reg, hipStream_t s,
                             void *ev_dq_begin, void *ev_dq_end) {
     if (ev_dq_begin) (void)hipEventRecord(static_cast<hipEvent_t>(ev_dq_begin), s);
-    const bool reg = (n_cdfs == 24 || n_cdfs == 16 || n_cdfs == 8 || n_cdfs == 32) && !sc2_pol().rans_dq_lds;   // (rans_dq_lds = 1: A/B)
     if (reg) {
         const dim3 grid((unsigned)((HW + 7) / 8), (unsigned)n_blocks);
         uint16_t *y = static_cast<uint16_t *>(y_hat);
@@ -1368,6 +1369,55 @@ extern "C" int sc2_rans_encode_batch(const int32_t *symbols, const int32_t *inde
     return SC2_OK;
 }
 
+// Which kernels a decode call runs: a pure function of the call's sizes and the policy.  decode_impl switches on it and
+// sc2_rans_decode_path reports it (tests/ref_rans_paths.py restates it; tests/test_gpu_rans_paths.py holds the two together).
+struct DecPlan {
+    int path;     // enum sc2_rans_dec_path
+    int waves;    // SC2_RANS_DEC_RAGGED2: waves (of 16 streams) per workgroup
+    int finish;   // enum sc2_rans_dec_finish
+};
+
+static DecPlan decode_plan(bool explicit_indexes, int n_streams, int64_t n_sym, int n_cdfs, int cdf_stride, bool fused_dq) {
+    DecPlan p;
+    p.waves = 1;
+    const long long n_entries = (long long)n_cdfs * cdf_stride;
+    if (!explicit_indexes && cdf_stride <= kMaxRowLds) {
+        const bool lut8 = sc2_pol().rans_lut8 != 0;   // (0: A/B, the two-lookup decoder)
+        p.path = lut8 && dec_table_bytes(n_cdfs, cdf_stride) > 0 ? SC2_RANS_DEC_LUT8
+                 : cdf_stride <= 257 ? SC2_RANS_DEC_LUT_U8 : SC2_RANS_DEC_LUT_U16;
+        const bool reg = (n_cdfs == 24 || n_cdfs == 16 || n_cdfs == 8 || n_cdfs == 32) && !sc2_pol().rans_dq_lds;   // (rans_dq_lds = 1: A/B)
+        p.finish = n_sym == 0 ? SC2_RANS_FINISH_NONE : !fused_dq ? SC2_RANS_FINISH_TRANSPOSE : reg ? SC2_RANS_FINISH_DQ_REG : SC2_RANS_FINISH_DQ_LDS;
+        return p;
+    }
+    p.finish = SC2_RANS_FINISH_NONE;
+    if (explicit_indexes && n_entries > 12288 && n_cdfs <= kRaggedRows) {
+        p.finish = n_sym == 0 ? SC2_RANS_FINISH_NONE : SC2_RANS_FINISH_TRANSPOSE;
+        if (n_cdfs <= kRagged2Rows && sc2_pol().rans_ragged2 != 0) {   // (0: A/B)
+            // waves (of 16 streams) per workgroup behind one copy of the tables: 1 is the fastest for a launch that runs alone (19.4 /
+            // 19.5 / 20.9 / 26.0 ms at 1 / 2 / 4 / 8, round 4); a wide launch inside a pipeline pins 120 KB of LDS per workgroup
+            // for ~20 ms, and there two waves per workgroup win (half the CUs held: `bench.py --workload mshp224` 36.6 -> 39.3 k
+            // images/s at 2 048 streams per launch, tools/attic/mshp_sweep.sh).  Policy 0 = by stream count.
+            const int v = sc2_pol().rans_ragged2_waves;
+            p.waves = v <= 0 ? (n_streams >= 1024 ? 2 : 1) : v <= 1 ? 1 : v <= 2 ? 2 : v <= 4 ? 4 : 8;
+            p.path = SC2_RANS_DEC_RAGGED2;
+        } else {
+            p.path = n_cdfs <= 64 ? SC2_RANS_DEC_RAGGED_8BIT : SC2_RANS_DEC_RAGGED_5BIT;
+        }
+        return p;
+    }
+    p.path = n_entries <= 12288 ? SC2_RANS_DEC_GENERIC_LDS : SC2_RANS_DEC_GENERIC_GLOBAL;
+    return p;
+}
+
+extern "C" int sc2_rans_decode_path(int explicit_indexes, int64_t index_div, int n_streams, int64_t n_sym, int n_cdfs, int cdf_stride,
+                                    int fused_dq, int *waves, int *finish) {
+    if (n_streams <= 0 || n_sym < 0 || n_cdfs <= 0 || cdf_stride < 3 || (!explicit_indexes && index_div <= 0)) return 0;
+    const DecPlan p = decode_plan(explicit_indexes != 0, n_streams, n_sym, n_cdfs, cdf_stride, fused_dq != 0);
+    if (waves) *waves = p.waves;
+    if (finish) *finish = p.finish;
+    return p.path;
+}
+
 // medians / y_hat: the fused dequantised output of sc2_rans_decode_dequantize_batch (symbols_out may then be null)
 static int decode_impl(const uint8_t *in, int64_t in_stride, const int32_t *in_offset,
                        const int32_t *in_nbytes, const int32_t *indexes, int64_t index_div,
@@ -1402,8 +1452,34 @@ static int decode_impl(const uint8_t *in, int64_t in_stride, const int32_t *in_o
     const int n_blocks = (n_streams + 63) / 64;
     const int n_entries = n_cdfs * cdf_stride;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const bool lut8 = sc2_pol().rans_lut8 != 0;   // (0: A/B, the two-lookup decoder)
-    if (!indexes && lut8 && dec_table_bytes(n_cdfs, cdf_stride) > 0) {
+    const DecPlan plan = decode_plan(indexes != nullptr, n_streams, n_sym, n_cdfs, cdf_stride, y_hat != nullptr);
+    // the parallel passes behind a serial kernel that leaves the [position][lane] intermediate
+    auto finish = [&]() -> int {
+        if (n_sym == 0) return SC2_OK;
+        const long long gx = (n_sym + 63) / 64;
+        if (y_hat) {
+            if (const int rc = launch_finish_dq(a, medians, y_hat, n_cdfs, (int)index_div, n_blocks, plan.finish == SC2_RANS_FINISH_DQ_REG, s,
+                                                ev_dq_begin, ev_dq_end))
+                return rc;
+        }
+        if (symbols_out) {
+            hipLaunchKernelGGL(rans_dec_finish_kernel, dim3((unsigned)gx, n_blocks), dim3(256), 0, s, a);
+            SC2_CHECK_LAUNCH();
+        }
+        return SC2_OK;
+    };
+    if (n_sym > 0 && plan.path != SC2_RANS_DEC_GENERIC_LDS && plan.path != SC2_RANS_DEC_GENERIC_GLOBAL)
+        SC2_REQUIRE((n_sym + 63) / 64 < (1ll << 31) && n_blocks <= 65535, SC2_ERR_UNSUPPORTED, "rans_decode: problem too large");
+    // explicit indexes reach the ragged kernels transposed to [position][lane] in the workspace
+    auto transpose_in = [&]() -> int {
+        if (n_sym == 0) return SC2_OK;
+        hipLaunchKernelGGL(rans_transpose_in_kernel, dim3((unsigned)((n_sym + 63) / 64), n_blocks), dim3(256), 0, s, indexes, n_streams,
+                           (long long)n_sym, a.ws);
+        SC2_CHECK_LAUNCH();
+        return SC2_OK;
+    };
+    switch (plan.path) {
+    case SC2_RANS_DEC_LUT8: {
         // one LDS round trip per symbol: bucketed tables built by a parallel pre-pass into the workspace (behind the [position][lane]
         // intermediate), then the serial kernel
         const long long n_rows = n_sym == 0 ? 0 : (n_sym - 1) / a.index_div + 1;
@@ -1418,21 +1494,11 @@ static int decode_impl(const uint8_t *in, int64_t in_stride, const int32_t *in_o
         allow_big_lds(rans_dec_lut8_kernel, lds);
         hipLaunchKernelGGL(rans_dec_lut8_kernel, dim3(n_blocks), dim3(64), lds, s, a, gtab);
         SC2_CHECK_LAUNCH();
-        if (n_sym > 0) {
-            const long long gx = (n_sym + 63) / 64;
-            SC2_REQUIRE(gx < (1ll << 31) && n_blocks <= 65535, SC2_ERR_UNSUPPORTED, "rans_decode: problem too large");
-            if (y_hat) {
-                if (const int rc = launch_finish_dq(a, medians, y_hat, n_cdfs, (int)index_div, n_blocks, s, ev_dq_begin, ev_dq_end)) return rc;
-            }
-            if (symbols_out) {
-                hipLaunchKernelGGL(rans_dec_finish_kernel, dim3((unsigned)gx, n_blocks), dim3(256), 0, s, a);
-                SC2_CHECK_LAUNCH();
-            }
-        }
-        return SC2_OK;
+        return finish();
     }
-    if (!indexes && cdf_stride <= kMaxRowLds) {
-        const bool small = cdf_stride <= 257;   // symbol indexes fit a byte
+    case SC2_RANS_DEC_LUT_U8:
+    case SC2_RANS_DEC_LUT_U16: {
+        const bool small = plan.path == SC2_RANS_DEC_LUT_U8;   // symbol indexes fit a byte
         const size_t lds = lds_pad((size_t)65536 * (small ? 1 : 2) + (size_t)kWin * 64 * 4 + (size_t)cdf_stride * 4 + 16, n_blocks);
         if (small) {
             allow_big_lds(rans_dec_lut_kernel<uint8_t>, lds);
@@ -1442,72 +1508,38 @@ static int decode_impl(const uint8_t *in, int64_t in_stride, const int32_t *in_o
             hipLaunchKernelGGL(rans_dec_lut_kernel<uint16_t>, dim3(n_blocks), dim3(64), lds, s, a);
         }
         SC2_CHECK_LAUNCH();
-        if (n_sym > 0) {
-            const long long gx = (n_sym + 63) / 64;
-            SC2_REQUIRE(gx < (1ll << 31) && n_blocks <= 65535, SC2_ERR_UNSUPPORTED, "rans_decode: problem too large");
-            if (y_hat) {
-                if (const int rc = launch_finish_dq(a, medians, y_hat, n_cdfs, (int)index_div, n_blocks, s, ev_dq_begin, ev_dq_end)) return rc;
-            }
-            if (symbols_out) {
-                hipLaunchKernelGGL(rans_dec_finish_kernel, dim3((unsigned)gx, n_blocks), dim3(256), 0, s, a);
-                SC2_CHECK_LAUNCH();
-            }
-        }
-        return SC2_OK;
+        return finish();
     }
-    const bool ragged2 = sc2_pol().rans_ragged2 != 0;   // (0: A/B)
-    if (indexes && n_entries > 12288 && n_cdfs <= kRagged2Rows && ragged2) {
-        // waves (of 16 streams) per workgroup behind one copy of the tables: 1 is the fastest for a launch that runs alone (19.4 /
-        // 19.5 / 20.9 / 26.0 ms at 1 / 2 / 4 / 8, round 4); a wide launch inside a pipeline pins 120 KB of LDS per workgroup
-        // for ~20 ms, and there two waves per workgroup win (half the CUs held: `bench.py --workload mshp224` 36.6 -> 39.3 k
-        // images/s at 2 048 streams per launch, tools/attic/mshp_sweep.sh).  Policy 0 = by stream count.
-        const int waves = [n_streams] { const int v = sc2_pol().rans_ragged2_waves; return v <= 0 ? (n_streams >= 1024 ? 2 : 1) : v <= 1 ? 1 : v <= 2 ? 2 : v <= 4 ? 4 : 8; }();
+    case SC2_RANS_DEC_RAGGED2: {
+        const int waves = plan.waves;
         const size_t lds = (size_t)kRagged2Cap * 2 + (((size_t)kRagged2Rows * 257 * 2 + 15) & ~(size_t)15) + (size_t)kWin * 16 * waves * 4 +
                            (size_t)(3 * kRagged2Rows + 1) * 4 + 16;
         auto kern = waves == 1 ? rans_dec_ragged2_kernel<1> : waves == 2 ? rans_dec_ragged2_kernel<2> : waves == 4 ? rans_dec_ragged2_kernel<4> : rans_dec_ragged2_kernel<8>;
         allow_big_lds(kern, lds);
-        if (n_sym > 0) {
-            const long long gx = (n_sym + 63) / 64;
-            SC2_REQUIRE(gx < (1ll << 31) && n_blocks <= 65535, SC2_ERR_UNSUPPORTED, "rans_decode: problem too large");
-            hipLaunchKernelGGL(rans_transpose_in_kernel, dim3((unsigned)gx, n_blocks), dim3(256), 0, s, indexes, n_streams,
-                               (long long)n_sym, a.ws);
-            SC2_CHECK_LAUNCH();
-        }
+        if (const int rc = transpose_in()) return rc;
         hipLaunchKernelGGL(kern, dim3((n_blocks * 64 + 16 * waves - 1) / (16 * waves)), dim3(64 * waves), lds, s, a);
         SC2_CHECK_LAUNCH();
-        if (n_sym > 0) {
-            const long long gx = (n_sym + 63) / 64;
-            hipLaunchKernelGGL(rans_dec_finish_kernel, dim3((unsigned)gx, n_blocks), dim3(256), 0, s, a);
-            SC2_CHECK_LAUNCH();
-        }
-        return SC2_OK;
+        return finish();
     }
-    if (indexes && n_entries > 12288 && n_cdfs <= kRaggedRows) {
-        const int bits = n_cdfs <= 64 ? 8 : 5;   // 257 / 33 bucket bounds per row: 33 KB / 17 KB at the largest row count
+    case SC2_RANS_DEC_RAGGED_8BIT:
+    case SC2_RANS_DEC_RAGGED_5BIT: {
+        const int bits = plan.path == SC2_RANS_DEC_RAGGED_8BIT ? 8 : 5;   // 257 / 33 bucket bounds per row: 33 KB / 17 KB at the largest row count
         const size_t lds = (size_t)kRaggedCap * 2 + (size_t)(3 * n_cdfs + 1) * 4 +
                            (size_t)n_cdfs * ((1 << bits) + 1) * 2 + 16;
         if (bits == 8) allow_big_lds(rans_dec_ragged_kernel<8>, lds);
         else allow_big_lds(rans_dec_ragged_kernel<5>, lds);
-        if (n_sym > 0) {
-            const long long gx = (n_sym + 63) / 64;
-            SC2_REQUIRE(gx < (1ll << 31) && n_blocks <= 65535, SC2_ERR_UNSUPPORTED, "rans_decode: problem too large");
-            hipLaunchKernelGGL(rans_transpose_in_kernel, dim3((unsigned)gx, n_blocks), dim3(256), 0, s, indexes, n_streams,
-                               (long long)n_sym, a.ws);
-            SC2_CHECK_LAUNCH();
-        }
+        if (const int rc = transpose_in()) return rc;
         if (bits == 8) hipLaunchKernelGGL(rans_dec_ragged_kernel<8>, dim3(n_blocks), dim3(64), lds, s, a);
         else hipLaunchKernelGGL(rans_dec_ragged_kernel<5>, dim3(n_blocks), dim3(64), lds, s, a);
         SC2_CHECK_LAUNCH();
-        if (n_sym > 0) {
-            const long long gx = (n_sym + 63) / 64;
-            hipLaunchKernelGGL(rans_dec_finish_kernel, dim3((unsigned)gx, n_blocks), dim3(256), 0, s, a);
-            SC2_CHECK_LAUNCH();
-        }
-        return SC2_OK;
-    } else if (n_entries <= 12288) {
+        return finish();
+    }
+    case SC2_RANS_DEC_GENERIC_LDS:
         hipLaunchKernelGGL(rans_dec_generic_kernel<true>, dim3(n_blocks), dim3(64), (size_t)n_entries * 4, s, a);
-    } else {
+        break;
+    default:
         hipLaunchKernelGGL(rans_dec_generic_kernel<false>, dim3(n_blocks), dim3(64), 0, s, a);
+        break;
     }
     SC2_CHECK_LAUNCH();
     return SC2_OK;

@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     'sc2_eb_forward', 'sc2_eb_backward', 'sc2_eb_bits_partial_len', 'sc2_eb_backward_planes_per_wg', 'sc2_eb_symbols', 'sc2_eb_dequantize',
     'sc2_gc_forward', 'sc2_gc_backward', 'sc2_gc_symbols_indexes', 'sc2_gc_dequantize',
     'sc2_pmf_to_quantized_cdf',
-    'sc2_rans_max_bytes', 'sc2_rans_workspace_bytes', 'sc2_rans_encode_batch', 'sc2_rans_decode_batch', 'sc2_rans_decode_dequantize_batch', 'sc2_rans_decode_dequantize_batch_ev',
+    'sc2_rans_max_bytes', 'sc2_rans_workspace_bytes', 'sc2_rans_encode_batch', 'sc2_rans_decode_batch', 'sc2_rans_decode_dequantize_batch', 'sc2_rans_decode_dequantize_batch_ev', 'sc2_rans_decode_path',
     'sc2_mse_partial_len', 'sc2_mse_sum_bf16', 'sc2_mse_grad_bf16', 'sc2_relu_bwd_bf16', 'sc2_relu_bwd_mse_bf16',
     'sc2_gdn_bwd_pre_blocks', 'sc2_colsum_blocks', 'sc2_gdn_bwd_post_blocks', 'sc2_layout_blocks', 'sc2_gdn1_rows_units', 'sc2_gdn1_rows_workgroups',
     'sc2_ar_scan', 'sc2_ar_scan_f32', 'sc2_rans_decode_resume',
@@ -334,6 +334,7 @@ def lib():
                                         vp]
     L.sc2_rans_decode_dequantize_batch.argtypes = [vp, i64, vp, vp, i64, i32, i64, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     L.sc2_rans_decode_dequantize_batch_ev.argtypes = [vp, i64, vp, vp, i64, i32, i64, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]
+    L.sc2_rans_decode_path.argtypes = [i32, i64, i32, i64, i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     L.sc2_mse_partial_len.argtypes = [ctypes.c_longlong]
     L.sc2_mse_sum_bf16.argtypes = [vp, vp, ctypes.c_longlong, vp, vp]
     L.sc2_mse_grad_bf16.argtypes = [vp, vp, ctypes.c_longlong, vp, vp, vp]
@@ -3096,6 +3097,22 @@ def rans_decode_dequantize_batch(buf, off, nb, n_sym, cdfs, cdf_sizes, offsets, 
 def rans_decode_dequantize_supported(n_cdfs, cdf_stride):
     """True if sc2_rans_decode_dequantize_batch takes these tables (channel count % 8 == 0, <= 64, rows within the LUT decoder)."""
     return n_cdfs % 8 == 0 and n_cdfs <= 64 and cdf_stride <= 4096 and host_policy.rans_fused_dq
+
+
+# sc2_rans_decode_path: enum sc2_rans_dec_path / sc2_rans_dec_finish of include/sc2_bottleneck.h by name
+RANS_DEC_PATHS = {1: 'lut8', 2: 'lut-u8', 3: 'lut-u16', 4: 'ragged2', 5: 'ragged-8bit', 6: 'ragged-5bit', 7: 'generic-lds', 8: 'generic-global'}
+RANS_DEC_FINISHES = {0: 'none', 1: 'transpose', 2: 'dq-reg', 3: 'dq-lds'}
+
+
+def rans_decode_path(explicit_indexes, index_div, n_streams, n_sym, n_cdfs, cdf_stride, fused_dq=False):
+    """Which kernels a decode call of these sizes runs under the policy in force (no launch): -> (serial kernel, waves per workgroup,
+    finishing pass) by the names above; the decision the decode entry points switch on."""
+    waves, finish = ctypes.c_int32(0), ctypes.c_int32(0)
+    path = int(lib().sc2_rans_decode_path(int(bool(explicit_indexes)), int(index_div), int(n_streams), int(n_sym), int(n_cdfs), int(cdf_stride),
+                                          int(bool(fused_dq)), ctypes.byref(waves), ctypes.byref(finish)))
+    if path not in RANS_DEC_PATHS:
+        raise Sc2Error('rans_decode_path: no decode call takes these sizes')
+    return RANS_DEC_PATHS[path], waves.value, RANS_DEC_FINISHES[finish.value]
 
 
 def rans_decode_batch(buf, off, nb, n_sym, cdfs, cdf_sizes, offsets, indexes=None, index_div=0):

@@ -931,10 +931,12 @@ def test_avgpool_nhwc(S, dev, N, H, W, C):
     assert torch.equal(b16, f32.to(torch.bfloat16))
 
 
-@pytest.mark.parametrize('N,C,H,W', [(3, 24, 55, 55), (2, 24, 7, 9), (5, 6, 16, 16), (2, 25, 10, 10)])
+@pytest.mark.parametrize('N,C,H,W', [(3, 24, 55, 55), (2, 24, 7, 9), (5, 6, 16, 16), (2, 25, 10, 10), (2, 6, 7, 9), (2, 6, 17, 17)])
 def test_dequantize_layouts(S, dev, N, C, H, W):
     """symbols + medians -> f32 NCHW and bf16 NHWC in one launch: both exact (tile-transposed form for even C, ragged last
-    pixel tile, a row base that is not 16-byte aligned; plane form for odd C)."""
+    pixel tile, a row base that is not 16-byte aligned; plane form for odd C).  (2, 6, 7, 9): an image is 63 * 6 * 2 = 756 bytes,
+    so image 1 starts at 756 = 4 (mod 16) -- the 4-byte store branch -- and image 0's aligned run ends in a 4-byte tail -- the
+    byte-wise loop; (2, 6, 17, 17): 289 * 12 = 3 468 bytes = 12 (mod 16), a second, ragged pixel tile on a misaligned base."""
     g = torch.Generator().manual_seed(N * C + W)
     sym = torch.randint(-40, 40, (N, C, H, W), generator=g, dtype=torch.int32).to(dev)
     med = torch.randn(C, generator=g).to(dev)
