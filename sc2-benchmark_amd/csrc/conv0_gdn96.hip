@@ -12,8 +12,10 @@
 //   conv    A fragments straight from the staged rows (consecutive pixels = consecutive 16-byte pairs), W0 fragments
 //           FRAGMENT-MAJOR from L2 into registers; wave (wm, wn) owns output row wm x channels [48 wn, 48 wn + 48);
 //   GDN1    |t| (bf16) goes to an LDS image [224 px][96 ch] (rows padded to 208 B: conflict-free fragment reads),
-//           norm = beta + gamma |t| is a second GEMM with gamma fragment-major from L2, y = t / norm on the f32
-//           accumulators, written to the image and streamed out as one contiguous 43 KB block.
+//           norm = beta + gamma |t| is a second GEMM with gamma fragment-major from L2 (|t| enters it ROUNDED TO bf16),
+//           y = t * rcp(norm) with t the f32 accumulator and rcp the hardware reciprocal (__builtin_amdgcn_rcpf, 1 ulp:
+//           NOT the IEEE division of the precise modes; inverse: t * norm), one rounding to bf16, written to the image
+//           and streamed out as one contiguous 43 KB block.
 // Units are claimed with one atomic each, one unit ahead (claim c means unit c + 2 * gridDim.x; a launch makes exactly
 // n_units claims, and the one that draws n_units - 1 writes the counter back to zero: no preset launch).  Geometry: any
 // width -- an output row is cut into segments of OW = 112 pixels (one segment for the 224-pixel-wide input; 513 x 513 ->

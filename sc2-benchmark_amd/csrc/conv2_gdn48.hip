@@ -18,8 +18,9 @@
 //   * every wave accumulates partial sums for the WHOLE 112 x 48 tile; they are added up through LDS in two rounds of
 //     four pixel tiles (48 KB), pixel tile 4 r + w summed by wave w, which then owns all 48 channels of its 16 pixels;
 //   * GDN1(48) is therefore wave-local: |t| (bf16) to the wave's own rows of an LDS image (no barrier), norm = beta +
-//     gamma |t| as six more MFMAs per owned tile (gamma fragments in LDS), y = t / norm, bf16 to a 10.5 KB output image
-//     that is one contiguous block of the NHWC output.
+//     gamma |t| as six more MFMAs per owned tile (gamma fragments in LDS; |t| enters them ROUNDED TO bf16), y = t * rcp(norm)
+//     with t the f32 sum and rcp the hardware reciprocal (__builtin_amdgcn_rcpf, 1 ulp: NOT the IEEE division of the precise
+//     modes; inverse: t * norm), one rounding to bf16 into a 10.5 KB output image that is one contiguous block of the NHWC output.
 // Units are claimed dynamically, two ahead, from one counter per XCD (claim c = local unit c + 2 x workgroups of the
 // XCD; an XCD makes exactly as many claims as it has units, and the last one re-arms its counter).
 #include <stdio.h>

@@ -15,7 +15,8 @@
 //     one per CU, XCD-contiguous tile ranges);
 //   * fused inverse GDN1: the tile's conv output goes to a bf16 image in LDS (32 channel-chunk planes of 224 rows),
 //     norm = gamma |x| is a second GEMM over the image (8 k-steps, gamma fragments through the same register ring),
-//     y = x * (beta + norm) with x read back from the lane's own image slots; 14 sixteen-byte stores per lane.
+//     y = x * (beta + norm) (non-inverse: x * (1.0f / (beta + norm)), IEEE division then one multiply) with x read back
+//     from the lane's own image slots -- the bf16 value in both places; 14 sixteen-byte stores per lane.
 //     Same operation order per output element as the tile kernels: results are bit-identical to theirs.
 #include <stdlib.h>
 

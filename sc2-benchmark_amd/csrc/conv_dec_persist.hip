@@ -399,7 +399,8 @@ __global__ __launch_bounds__(512, 2) void conv_igemm8p_kernel(const ConvArgs p, 
         unsigned char *img = smem;
         if (fused) {
             // conv followed by GDN1 / inverse GDN1: x -> image, norm = gamma |x| as a second GEMM (gamma fragment-major
-            // from L2 into registers, one step ahead), y = x * (beta + norm) or x / (...) in place in the image
+            // from L2 into registers, one step ahead), y = x * (beta + norm) or x * (1.0f / (...)) (IEEE division, then one
+            // multiply) in place in the image: x is the image's bf16 value in both places
 #pragma unroll
             for (int i = 0; i < MT; ++i)
 #pragma unroll

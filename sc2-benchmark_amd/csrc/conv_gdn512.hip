@@ -16,8 +16,9 @@
 //            64-deep step (the k order inside a step is permuted identically for both operands so that the four
 //            lanes of a row fetch one whole line).  No barrier inside the phase: the two waves of a SIMD drift
 //            apart and one issues MFMAs while the other waits for its loads.
-//   epilogue y = t * (beta + norm) in f32, written back IN PLACE into the image (each 8-byte slot belongs to one
-//            lane), then the 128 KB tile - contiguous in the NHWC output - is streamed out in 16-byte stores.
+//   epilogue y = t * (beta + norm) in f32 (non-inverse: t * (1.0f / (beta + norm)), IEEE division then one multiply; t is
+//            the image's bf16 value here as in phase 2), written back IN PLACE into the image (each 8-byte slot belongs
+//            to one lane), then the 128 KB tile - contiguous in the NHWC output - is streamed out in 16-byte stores.
 // HBM traffic per tile: 128 x Cin x 2 B in (x taps overlap in L2), 128 KB out.
 #include <stdlib.h>
 

@@ -533,7 +533,10 @@ __device__ __forceinline__ void conv_store_tile_f32(const ConvArgs &p, unsigned 
 
 // Fused GDN1 / inverse GDN1 of a tile that holds every output channel of its pixels (BN <= 96): norm = beta + gamma |x|
 // is a second, LDS-resident GEMM - |x| (bf16) is written to an LDS image straight from the accumulators, gamma is staged
-// next to it, and y = x / norm (or x * norm) is applied to the f32 accumulators: the GDN costs no HBM traffic.
+// next to it, and y = x * (1.0f / norm) (IEEE division, then one multiply; inverse: x * norm) is applied to the f32
+// accumulators: |x| enters the second GEMM rounded to bf16, the product takes the unrounded f32 x.  The GDN costs no HBM traffic.
+// (The stand-alone SC2_EPI_GDN / _IGDN epilogues of conv_store_tile* above: x is the caller's bf16 tensor in both places, the
+//  same IEEE division and one multiply.)
 // Call with the LDS idle; returns with the LDS idle.
 template <class C>
 __device__ __forceinline__ void conv_fused_gdn_small(const ConvArgs &p, unsigned char *smem, f32x4_t (&acc)[C::MT][C::NT],

@@ -15,6 +15,13 @@ Bias: f32 integers in {-4..4}; residuals: bf16 integers in {-3..3}.  `check_boun
 for a case.  References run on the CPU in f64 (F.conv2d, conv_transpose2d, autograd for the weight gradient); the test applies
 the kernel's documented epilogue in f64 and `cast` rounds ONCE to the output type.
 
+GDN1 with a live gamma: `gdn_params` draws gamma with three entries from {1/2, 1, 2} per row and column and beta from {1, 2, 3}, so
+n = beta + gamma |t| is a multiple of 1/2 and an exact f32 number in any summation order (`gdn_norm` asserts it).  The forward form
+r = 1.0f / n, y = t * r is then two correctly rounded f32 operations on exact operands -- the same bits on the CPU as on the device --
+and `gdn_restate` is that arithmetic in torch float32, with the precision (f32 accumulator or its bf16 rounding) in which t enters the
+second GEMM and the product as parameters.  `gdn_admissible` gives, for the two kernels that multiply by the hardware reciprocal
+(within 1 ulp), the bf16 results under r and its two f32 neighbours; `assert_bits_in` compares with such a set.
+
 `arena(t)` puts an operand between two guard bands of NaN (integer types: a large sentinel) inside a larger buffer, so that a
 read past an operand -- even one multiplied by a zero weight -- poisons the output, and a write past an output shows in
 `bands_untouched`.  Only memory the test owns is read or written."""
@@ -45,6 +52,28 @@ def gen(*seed):
 def wide(shape, g):
     """f32 tensor of integers uniform in {-3..3}."""
     return torch.randint(-3, 4, tuple(shape), generator=g).float()
+
+
+def wide_amplitude(K):
+    """The GDN1 cases' wide set at short K: with {-3..3} a sum of K < 512 products stays a bf16-exact integer (4 sqrt(K) < 90), and
+    whether a kernel takes t as its f32 accumulator or rounded to bf16 could not be seen.  Integers up to 8 (K >= 128) or 15 are
+    still exact in bf16, their products exact in f32, and the sums reach past 256."""
+    return 3 if K >= 512 else 8 if K >= 128 else 15
+
+
+def narrow_amplitude(K):
+    """The GDN1 cases' narrow set at short K: {-1, 0, 1} leaves |t| <= 8 or so at K = 8 .. 100, mostly powers of two, for which
+    t * (1 / n) IS the rounded t / n -- the order of operations could not be seen.  The largest a with a (a + 1) sqrt(K) <= 120
+    (uniform {-a..a}: std(t) = a (a + 1) sqrt(K) / 3 <= 40, so max|t| <= 256 still holds and is still asserted); 1: the plain set."""
+    a = 1
+    while (a + 1) * (a + 2) * math.sqrt(max(int(K), 1)) <= 120.0:
+        a += 1
+    return a
+
+
+def wide_to(shape, a, g):
+    """f32 tensor of integers uniform in {-a..a}."""
+    return torch.randint(-int(a), int(a) + 1, tuple(shape), generator=g).float()
 
 
 def narrow_p(K):
@@ -163,6 +192,90 @@ def cast(ref64, dtype):
     return f32.to(dtype)
 
 
+# --------------------------------------------------------------------------------------------- #
+# GDN1 with a live gamma: y = t * (1 / (beta + gamma |t|))  (inverse: t * (beta + gamma |t|))
+# --------------------------------------------------------------------------------------------- #
+GAMMA_VALUES = (0.5, 1.0, 2.0)
+GAMMA_DIAGONALS = 3
+
+
+def live_gamma(C, g):
+    """[C, C] with three random (cyclic) diagonals: every row and every column holds exactly three entries, each from {1/2, 1, 2}."""
+    C = int(C)
+    assert C >= GAMMA_DIAGONALS
+    offs = torch.randperm(C, generator=g)[:GAMMA_DIAGONALS]
+    vals = torch.tensor(GAMMA_VALUES)[torch.randint(0, len(GAMMA_VALUES), (GAMMA_DIAGONALS, C), generator=g)]
+    gamma = torch.zeros(C, C)
+    rows = torch.arange(C)
+    for d in range(GAMMA_DIAGONALS):
+        gamma[rows, (rows + int(offs[d])) % C] = vals[d]
+    assert bool(((gamma != 0).sum(0) == GAMMA_DIAGONALS).all()) and bool(((gamma != 0).sum(1) == GAMMA_DIAGONALS).all())
+    return gamma
+
+
+def gdn_params(kind, C, g, inverse, tmax=None):
+    """(gamma [C, C], beta [C], label) variants of one GDN1: the SAME three kinds of variant for both directions and both operand sets
+    (`kind` is only validated and `inverse` is not used: they are taken so that a call names its case, and the values differ from case
+    to case through the generator `g` alone).  gamma = 0: beta 1 -> the conv itself,
+    beta 2 -> exactly half / double.  'live gamma': `live_gamma` and beta in {1, 2, 3} -- the norm is then a multiple of 1/2, a sum of
+    non-negative terms, and (tmax given: asserted here; always asserted by gdn_restate) stays under EXACT_LIMIT quanta of 1/2: exact
+    in f32 in any summation order."""
+    assert kind in ('wide', 'narrow')
+    out = [(torch.zeros(C, C), torch.ones(C), 'gamma 0 beta 1'), (torch.zeros(C, C), torch.full((C,), 2.0), 'gamma 0 beta 2')]
+    gamma = live_gamma(C, g)
+    beta = torch.randint(1, 4, (int(C),), generator=g).float()
+    if tmax is not None:
+        assert 2 * (3 + GAMMA_DIAGONALS * max(GAMMA_VALUES) * float(tmax)) < EXACT_LIMIT
+    out.append((gamma, beta, 'live gamma'))
+    return out
+
+
+def _in_precision(t64, dtype):
+    """The exact f64 conv output as the f32 tensor a kernel holds it in: the f32 accumulator, or that rounded once to bf16."""
+    assert dtype in (torch.float32, torch.bfloat16)
+    f32 = t64.to(torch.float32)
+    assert torch.equal(f32.double(), t64), 't is not exact in f32'
+    return f32 if dtype == torch.float32 else f32.to(torch.bfloat16).float()
+
+
+def gdn_norm(t64, gamma, beta, t_gemm):
+    """n = beta + gamma |cast(t, t_gemm)| (NCHW), computed in f64 and asserted to be an exact f32 number below EXACT_LIMIT quanta
+    of 1/2 (every term is non-negative, so n is the sum of magnitudes: any partial sum in any order is exact as well) -> f32."""
+    assert bool((gamma >= 0).all()) and bool((beta > 0).all())
+    assert torch.equal(gamma * 2, (gamma * 2).round()) and torch.equal(beta * 2, (beta * 2).round())
+    a = _in_precision(t64, t_gemm).double().abs()
+    n64 = torch.einsum('oc,nchw->nohw', gamma.double(), a) + beta.double().view(1, -1, 1, 1)
+    assert torch.equal(n64 * 2, (n64 * 2).round())
+    assert float(n64.max()) * 2 < EXACT_LIMIT, 'norm of {} half quanta >= 2^24'.format(float(n64.max()) * 2)
+    n32 = n64.to(torch.float32)
+    assert torch.equal(n32.double(), n64)
+    return n32
+
+
+def gdn_restate(t64, gamma, beta, inverse, t_gemm, t_prod, out_dtype):
+    """A kernel's documented GDN1 arithmetic in torch float32 on the CPU (IEEE, no fused operations), NCHW:
+        n = beta + gamma |cast(t, t_gemm)|                  (exact, see gdn_norm)
+        forward: r = f32(1) / n (correctly rounded), y = f32(cast(t, t_prod)) * r;      inverse: y = f32(cast(t, t_prod)) * n
+    then ONE cast to out_dtype.  t_gemm / t_prod: torch.float32 (the accumulator) or torch.bfloat16 (the accumulator rounded once)."""
+    n = gdn_norm(t64, gamma, beta, t_gemm)
+    tp = _in_precision(t64, t_prod)
+    y = tp * n if inverse else tp * (torch.ones((), dtype=torch.float32) / n)
+    assert y.dtype == torch.float32
+    return y.to(out_dtype)
+
+
+def gdn_admissible(t64, gamma, beta, t_gemm, t_prod, out_dtype=torch.bfloat16):
+    """The forward GDN1 of a kernel whose reciprocal is the hardware's (v_rcp_f32: within 1 ulp of 1 / n, so one of the correctly
+    rounded r and its two f32 neighbours): -> ([cast(t * r') for r' in (r, below, above)], mask of the elements where these differ)."""
+    n = gdn_norm(t64, gamma, beta, t_gemm)
+    tp = _in_precision(t64, t_prod)
+    r = torch.ones((), dtype=torch.float32) / n
+    zero, inf = torch.zeros_like(r), torch.full_like(r, float('inf'))
+    cands = [(tp * rr).to(out_dtype) for rr in (r, torch.nextafter(r, zero), torch.nextafter(r, inf))]
+    many = (cands[1] != cands[0]) | (cands[2] != cands[0])
+    return cands, many
+
+
 def nhwc(t):
     return t.permute(0, 2, 3, 1).contiguous()
 
@@ -219,6 +332,30 @@ def assert_bits_equal(got, ref, what, layout='nhwc'):
         elif single['n']:
             lines.append('=> all in ONE image')
     raise AssertionError('\n  '.join(lines))
+
+
+def assert_bits_in(got, candidates, what, layout='nhwc'):
+    """Every element of `got` equals that element of at least ONE of `candidates` (same shape and dtype each; NaN equals nothing);
+    on failure: the number of elements that match no candidate and the first such coordinate with got / the candidates there."""
+    got = got.detach().cpu()
+    cands = [c.detach().cpu() for c in candidates]
+    assert cands, '{}: no candidates'.format(what)
+    for c in cands:
+        assert got.shape == c.shape, '{}: shape {} != {}'.format(what, tuple(got.shape), tuple(c.shape))
+        assert got.dtype == c.dtype, '{}: dtype {} != {}'.format(what, got.dtype, c.dtype)
+    ok = torch.zeros(got.shape, dtype=torch.bool)
+    for c in cands:
+        ok |= got == c
+    if bool(ok.all()):
+        return
+    if got.dim() == 4 and layout == 'nchw':
+        got, ok, cands = got.permute(0, 2, 3, 1), ok.permute(0, 2, 3, 1), [c.permute(0, 2, 3, 1) for c in cands]
+    names = ('n', 'oh', 'ow', 'c') if got.dim() == 4 else tuple('d{}'.format(i) for i in range(got.dim()))
+    idx = (~ok).nonzero()
+    first = tuple(int(v) for v in idx[0])
+    raise AssertionError('{}: {} of {} elements match none of the {} admissible values\n  first at ({}) = {}: got {!r}, admissible {}'.format(
+        what, idx.shape[0], ok.numel(), len(cands), ', '.join(names), first, got[first].item(),
+        sorted(set(c[first].item() for c in cands))))
 
 
 # --------------------------------------------------------------------------------------------- #

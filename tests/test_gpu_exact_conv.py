@@ -8,7 +8,8 @@ Every operand a case hands to a wrapper sits in a NaN arena (>= 64 KB of NaN on 
 output.  Where a wrapper takes `out=`, the output sits in an arena too and its bands are asserted untouched.
 
 There is no tolerance in this file: every comparison is torch.equal (through exact_ints.assert_bits_equal, which names the first
-mismatching coordinate and the index sets the mismatches span) or an integer equality.
+mismatching coordinate and the index sets the mismatches span), membership in a set of at most three exact values
+(exact_ints.assert_bits_in: the two hardware-reciprocal kernels) or an integer equality.
 
 Cases come from each family's `*_supported` predicate and tile constants:
   conv2d_fwd          128-pixel tiles (generic 32 / 48 / 64 / 96 / 128-row tiles), 256-pixel 8-wave tiles, K slabs of 32, ring of 2 - 4
@@ -17,11 +18,18 @@ Cases come from each family's `*_supported` predicate and tile constants:
   conv1x1_pair        112-pixel tiles;  conv2x2_win 4 rows x 55-column segments;  conv2x2_c48 16-pixel tiles;  fc 128-row tiles
   conv2d_wgrad        32-pixel slabs, 128-column tiles;  conv2d_f32 / split 128-pixel tiles, 32-pixel units of the persistent first stage
 
-Cases set aside (a kernel's documented arithmetic is not integer-closed there):
-  * the forward GDN1's division with gamma != 0 (all fused families): stays with the tolerance tests, as its division is not integer-closed; the
-    forward form is pinned here with gamma = 0 (beta = 1: the conv itself; beta = 2: exactly half).  Nothing else is set aside.
-(EPI_FUSED_* of the 256-wide tiles: the conv output enters the normalisation as bf16 -- documented: the LDS image -- so the reference
-casts it to bf16 first and stays zero-tolerance, f32 outputs on the wide set included.)
+GDN1 with a live gamma (nothing is set aside): the forward form's division is not integer-closed, but it is two IEEE f32 operations
+on exact operands.  gamma has three entries from {1/2, 1, 2} per row and column and beta is in {1, 2, 3}, so n = beta + gamma |t| is a
+multiple of 1/2, exact in f32 in any summation order; r = 1.0f / n and y = t * r (inverse: y = t * n) then give the same bits on the CPU
+as on the device, and exact_ints.gdn_restate IS that arithmetic in torch float32.  What differs between the kernel families -- whether
+t enters the second GEMM, and the product, as the f32 accumulator or rounded to bf16 -- is the GDN_FAMILIES table below, each row
+taken from the family's own comment.  Every fused-GDN test runs gamma = 0 (beta 1: the conv itself; beta 2: exactly half / double)
+and the live gamma, forward and inverse, on both operand sets, f32 and bf16 outputs; conv0_gdn96 and conv2_gdn48, whose forward form
+multiplies by the hardware reciprocal (within 1 ulp), must hit one of the bf16 values admissible under it (assert_bits_in) -- a
+single value on the narrow set and on all but < 0.1 % of the wide set's elements.  tests/test_exact_ints_cpu.py proves on the
+references alone, for exactly these cases, that the norms are exact, that t * (1 / n) and t / n differ on > 5 % of the f32
+outputs (the order of operations is visible), how few elements are ambiguous, and that a dropped gamma entry, swapped gamma rows or
+columns, a beta added behind the reciprocal and the other precision of |t| each change the expected bits.
 
 Not in arenas: conv2d_dgrad packs its sub-filters and conv2d_wgrad / the wrappers without `out=` allocate their outputs inside the
 wrapper, so those packed weights and outputs are ordinary allocations; x, dY and the weight given to the wrapper are in arenas.
@@ -93,8 +101,10 @@ def out_shape(S, fmt, N, cout, OH, OW):
     return (N, cout, OH, OW), torch.float32 if fmt == hip.OUT_F32_NCHW else torch.int32
 
 
-def conv2d(S, dev, xd, wp, cout, k, stride, pad, ref64, what, fmt=None, **kw):
-    """One sc2_conv2d_fwd launch into an output arena, compared with the f64 reference (NCHW) cast once; bands checked."""
+def conv2d(S, dev, xd, wp, cout, k, stride, pad, ref64, what, fmt=None, restate=None, **kw):
+    """One sc2_conv2d_fwd launch into an output arena, compared with the f64 reference (NCHW) cast once; bands checked.
+    restate: a function of the output dtype that gives the wanted NCHW tensor itself (the GDN1 restatements, whose f32 operations
+    round), ref64 then only carries the shape."""
     hip = S.hip
     fmt = hip.OUT_BF16_NHWC if fmt is None else fmt
     kh, kw_ = (k, k) if isinstance(k, int) else k
@@ -105,7 +115,8 @@ def conv2d(S, dev, xd, wp, cout, k, stride, pad, ref64, what, fmt=None, **kw):
     torch.cuda.synchronize()
     assert got.data_ptr() == out.data_ptr()
     nchw = fmt in (hip.OUT_F32_NCHW, hip.OUT_I32_NCHW_SYM)
-    want = E.cast(ref64, dtype)
+    want = E.cast(ref64, dtype) if restate is None else restate(dtype)
+    assert want.dtype == dtype
     E.assert_bits_equal(got, want if nchw else E.nhwc(want), what, layout='nchw' if nchw else 'nhwc')
     E.assert_bands_untouched(out, what)
     return got
@@ -856,71 +867,150 @@ def test_precise_convs_operand_ops(S, dev, kind, a_op, cin, cout, k, H, W, N):
         E.assert_bits_equal(got, want_nhwc(ref, torch.float32), '{} a_op {} {}->{} k{} {}'.format(mode, a_op, cin, cout, k, kind))
 
 
-def _gdn_params(kind, C, g, inverse):
-    """(gamma [C, C], beta [C], label) variants.  gamma = 0: beta 1 -> the conv itself, beta 2 -> exactly half / double.  Inverse form
-    on the narrow set: sparse gamma in {0, 1} and integer beta keep t (beta + sum gamma |t|) an integer."""
-    out = [(torch.zeros(C, C), torch.ones(C), 'gamma 0 beta 1'), (torch.zeros(C, C), torch.full((C,), 2.0), 'gamma 0 beta 2')]
-    if inverse and kind == 'narrow':
-        gamma = (torch.rand(C, C, generator=g) < 3.0 / C).float()
-        out.append((gamma, torch.randint(1, 4, (C,), generator=g).float(), 'sparse gamma'))
-    return out
+# --------------------------------------------------------------------------------------------- #
+# GDN1 with a live gamma, bit for bit: the arithmetic each kernel family documents
+# --------------------------------------------------------------------------------------------- #
+F32 = torch.float32
+# family -> (precision in which t = the conv output enters the second GEMM as |t|, precision in which it enters the final product,
+#            the reciprocal of the forward form).  'ieee': r = 1.0f / n, correctly rounded, then ONE multiply t * r -- restated on the
+# CPU by exact_ints.gdn_restate and compared with assert_bits_equal; 'rcpf': the hardware reciprocal (within 1 ulp), compared with
+# assert_bits_in against exact_ints.gdn_admissible.  The inverse form is t * n in every family (one f32 multiply).  Each row is what
+# the family's own comment states, csrc/ file and line of that comment:
+GDN_FAMILIES = {
+    # conv_fused_gdn_small: "|x| enters the second GEMM rounded to bf16, the product takes the unrounded f32 x", "IEEE division, then one multiply"
+    'small tiles': (BF16, F32, 'ieee'),           # conv_igemm_impl.h:534-539; code: pack_bf16x2(acc) & 0x7FFF7FFF -> Xi; acc * (1.0f / norm)
+    # conv_store_tile / conv_store_tile_f32 with SC2_EPI_GDN / _IGDN: ep_x is the caller's bf16 tensor, read for the GEMM (a_op ABS) and the product
+    'tile epilogue': (BF16, BF16, 'ieee'),        # conv_igemm_impl.h:537-538; code: xv[t] * (1.0f / norm) at 269, 476, 511
+    # the 256-wide tiles and their persistent form: "x is the image's bf16 value in both places", "IEEE division, then one multiply"
+    '256-wide tiles': (BF16, BF16, 'ieee'),       # conv_igemm_impl.h:1002-1005 ("x goes to an LDS image as bf16 ... x read back from the image"), conv_dec_persist.hip:401-403
+    # "t is rounded to bf16 into the LDS IMAGE", "t is the image's bf16 value here as in phase 2", "IEEE division then one multiply"
+    'conv_gdn512': (BF16, BF16, 'ieee'),          # conv_gdn512.hip:13-21
+    # "x read back from the lane's own image slots -- the bf16 value in both places", "IEEE division then one multiply"
+    'conv2x2_win': (BF16, BF16, 'ieee'),          # conv2x2_win.hip:16-20
+    # modes f32, bf16x3, bf16x6: "norm = gamma |x| consumes [the accumulators] in place" (f32) / "norm = gamma |acc| as a split GEMM"; the
+    # one epilogue: "norm = beta + acc, IEEE division, one multiply"
+    'precise': (F32, F32, 'ieee'),                # conv_precise.h:6-8, conv_f32.hip:263-267, conv_split.hip:211-212
+    # "|t| enters it ROUNDED TO bf16", "y = t * rcp(norm) with t the f32 accumulator and rcp the hardware reciprocal"
+    'conv0_gdn96': (BF16, F32, 'rcpf'),           # conv0_gdn96.hip:14-18
+    'conv2_gdn48': (BF16, F32, 'rcpf'),           # conv2_gdn48.hip:20-23
+}
+
+FUSED_PRECISE = [(4, 96, 5, 2, 2, 21, 18, 3), (96, 48, 5, 2, 2, 9, 30, 1), (8, 32, 3, 1, 1, 1, 129, 1), (4, 20, 1, 1, 0, 7, 5, 1)]
+FIRST_STAGE = [(1, 224, 224), (3, 9, 14), (1, 2, 62), (1, 2, 64), (1, 2, 66), (1, 1, 2)]
+FUSED_SMALL = [(96, 48, 5, 2, 2, 13, 10, 3), (16, 96, 3, 1, 1, 1, 129, 1), (24, 64, 2, 1, 1, 7, 9, 1), (8, 32, 1, 1, 0, 1, 1, 1)]
+FUSED_BIG = [(512, 2, 0, 11, 10, 3), (64, 1, 0, 1, 257, 1), (256, 2, 1, 15, 15, 1)]
+CONV0_GDN96 = [(1, 224, 224), (3, 11, 224), (1, 5, 226), (1, 4, 2), (3, 6, 40), (1, 3, 448)]
+CONV2_GDN48 = [(1, 112, 112), (3, 9, 112), (1, 3, 111), (1, 4, 113), (1, 1, 1), (3, 5, 30), (1, 2, 257)]
+GDN512 = [(24, 1, 27, 27), (24, 3, 7, 9), (16, 1, 1, 126), (8, 1, 1, 127), (24, 1, 1, 128), (8, 1, 1, 1), (16, 3, 5, 20)]
+WIN_FUSED = [(512, 0, 1, 56, 56), (128, 1, 3, 6, 55), (64, 0, 1, 5, 111), (64, 1, 3, 1, 1), (64, 0, 1, 6, 57)]
+TILE_EPILOGUE = [(C, M) for C in (48, 40) for M in (1, 128, 129)]
+# test -> (family, cases, case -> (cin, cout, k, stride, pad, H, W, N) of the convolution in front of the GDN1).  tests/test_exact_ints_cpu.py
+# walks this table: what it proves on the CPU, it proves for the operands the tests below hand to the kernels.
+GDN_TESTS = {
+    'test_precise_fused_gdn_exact': ('precise', FUSED_PRECISE, lambda c: c),
+    'test_precise_first_stage_on_the_image': ('precise', FIRST_STAGE, lambda c: (3, 96, 5, 2, 2, c[1], c[2], c[0])),
+    'test_conv2d_fused_gdn_small_tiles_exact': ('small tiles', FUSED_SMALL, lambda c: c),
+    'test_conv2d_fused_gdn_big_tile_exact': ('256-wide tiles', FUSED_BIG, lambda c: (c[0], 256, c[1], 1, c[2], c[3], c[4], c[5])),
+    'test_conv0_gdn96_exact': ('conv0_gdn96', CONV0_GDN96, lambda c: (3, 96, 5, 2, 2, c[1], c[2], c[0])),
+    'test_conv2_gdn48_exact': ('conv2_gdn48', CONV2_GDN48, lambda c: (96, 48, 5, 2, 2, c[1], c[2], c[0])),
+    'test_conv2x2_gdn512_exact': ('conv_gdn512', GDN512, lambda c: (c[0], 512, 2, 1, 1, c[2], c[3], c[1])),
+    'test_conv2x2_win_fused_gdn_exact': ('conv2x2_win', WIN_FUSED, lambda c: (c[0], 256, 2, 1, c[1], c[3], c[4], c[2])),
+    'test_gdn1_tile_epilogue_exact': ('tile epilogue', TILE_EPILOGUE, None),
+}
 
 
-def _gdn_ref(t64, gamma, beta, inverse):
-    """t (beta + gamma |t|) or t / (beta + gamma |t|) in f64, NCHW."""
-    norm = torch.einsum('oc,nchw->nohw', gamma.double(), t64.abs()) + beta.double().view(1, -1, 1, 1)
-    return t64 * norm if inverse else t64 / norm
+# (test, case, kind, inverse) -> another seed, where test_exact_ints_cpu.py found the first one's operands blind to one of its mutants:
+# at the single output pixel of a 1 x 1 / 1 x 2 map, swapping gamma's first two columns did not change the expected bits
+GDN_RESEED = {('test_precise_first_stage_on_the_image', (1, 1, 2), 'narrow', True): 1}
+
+
+def gdn_case(test, kind, inverse, case):
+    """-> (family, x, w, t, params): the operands of one case of one test above, its exact conv output t (f64 NCHW) and the
+    (gamma, beta, label) variants -- drawn ONCE per case, after the operands, from the case's generator.  (The stand-alone GDN1 has no
+    conv: x is then the integer tensor before its rounding to bf16, the operand of the precise modes' launches, and w is None.)"""
+    family, _, geom = GDN_TESTS[test]
+    if geom is None:                 # the stand-alone GDN1: t IS the bf16 input tensor [1, C, 1, M]
+        C, M = case
+        g = E.gen(C, M, inverse, kind == 'wide')
+        t = torch.randint(-4000, 4001, (1, C, 1, M), generator=g) if kind == 'wide' else torch.randint(-256, 257, (1, C, 1, M), generator=g)
+        x = t.double()                           # the integers themselves (wide: not bf16-exact): what the precise modes take as f32
+        t = t.float().to(BF16).double()          # wide: integers rounded to bf16 (still integers); narrow: |t| <= 256 is bf16-exact
+        w = None
+        cout = C
+    else:
+        cin, cout, k, s, p, H, W, N = geom(case)
+        kh, kw = (k, k) if isinstance(k, int) else k
+        g, K, x, w = operands(kind, cin, cout, k, H, W, N, seed=int(inverse) + 2 * GDN_RESEED.get((test, case, kind, inverse), 0))
+        live = cin * min(kh, H) * min(kw, W)                    # the taps that can lie inside the map: a 1 x 1 map under a 5 x 5 filter has one
+        if kind == 'wide' and E.wide_amplitude(live) != 3:      # short K: larger integers, so that |t| leaves the bf16-exact integers
+            x, w = E.wide_to(x.shape, E.wide_amplitude(live), g), E.wide_to(w.shape, E.wide_amplitude(live), g)
+        if kind == 'narrow' and E.narrow_amplitude(live) != 1:   # short K: a few more values, so that |t| is not a handful of powers of two
+            x, w = E.wide_to(x.shape, E.narrow_amplitude(live), g), E.wide_to(w.shape, E.narrow_amplitude(live), g)
+        E.check_bound(K, x, w)
+        t = E.conv_ref(x, w, s, p)
+    if kind == 'narrow':
+        E.check_narrow(t)
+    params = E.gdn_params(kind, cout, g, inverse, tmax=float(t.abs().max()))
+    return family, x, w, t, params
+
+
+def gdn_restated(family, t, gamma, beta, inverse, dtype):
+    t_gemm, t_prod, _ = GDN_FAMILIES[family]
+    return E.gdn_restate(t, gamma, beta, inverse, t_gemm, t_prod, dtype)
+
+
+def assert_gdn(family, got_nhwc, t, gamma, beta, inverse, label, what):
+    """bf16 / f32 NHWC output of one launch against the family's restatement: bit-equal, but for the forward live-gamma form of the two
+    hardware-reciprocal kernels, which must hit one of the admissible values (a single one almost everywhere: test_exact_ints_cpu.py)."""
+    t_gemm, t_prod, rcp = GDN_FAMILIES[family]
+    if rcp == 'rcpf' and not inverse and label == 'live gamma':
+        cands, _ = E.gdn_admissible(t, gamma, beta, t_gemm, t_prod, got_nhwc.dtype)
+        E.assert_bits_in(got_nhwc, [E.nhwc(c) for c in cands], what)
+    else:
+        E.assert_bits_equal(got_nhwc, E.nhwc(E.gdn_restate(t, gamma, beta, inverse, t_gemm, t_prod, got_nhwc.dtype)), what)
 
 
 @pytest.mark.parametrize('kind', KINDS)
 @pytest.mark.parametrize('inverse', [False, True])
-@pytest.mark.parametrize('cin,cout,k,s,p,H,W,N', [(4, 96, 5, 2, 2, 21, 18, 3), (96, 48, 5, 2, 2, 9, 30, 1), (8, 32, 3, 1, 1, 1, 129, 1), (4, 20, 1, 1, 0, 7, 5, 1)])
+@pytest.mark.parametrize('cin,cout,k,s,p,H,W,N', FUSED_PRECISE)
 def test_precise_fused_gdn_exact(S, dev, kind, inverse, cin, cout, k, s, p, H, W, N):
     hip = S.hip
-    g, K, x, w = operands(kind, cin, cout, k, H, W, N, seed=inverse)
-    E.check_bound(K, x, w)
-    t = E.conv_ref(x, w, s, p)
-    if kind == 'narrow':
-        E.check_narrow(t)
+    family, x, w, t, params = gdn_case('test_precise_fused_gdn_exact', kind, inverse, (cin, cout, k, s, p, H, W, N))
     xd = X(x, dev, torch.float32)
     for mode in ('f32', 'bf16x3', 'bf16x6'):
         pack, fwd = _precise(S, mode)
         wf = A(pack(w.to(dev)), dev)
-        for gamma, beta, label in _gdn_params(kind, cout, g, inverse):
+        for gamma, beta, label in params:
             got = fwd(xd, wf, cout, k, k, s, p, epilogue=hip.EPI_FUSED_IGDN if inverse else hip.EPI_FUSED_GDN,
                       ep_x=A(pack(gamma.reshape(cout, cout, 1, 1).to(dev)), dev), ep_beta=A(beta, dev))
             torch.cuda.synchronize()
-            E.assert_bits_equal(got, want_nhwc(_gdn_ref(t, gamma, beta, inverse), torch.float32),
-                                '{} fused {} {}->{} {} {}'.format(mode, 'IGDN' if inverse else 'GDN', cin, cout, label, kind))
+            assert_gdn(family, got, t, gamma, beta, inverse, label,
+                       '{} fused {} {}->{} {} {}'.format(mode, 'IGDN' if inverse else 'GDN', cin, cout, label, kind))
 
 
 @pytest.mark.parametrize('kind', KINDS)
 @pytest.mark.parametrize('inverse', [False, True])
 @pytest.mark.parametrize('persist', ['1', '0'])
-@pytest.mark.parametrize('N,H,W', [(1, 224, 224), (3, 9, 14), (1, 2, 62), (1, 2, 64), (1, 2, 66), (1, 1, 2)])
+@pytest.mark.parametrize('N,H,W', FIRST_STAGE)
 def test_precise_first_stage_on_the_image(S, dev, monkeypatch, kind, inverse, persist, N, H, W):
     """x_is_nchw_rgb: the f32 NCHW image read in place; conv0 + GDN1(96) as the persistent first stage (32-pixel units: 1 x 31 / 32 /
     33 output pixels) and as its tile form (SC2_F32_PERSIST0=0); the split modes on the same image."""
     hip = S.hip
     monkeypatch.setenv('SC2_F32_PERSIST0', persist)
-    g, K, x, w = operands(kind, 3, 96, 5, H, W, N, seed=inverse)
-    E.check_bound(K, x, w)
-    t = E.conv_ref(x, w, 2, 2)
-    if kind == 'narrow':
-        E.check_narrow(t)
+    family, x, w, t, params = gdn_case('test_precise_first_stage_on_the_image', kind, inverse, (N, H, W))
     xd = A(x, dev)
+    wants = [E.nhwc(gdn_restated(family, t, gamma, beta, inverse, F32)) for gamma, beta, _ in params]      # once, shared by the modes
     for mode in ('f32', 'bf16x3', 'bf16x6'):
         pack, fwd = _precise(S, mode)
         wf = A(pack(w.to(dev)), dev)
         got = fwd(xd, wf, 96, 5, 5, 2, 2, x_is_nchw_rgb=True)
         torch.cuda.synchronize()
         E.assert_bits_equal(got, want_nhwc(t, torch.float32), '{} conv0 on the image {}x{}x{} {}'.format(mode, N, H, W, kind))
-        for gamma, beta, label in _gdn_params(kind, 96, g, inverse):
+        for (gamma, beta, label), want in zip(params, wants):
             got = fwd(xd, wf, 96, 5, 5, 2, 2, x_is_nchw_rgb=True, epilogue=hip.EPI_FUSED_IGDN if inverse else hip.EPI_FUSED_GDN,
                       ep_x=A(pack(gamma.reshape(96, 96, 1, 1).to(dev)), dev), ep_beta=A(beta, dev))
             torch.cuda.synchronize()
-            E.assert_bits_equal(got, want_nhwc(_gdn_ref(t, gamma, beta, inverse), torch.float32),
-                                '{} first stage persist {} {}x{}x{} {} {}'.format(mode, persist, N, H, W, label, kind))
+            E.assert_bits_equal(got, want, '{} first stage persist {} {}x{}x{} {} {}'.format(mode, persist, N, H, W, label, kind))
 
 
 # --------------------------------------------------------------------------------------------- #
@@ -928,156 +1018,163 @@ def test_precise_first_stage_on_the_image(S, dev, monkeypatch, kind, inverse, pe
 # --------------------------------------------------------------------------------------------- #
 @pytest.mark.parametrize('kind', KINDS)
 @pytest.mark.parametrize('inverse', [False, True])
-@pytest.mark.parametrize('cin,cout,k,s,p,H,W,N', [(96, 48, 5, 2, 2, 13, 10, 3), (16, 96, 3, 1, 1, 1, 129, 1), (24, 64, 2, 1, 1, 7, 9, 1), (8, 32, 1, 1, 0, 1, 1, 1)])
+@pytest.mark.parametrize('cin,cout,k,s,p,H,W,N', FUSED_SMALL)
 def test_conv2d_fused_gdn_small_tiles_exact(S, dev, kind, inverse, cin, cout, k, s, p, H, W, N):
     """EPI_FUSED_GDN / _IGDN of the 32 / 48 / 64 / 96-row tiles, f32 and bf16 outputs."""
     hip = S.hip
-    g, K, x, w = operands(kind, cin, cout, k, H, W, N, seed=inverse)
-    E.check_bound(K, x, w)
-    t = E.conv_ref(x, w, s, p)
-    if kind == 'narrow':
-        E.check_narrow(t)
+    family, x, w, t, params = gdn_case('test_conv2d_fused_gdn_small_tiles_exact', kind, inverse, (cin, cout, k, s, p, H, W, N))
     xd, wp = X(x, dev), A(hip.pack_conv_weight(w.to(dev)), dev)
     assert hip.conv_fused_gdn_supported(tuple(xd.shape), cout, k, k, s, p) == 1
-    for gamma, beta, label in _gdn_params(kind, cout, g, inverse):
+    for gamma, beta, label in params:
         gd = A(hip.pack_conv_weight(gamma.reshape(cout, cout, 1, 1).to(dev)), dev)
         for fmt in (hip.OUT_BF16_NHWC, hip.OUT_F32_NCHW):
-            conv2d(S, dev, xd, wp, cout, k, s, p, _gdn_ref(t, gamma, beta, inverse),
+            conv2d(S, dev, xd, wp, cout, k, s, p, t,
                    'fused {} {}->{} fmt {} {} {}'.format('IGDN' if inverse else 'GDN', cin, cout, fmt, label, kind), fmt=fmt,
+                   restate=lambda dt: gdn_restated(family, t, gamma, beta, inverse, dt),
                    epilogue=hip.EPI_FUSED_IGDN if inverse else hip.EPI_FUSED_GDN, ep_x=gd, ep_beta=A(beta, dev))
 
 
 @pytest.mark.parametrize('kind', KINDS)
 @pytest.mark.parametrize('inverse', [False, True])
 @pytest.mark.parametrize('half', ['0', '1', 'r4'])
-@pytest.mark.parametrize('cin,k,pad,H,W,N', [(512, 2, 0, 11, 10, 3), (64, 1, 0, 1, 257, 1), (256, 2, 1, 15, 15, 1)])
+@pytest.mark.parametrize('cin,k,pad,H,W,N', FUSED_BIG)
 def test_conv2d_fused_gdn_big_tile_exact(S, dev, monkeypatch, kind, inverse, half, cin, k, pad, H, W, N):
-    """conv + GDN1(256) in one launch of the 256-wide tiles (forced), the 128-row twins and the 4-wave register tile."""
+    """conv + GDN1(256) in one launch of the 256-wide tiles (forced), the 128-row twins and the 4-wave register tile.  Documented: the
+    conv output enters the second GEMM and the final product as bf16 (the LDS image)."""
     hip = S.hip
     monkeypatch.setenv('SC2_CONV_FORCE_BIG', '1')
     monkeypatch.setenv('SC2_CONV_HALF', '0' if half == 'r4' else half)
     monkeypatch.setenv('SC2_CONV_BIG4', '1' if half == 'r4' else '0')
     cout = 256
-    g, K, x, w = operands(kind, cin, cout, k, H, W, N, seed=inverse)
-    E.check_bound(K, x, w)
-    t = E.conv_ref(x, w, 1, pad)
-    if kind == 'narrow':
-        E.check_narrow(t)
+    family, x, w, t, params = gdn_case('test_conv2d_fused_gdn_big_tile_exact', kind, inverse, (cin, k, pad, H, W, N))
     xd, wp = X(x, dev), A(hip.pack_conv_weight(w.to(dev)), dev)
     assert hip.conv_fused_gdn_supported(tuple(xd.shape), cout, k, k, 1, pad) == 2
-    for gamma, beta, label in _gdn_params(kind, cout, g, inverse):
+    for gamma, beta, label in params:
         gd = A(hip.pack_gamma_fragments(gamma.to(dev)), dev)
-        tb = E.cast(t, BF16).double()      # documented: the conv output enters the second GEMM and the final product as bf16 (LDS image)
         for fmt in (hip.OUT_BF16_NHWC, hip.OUT_F32_NHWC):
-            conv2d(S, dev, xd, wp, cout, k, 1, pad, _gdn_ref(tb, gamma, beta, inverse),
+            conv2d(S, dev, xd, wp, cout, k, 1, pad, t,
                    'big fused {} {} k{} half {} fmt {} {} {}'.format('IGDN' if inverse else 'GDN', cin, k, half, fmt, label, kind), fmt=fmt,
+                   restate=lambda dt: gdn_restated(family, t, gamma, beta, inverse, dt),
                    epilogue=hip.EPI_FUSED_IGDN if inverse else hip.EPI_FUSED_GDN, ep_x=gd, ep_beta=A(beta, dev))
 
 
 @pytest.mark.parametrize('kind', KINDS)
 @pytest.mark.parametrize('inverse', [False, True])
-@pytest.mark.parametrize('N,H,W', [(1, 224, 224), (3, 11, 224), (1, 5, 226), (1, 4, 2), (3, 6, 40), (1, 3, 448)])
+@pytest.mark.parametrize('N,H,W', CONV0_GDN96)
 def test_conv0_gdn96_exact(S, dev, kind, inverse, N, H, W):
     """The persistent first stage of the bf16 encoder: 112-pixel output segments (224: the static geometry; 226 -> 112 + 1; a single
     pixel pair; 448 -> two whole segments); y and the emitted conv output t; the in-place NCHW form."""
     hip = S.hip
-    g, K, x, w = operands(kind, 3, 96, 5, H, W, N, seed=inverse)
-    E.check_bound(K, x, w)
-    t = E.conv_ref(x, w, 2, 2)
-    if kind == 'narrow':
-        E.check_narrow(t)
+    family, x, w, t, params = gdn_case('test_conv0_gdn96_exact', kind, inverse, (N, H, W))
     x4 = torch.zeros(N, H, W, 4)
     x4[..., :3] = E.nhwc(x)
     xp = A(x4.to(BF16).view(N, H, W // 2, 8), dev)
     assert hip.conv0_gdn96_supported(tuple(xp.shape), 96)
     wf = A(hip.pack_weight_fragments(hip.pack_conv0_weight_pairs(w.to(dev))[:96]), dev)
     xn = A(x, dev)
-    for gamma, beta, label in _gdn_params(kind, 96, g, inverse):
+    for gamma, beta, label in params:
         gf, bd = A(hip.pack_gamma_fragments(gamma.to(dev)), dev), A(beta, dev)
         tag = 'conv0+gdn96 {}x{}x{} inverse {} {} {}'.format(N, H, W, inverse, label, kind)
-        want = want_nhwc(_gdn_ref(t, gamma, beta, inverse))
         y, tt = hip.conv0_gdn96_fwd(xp, wf, gf, bd, inverse, want_t=True)
         torch.cuda.synchronize()
-        E.assert_bits_equal(y, want, tag)
+        assert_gdn(family, y, t, gamma, beta, inverse, label, tag)
         E.assert_bits_equal(tt, want_nhwc(t), tag + ' t')
         y = hip.conv0_gdn96_fwd(xp, wf, gf, bd, inverse)
         torch.cuda.synchronize()
-        E.assert_bits_equal(y, want, tag + ' (no t)')
+        assert_gdn(family, y, t, gamma, beta, inverse, label, tag + ' (no t)')
         y = hip.conv0_gdn96_nchw_fwd(xn, wf, gf, bd, inverse)
         torch.cuda.synchronize()
-        E.assert_bits_equal(y, want, tag + ' nchw in place')
+        assert_gdn(family, y, t, gamma, beta, inverse, label, tag + ' nchw in place')
 
 
 @pytest.mark.parametrize('kind', KINDS)
 @pytest.mark.parametrize('inverse', [False, True])
-@pytest.mark.parametrize('N,H,W', [(1, 112, 112), (3, 9, 112), (1, 3, 111), (1, 4, 113), (1, 1, 1), (3, 5, 30), (1, 2, 257)])
+@pytest.mark.parametrize('N,H,W', CONV2_GDN48)
 def test_conv2_gdn48_exact(S, dev, kind, inverse, N, H, W):
     """The persistent second stage: W = 112 is static, any other width runs 56-column output segments (111 -> 56; 113 -> 56 + 1;
     257 -> 56 + 56 + 17)."""
     hip = S.hip
-    g, K, x, w = operands(kind, 96, 48, 5, H, W, N, seed=inverse)
-    E.check_bound(K, x, w)
-    t = E.conv_ref(x, w, 2, 2)
-    if kind == 'narrow':
-        E.check_narrow(t)
+    family, x, w, t, params = gdn_case('test_conv2_gdn48_exact', kind, inverse, (N, H, W))
     xd = X(x, dev)
     assert hip.conv2_gdn48_supported(tuple(xd.shape), 48, 5, 5, 2, 2)
     wp = A(hip.pack_conv_weight(w.to(dev), hip.K_SLAB_MAJOR | hip.K_B_FRAG_MAJOR), dev)
-    for gamma, beta, label in _gdn_params(kind, 48, g, inverse):
+    for gamma, beta, label in params:
         gf = A(hip.pack_weight_fragments(hip.pack_conv_weight(gamma.reshape(48, 48, 1, 1).to(dev))), dev)
         bd = A(beta, dev)
         tag = 'conv2+gdn48 {}x{}x{} inverse {} {} {}'.format(N, H, W, inverse, label, kind)
-        want = want_nhwc(_gdn_ref(t, gamma, beta, inverse))
         y, tt = hip.conv2_gdn48_fwd(xd, wp, gf, bd, inverse, want_t=True)
         torch.cuda.synchronize()
-        E.assert_bits_equal(y, want, tag)
+        assert_gdn(family, y, t, gamma, beta, inverse, label, tag)
         E.assert_bits_equal(tt, want_nhwc(t), tag + ' t')
         y = hip.conv2_gdn48_fwd(xd, wp, gf, bd, inverse)
         torch.cuda.synchronize()
-        E.assert_bits_equal(y, want, tag + ' (no t)')
+        assert_gdn(family, y, t, gamma, beta, inverse, label, tag + ' (no t)')
 
 
 @pytest.mark.parametrize('kind', KINDS)
 @pytest.mark.parametrize('inverse', [False, True])
-@pytest.mark.parametrize('cin,N,H,W', [(24, 1, 27, 27), (24, 3, 7, 9), (16, 1, 1, 126), (8, 1, 1, 127), (24, 1, 1, 128), (8, 1, 1, 1), (16, 3, 5, 20)])
+@pytest.mark.parametrize('cin,N,H,W', GDN512)
 def test_conv2x2_gdn512_exact(S, dev, kind, inverse, cin, N, H, W):
     """decoder[0] + GDN1(512): 128-pixel tiles (2 x 127 = 254, 2 x 128 = 256, 2 x 129 = 258 output pixels)."""
     hip = S.hip
     assert hip.conv2x2_gdn512_supported(cin, 512, 2, 2, 1, 1)
-    g, K, x, w = operands(kind, cin, 512, 2, H, W, N, seed=inverse)
-    E.check_bound(K, x, w)
-    t = E.conv_ref(x, w, 1, 1)
-    if kind == 'narrow':
-        E.check_narrow(t)
+    family, x, w, t, params = gdn_case('test_conv2x2_gdn512_exact', kind, inverse, (cin, N, H, W))
     xd, wp = X(x, dev), A(hip.pack_conv_weight(w.to(dev)), dev)
-    for gamma, beta, label in _gdn_params(kind, 512, g, inverse):
+    for gamma, beta, label in params:
         gf, bd = A(hip.pack_gamma_fragments(gamma.to(dev)), dev), A(beta, dev)
         tag = 'conv2x2+gdn512 {} {}x{}x{} inverse {} {} {}'.format(cin, N, H, W, inverse, label, kind)
-        want = want_nhwc(_gdn_ref(t, gamma, beta, inverse))
         y, tt = hip.conv2x2_gdn512_fwd(xd, wp, gf, bd, inverse, want_t=True)
         torch.cuda.synchronize()
-        E.assert_bits_equal(y, want, tag)
+        assert_gdn(family, y, t, gamma, beta, inverse, label, tag)
         E.assert_bits_equal(tt, want_nhwc(t), tag + ' t')
         y = hip.conv2x2_gdn512_fwd(xd, wp, gf, bd, inverse)
         torch.cuda.synchronize()
-        E.assert_bits_equal(y, want, tag + ' (no t)')
+        assert_gdn(family, y, t, gamma, beta, inverse, label, tag + ' (no t)')
 
 
 @pytest.mark.parametrize('kind', KINDS)
 @pytest.mark.parametrize('inverse', [False, True])
-@pytest.mark.parametrize('cin,pad,N,H,W', [(512, 0, 1, 56, 56), (128, 1, 3, 6, 55), (64, 0, 1, 5, 111), (64, 1, 3, 1, 1), (64, 0, 1, 6, 57)])
+@pytest.mark.parametrize('cin,pad,N,H,W', WIN_FUSED)
 def test_conv2x2_win_fused_gdn_exact(S, dev, kind, inverse, cin, pad, N, H, W):
     """conv2x2_win_fwd with beta: the GDN1 behind the decoder conv in the window-plane kernel."""
     hip = S.hip
-    g, K, x, w = operands(kind, cin, 256, 2, H, W, N, seed=inverse)
-    E.check_bound(K, x, w)
-    t = E.conv_ref(x, w, 1, pad)
-    if kind == 'narrow':
-        E.check_narrow(t)
+    family, x, w, t, params = gdn_case('test_conv2x2_win_fused_gdn_exact', kind, inverse, (cin, pad, N, H, W))
     xd = X(x, dev)
-    for gamma, beta, label in _gdn_params(kind, 256, g, inverse):
+    for gamma, beta, label in params:
         wf = A(hip.pack_conv2x2_win(w.to(dev), gamma.to(dev)), dev)
         got = hip.conv2x2_win_fwd(xd, wf, pad, beta=A(beta, dev), inverse=inverse)
         torch.cuda.synchronize()
-        E.assert_bits_equal(got, want_nhwc(_gdn_ref(t, gamma, beta, inverse)),
-                            '2x2 win fused {} p{} {}x{}x{} inverse {} {} {}'.format(cin, pad, N, H, W, inverse, label, kind))
+        assert_gdn(family, got, t, gamma, beta, inverse, label,
+                   '2x2 win fused {} p{} {}x{}x{} inverse {} {} {}'.format(cin, pad, N, H, W, inverse, label, kind))
+
+
+@pytest.mark.parametrize('kind', KINDS)
+@pytest.mark.parametrize('inverse', [False, True])
+@pytest.mark.parametrize('C,M', TILE_EPILOGUE)
+def test_gdn1_tile_epilogue_exact(S, dev, kind, inverse, C, M):
+    """The stand-alone GDN1 at widths the resident-row kernels refuse (C = 48: a whole 48-row tile; C = 40: a partial one; M = one
+    pixel, one 128-pixel tile, one more): conv2d_fwd(a_op=AOP_ABS, epilogue=EPI_GDN / EPI_IGDN, ep_x=x) with bf16 and f32 outputs, and
+    the same launch of the three precise modes (their stand-alone epilogue: f32 in both places) on the f32 tensor of the integers
+    BEFORE their rounding to bf16 -- on the wide set most of them are not bf16-exact, so a norm or a product taken from a bf16 value
+    would show."""
+    hip = S.hip
+    family, t32, _, t, params = gdn_case('test_gdn1_tile_epilogue_exact', kind, inverse, (C, M))
+    xd = X(t, dev)
+    assert torch.equal(xd.cpu().double(), E.nhwc(t))          # t is bf16-exact: the tensor the kernel reads IS t
+    assert not hip.gdn1_rows_supported(xd, C)
+    assert kind == 'narrow' or not torch.equal(t32, t)
+    x32 = X(t32, dev, torch.float32)
+    epi = hip.EPI_IGDN if inverse else hip.EPI_GDN
+    for gamma, beta, label in params:
+        tag = 'GDN1 tile epilogue C {} M {} inverse {} {} {}'.format(C, M, inverse, label, kind)
+        gd, bd = A(hip.pack_conv_weight(gamma.reshape(C, C, 1, 1).to(dev)), dev), A(beta, dev)
+        for fmt in (hip.OUT_BF16_NHWC, hip.OUT_F32_NHWC, hip.OUT_F32_NCHW):
+            conv2d(S, dev, xd, gd, C, 1, 1, 0, t, '{} fmt {}'.format(tag, fmt), fmt=fmt,
+                   restate=lambda dt: gdn_restated(family, t, gamma, beta, inverse, dt), a_op=hip.AOP_ABS, epilogue=epi, ep_x=xd, ep_beta=bd)
+        for mode in ('f32', 'bf16x3', 'bf16x6'):
+            pack, fwd = _precise(S, mode)
+            got = fwd(x32, A(pack(gamma.reshape(C, C, 1, 1).to(dev)), dev), C, 1, 1, 1, 0, a_op=hip.AOP_ABS, epilogue=epi, ep_x=x32, ep_beta=bd)
+            torch.cuda.synchronize()
+            assert_gdn('precise', got, t32, gamma, beta, inverse, label, '{} mode {}'.format(tag, mode))
+
+
